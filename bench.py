@@ -12,18 +12,25 @@ across ranks with no data-path collective ("weak" scaling); the only collectives
 barrier and the max-reduce of the elapsed time.
 
 Protocol, independent of --warmup: an untimed burn-in of episode_length + 50 control steps brings the
-fall/reset distribution to its stationary regime, then W warm-up steps, then the K timed steps -- ONE HIP-graph
-replay bracketed by barrier + synchronize -- are repeated 5 times and the MEDIAN repeat is reported (each repeat is
-exactly K steps; max over ranks per repeat).  `roofline.kernel_ms_avg` comes from HIP events recorded on the launch
-stream around the SAME replays, so it can never exceed ms_per_step.
+fall/reset distribution to its stationary regime, then W warm-up steps, then exactly K timed steps -- ONE HIP-graph
+replay of K step launches bracketed by barrier + synchronize (max over ranks).  ms_per_step = that time / K.
+`roofline.kernel_ms_avg` comes from HIP events recorded on the launch stream around the SAME replay, so it can never
+exceed ms_per_step.
 
-Prints ONE JSON line: value = whole-job env-steps/s, `roofline` (algorithmic bytes of SURVEY.md 8d / that kernel time;
+Prints ONE JSON line: value = whole-job env-steps/s and `roofline` (algorithmic bytes of SURVEY.md 8d / that kernel time;
 HBM traffic, VALU issue rate and FP32 rate from the committed rocprofv3 PMC passes -- only while the loaded library IS the
-one they were measured on, by hash), `f64` (the same workload on the engine's double-precision instantiation: the reference's
-arithmetic is fp64 until agents/ppo/envs.py:192), `cpu_baseline` (the fp64 oracle timed on the host cores per BASELINE.md
-section 3: 64 and 4096 envs, median of 5, all granted cores and one thread; rank 0, N=1 only) and `ppo_loop` (the full PPO
-iteration of BASELINE config 3 with the README recipe, median of 3 iterations; with N > 1 every optimizer step carries the
-80 KB RCCL all-reduce of the flat gradient bucket).
+one they were measured on, by hash).
+
+--dump-outputs DIR: after the timed steps, what the last timed step returned to its caller (observations, rewards, done
+flags, the info arrays) is written as DIR/<name>.npy in float32 (ranks > 0 of a multi-GPU run: <name>.rank<r>.npy).  The
+inputs (env seed, action tensor, step counts) depend only on the arguments, so two builds can be compared output for output.
+
+--full adds the auxiliary legs, each measured after the headline: `repeats_ms_per_step` (REPEATS more replays of the same
+graph: the spread), `f64` (the same workload on the engine's double-precision instantiation: the reference's arithmetic is
+fp64 until agents/ppo/envs.py:192), `cpu_baseline` (the fp64 oracle timed on the host cores per BASELINE.md section 3: 64
+and 4096 envs, median of 5, all granted cores and one thread; rank 0, N=1 only) and `ppo_loop` (the full PPO iteration of
+BASELINE config 3 with the README recipe, median of 3 iterations; with N > 1 every optimizer step carries the 80 KB RCCL
+all-reduce of the flat gradient bucket).  --no-f64, --no-cpu-baseline, --ppo-steps 0 drop single legs of --full.
 """
 import argparse
 import hashlib
@@ -45,7 +52,8 @@ EPISODE_LENGTH = 400
 HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP32_VECTOR_PEAK_TF = 157.3     # MI355X_MICROARCH.md: peak FP32 (vector)
 VALU_ISSUE_PEAK = 256 * 4 * 2.4e9 / 2.0   # wave64 VALU instructions/s: 256 CUs x 4 SIMD-32, 2 cycles each (a LONE wave sustains 4)
-REPEATS = 5
+REPEATS = 5                     # --full: replays of the timed graph after the headline, for the spread
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: larger outputs are cut to a fixed, seeded sample of env rows
 TRAFFIC_FILE = os.path.join(ROOT, "profiles", "r04_traffic.json")
 EXIT_WATCHDOG = 3               # --strict: exit code when the watchdog cut the auxiliary legs short (the headline line is out by then)
 
@@ -62,6 +70,8 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--envs-per-gpu", type=int, default=ENVS_PER_GPU)
+    ap.add_argument("--full", action="store_true", help="also run the auxiliary legs (repeats, fp64, PPO loop, CPU baseline) after the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-f64", action="store_true", help="skip the fp64-instantiation leg")
     ap.add_argument("--leg-timeout", type=int, default=420, help="watchdog (s) over the auxiliary legs (PPO loop, fp64, CPU baseline): the headline line is printed without them if they hang")
@@ -158,6 +168,24 @@ def cpu_baseline(cfg, budget_s=12.0):
             "all_cores": {"envs_4096": all_4096, "envs_64": all_64},
             "single_thread": {"envs_4096": one_4096, "envs_64": one_64},
             "thread_scaling_4096": all_4096["value"] / one_4096["value"]}
+
+
+def dump_outputs(out_dir, arrays, suffix=""):
+    """arrays: name -> tensor with the env axis first.  Writes out_dir/<name><suffix>.npy as float32; above DUMP_LIMIT_BYTES in all,
+    every array keeps the same fixed, seeded sample of env rows (sorted).  Returns the file names."""
+    import numpy as np
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    n = next(iter(host.values())).shape[0]
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, int(DUMP_LIMIT_BYTES * n // total), replace=False))
+        host = {k: a[rows] for k, a in host.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    names = []
+    for k, a in host.items():
+        names.append(k + suffix + ".npy")
+        np.save(os.path.join(out_dir, names[-1]), np.ascontiguousarray(a))
+    return names
 
 
 class LineGuard:
@@ -377,34 +405,40 @@ def main(argv=None):
 
     def timed(run):
         """exactly K steps: wall clock between barrier+synchronize on both sides, and HIP events on the launch stream
-        around the same work"""
+        around the same work; max over ranks"""
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         barrier()
         t0 = time.perf_counter()
         e0.record(); run(); e1.record()
         barrier()
-        el = time.perf_counter() - t0
-        return el, e0.elapsed_time(e1) * 1e-3
-
-    if graph is not None:
-        probe = env.get_state(0).rng_counter, env.get_state(0).timestep, float(env._obs.double().sum())
-        first = timed(graph.replay)
-        after = env.get_state(0).rng_counter, env.get_state(0).timestep, float(env._obs.double().sum())
-        if not all_ranks(after != probe):   # a replay did nothing (capture did not see the launches): do not report it
-            graph, launch = None, "eager"
-    run = graph.replay if graph is not None else eager_steps
-    walls, devs = [], []
-    for r in range(REPEATS):
-        el, dv = timed(run)
+        el, dv = time.perf_counter() - t0, e0.elapsed_time(e1) * 1e-3
         if world > 1:
             t_ = torch.tensor([el, dv], device=dev, dtype=torch.float64)
             dist.all_reduce(t_, op=dist.ReduceOp.MAX)
             el, dv = t_.tolist()
-        walls.append(el); devs.append(dv)
-    order = sorted(range(REPEATS), key=lambda i: walls[i])
-    mid = order[REPEATS // 2]
-    elapsed, dev_elapsed = walls[mid], devs[mid]
+        return el, dv
+
+    def probe():
+        return env.get_state(0).rng_counter, env.get_state(0).timestep, float(env._obs.double().sum())
+
+    run = graph.replay if graph is not None else eager_steps
+    before = probe()
+    elapsed, dev_elapsed = timed(run)
+    if graph is not None and not all_ranks(probe() != before):
+        # the replay did nothing (capture did not see the launches): do not report it, time K eager launches instead
+        graph, launch, run = None, "eager", eager_steps
+        elapsed, dev_elapsed = timed(run)
     k_avg = 1e3 * dev_elapsed / K                 # ms per launch inside the timed window (graph: includes the ~1 us node gaps)
+
+    if args.dump_outputs:
+        # what the last timed step returned to its caller: step_inplace hands out these engine-owned buffers
+        outs = {"obs": env._obs, "reward": env._rew, "done": env._done}
+        outs.update({"info_" + k: v for k, v in env._info.items()})
+        dump_outputs(args.dump_outputs, outs, "" if world == 1 else ".rank%d" % rank)
+
+    walls = None
+    if args.full:                                 # the spread: more replays of the same graph, after the headline and the dump
+        walls = [timed(run)[0] for _ in range(REPEATS)]
 
     def build_line(state):
         f64, ppo = state["f64"], state["ppo"]
@@ -424,12 +458,11 @@ def main(argv=None):
                                   "warmstart": cfg.warmstart, "friction_model": "cone" if cfg.friction_model else "pyramid", "erp": cfg.erp, "contact_erp": cfg.contact_erp,
                                   "note": "PyBullet defaults [K]: 50 iterations, solverResidualThreshold 1e-7, no multibody warm start, implicit friction cone, erp 0.2 / contactERP 0.08"},
                        "engine": {k: env.get_property(k) for k in ("lanes_per_env", "sweep_variant", "max_contacts", "max_limit_rows")},
-                       "burn_in_steps": burn_in, "repeats": REPEATS, "statistic": "median of %d repeats of exactly %d steps" % (REPEATS, K)},
-            "repeats_ms_per_step": [1e3 * w / K for w in walls],
+                       "burn_in_steps": burn_in, "statistic": "one timed run of exactly %d steps" % K},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": None,
                          "kernel": "step_kernel_team<float,solo12>", "kernel_ms_avg": k_avg,
-                         "kernel_ms_source": "HIP events around the median timed replay / steps",
+                         "kernel_ms_source": "HIP events around the timed replay / steps",
                          "algorithmic_bytes_per_env_step": bytes_step,
                          "note": "path is FP32-VALU issue / dependency bound (SURVEY 8d), see valu_issue and fp32; HBM fraction is small by construction"},
         }
@@ -457,6 +490,8 @@ def main(argv=None):
                 rf["fp32"] = {"achieved_tflops": fl / 1e12, "peak_tflops": FP32_VECTOR_PEAK_TF, "frac": fl / 1e12 / FP32_VECTOR_PEAK_TF,
                               "flops_per_launch": prof["fp32_flops_per_launch"], "flops_per_env_step": prof["fp32_flops_per_launch"] / N,
                               "count": prof.get("fp32_flops_note", "")}
+        if walls is not None:
+            out["repeats_ms_per_step"] = [1e3 * w / K for w in walls]
         if f64 is not None:
             out["f64"] = f64
         if ppo is not None:
@@ -466,13 +501,14 @@ def main(argv=None):
         return out
 
     ppo = None
-    # From here on every leg is auxiliary to the headline measurement above (LineGuard: the line is printed even if one hangs).
-    guard = LineGuard(rank, args.leg_timeout, args.strict, build_line, args.ppo_steps > 0)
+    # From here on every leg is auxiliary to the headline measurement above and runs with --full only (LineGuard: the line is
+    # printed even if one hangs).
+    guard = LineGuard(rank, args.leg_timeout, args.strict, build_line, args.full and args.ppo_steps > 0)
     state = guard.state
     guard.start()
     # the same workload on the engine's fp64 instantiation (the reference's arithmetic type), single repeat of <= 100 steps
     f64 = None
-    if not args.no_f64:
+    if args.full and not args.no_f64:
         try:
             from solorl_amd.config import PRECISION_F64
             c64 = cfg.copy(); c64.precision = PRECISION_F64
@@ -518,7 +554,7 @@ def main(argv=None):
             f64 = {"error": "%s: %s" % (type(ex).__name__, ex)}
     state["f64"] = f64
 
-    if args.ppo_steps > 0:
+    if args.full and args.ppo_steps > 0:
         # BASELINE config 3 / 4: the full PPO loop (rollout + GAE + clipped update) on the same engine; never fatal
         try:
             ppo = ppo_leg(env, dev, world, args.ppo_steps, args.ppo_epoch)
@@ -537,7 +573,7 @@ def main(argv=None):
         except Exception as ex:
             ppo["grad_allreduce"] = {"error": "%s: %s" % (type(ex).__name__, ex)}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         state["cpu"] = cpu_baseline(cfg)
     guard.finish()
     if world > 1:                         # the line is out: a rank whose process group is unhealthy must not keep the job from ending

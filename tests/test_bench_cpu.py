@@ -109,3 +109,31 @@ def test_line_guard_rearm_shortens_the_fuse():
     g.start(); g.rearm(0.2)
     time.sleep(0.6)
     assert fired == [0] and g.timeout_s == 0.2
+
+
+def test_plain_run_is_lean_and_dump_outputs_are_float32(tmp_path, monkeypatch):
+    """The auxiliary legs are off unless --full; --dump-outputs writes float32 .npy files, and above the size limit every array keeps the
+    same fixed, seeded sample of env rows."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    import torch
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+    assert bench.parse_args(["--full", "--dump-outputs", "D"]).full and bench.parse_args(["--dump-outputs", "D"]).dump_outputs == "D"
+    n = 64
+    outs = {"obs": torch.arange(n * 4, dtype=torch.float32).reshape(n, 4), "reward": torch.arange(n, dtype=torch.float32),
+            "done": torch.arange(n, dtype=torch.uint8) % 2, "info_episode_length": torch.arange(n, dtype=torch.int32)}
+    names = bench.dump_outputs(str(tmp_path / "all"), outs)
+    assert sorted(names) == ["done.npy", "info_episode_length.npy", "obs.npy", "reward.npy"]
+    for k, v in outs.items():
+        x = np.load(tmp_path / "all" / (k + ".npy"))
+        assert x.dtype == np.float32 and np.array_equal(x, v.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 16 * 7 * 4)      # 7 of the 64 rows of 7 floats each
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), outs, ".rank1")
+    obs = np.load(tmp_path / "s1" / "obs.rank1.npy")
+    rows = (obs[:, 0] / 4).astype(int)
+    assert obs.shape == (16, 4) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "s1" / "reward.rank1.npy"), rows.astype(np.float32))
+    assert all(np.array_equal(np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f)) for f in os.listdir(tmp_path / "s1"))
