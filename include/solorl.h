@@ -24,6 +24,8 @@
  *   solorl_ppo_clip_adam   <- agents/ppo/ppo.py:75-77 (clip_grad_norm_ + optimizer.step) on the MLP's 13 parameter tensors
  *   solorl_step_act        <- agents/ppo/train.py:84-88: the rollout's pair `actor_critic.act(obs)` + `envs.step(action)` as ONE launch
  *                             (the policy is evaluated on each observation by the wavefront that has just produced it)
+ *   solorl_step_n / solorl_rollout : K x solorl_step / solorl_step_act in one launch (no reference counterpart: the reference's
+ *                             send-all / receive-all of agents/ppo/envs.py:91-95 is a barrier between every two steps)
  *   solorl_get_state / solorl_set_state / solorl_get_property : no reference counterpart (parity-test hooks, run records)
  *   solorl_destroy         <- agents/ppo/envs.py:129-135 (close)
  *
@@ -202,7 +204,9 @@ int solorl_increment_curriculum(solorl_env* env, double value);
  * or a scaling run can record and pin what it measured.  Names: "lanes_per_env" (16 team mode / 1 lane mode), "sweep_variant"
  * (2: PGS sweep with the K7 residual exit -- the default, one variant at every batch size; 1 / 0: fixed-iteration sweep,
  * software-pipelined / plain -- chosen by grid size when solver_residual_threshold = 0 unless SOLORL_PGS_PIPE pins it, the last bits
- * of an env then depend on which side of one wavefront per SIMD its batch is), "max_contacts", "max_limit_rows", "f64".
+ * of an env then depend on which side of one wavefront per SIMD its batch is), "max_contacts", "max_limit_rows", "f64",
+ * "step_n_one_launch" (1: solorl_step_n / solorl_rollout run K steps in one launch; 0: lane mode or contact-count sorting, where
+ * solorl_step_n issues K ordinary steps and solorl_rollout is refused).
  * Unknown name: SOLORL_ERR_INVALID. */
 int solorl_get_property(const solorl_env* env, const char* name, double* value);
 
@@ -319,6 +323,26 @@ int solorl_ppo_clip_adam(const solorl_policy_params* p, const solorl_ppo_grads* 
 int solorl_step_act(solorl_env* env, const float* actions, float* obs_out, float* reward_out, uint8_t* done_out,
                     const solorl_info_soa* info_out, const solorl_policy_params* p, const float* noise, float* value_out,
                     float* action_out, float* logp_out, void* stream);
+
+/* K control steps = K calls of solorl_step, in one launch where solorl_get_property "step_n_one_launch" is 1 (the defaults: team
+ * mode, no contact-count sorting; otherwise the engine issues K ordinary steps itself, with the same results).  One launch: each
+ * wavefront runs its own four envs through all K steps without waiting for the others in between, so a window costs about the sum
+ * of the MEAN wavefront's steps instead of K times the slowest one's.
+ * actions [K][N][A]; obs_out [K][N][O]; reward_out [K][N]; done_out [K][N];
+ * info_out: every per-step field is [K][N] (applied_torque [K][N][A]); ep_stats stays [FIELDS][N] and accumulates.
+ * K < 1 or a null array: SOLORL_ERR_INVALID; before reset: SOLORL_ERR_STATE.  No host synchronisation, no allocation (capturable). */
+int solorl_step_n(solorl_env* env, int K, const float* actions, float* obs_out, float* reward_out, uint8_t* done_out,
+                  const solorl_info_soa* info_out, void* stream);
+
+/* Closed loop = K calls of solorl_step_act, the action each produces driving the next step, in one launch.
+ * Rows are rollout-storage rows: row r of actions / noise / value_out / logp_out belongs to the observation produced by step r-1.
+ * actions: row 0 is read; rows 1..K-1 are written, and row K too when policy_after_last != 0 (the first action of the next
+ * window; the caller then provides K + 1 rows of actions, noise, value_out and logp_out).  Row 0 of noise / value_out / logp_out is
+ * neither read nor written; noise NULL: every action = the mean.  Other outputs as solorl_step_n.
+ * Same prerequisites as solorl_step_act, otherwise SOLORL_ERR_INVALID. */
+int solorl_rollout(solorl_env* env, int K, float* actions, float* obs_out, float* reward_out, uint8_t* done_out,
+                   const solorl_info_soa* info_out, const solorl_policy_params* p, const float* noise,
+                   float* value_out, float* logp_out, int policy_after_last, void* stream);
 
 const char* solorl_last_error(void);
 const char* solorl_version(void);

@@ -946,6 +946,58 @@ step_kernel_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict__
   step_team<T, ROBOT>(sf, si, snf, sni, M, L, N, P, pp, actions, out, mode);
 }
 
+// K control steps in one launch (solorl_step_n, solorl_rollout): each wavefront runs step_team K times for its own four envs, and no
+// wavefront waits for another between steps.  One launch of step_kernel_team lasts as long as its slowest wavefront, ~2x the mean at
+// 4096 envs (profiles/r04_wave_hist.txt); a wavefront's K steps add up to a sum that spreads much less than one step does, so the tail
+// costs about one step per window instead of one per step.  Same grid, block and register bound as step_kernel_team; the state still
+// makes its HBM round trip every step.  Step k reads actions row k and writes row k of every per-step output ([K][N] rows, offsets in
+// 64 bits); ep_stats accumulates as it does over K launches.  With a policy tail (out.pol.value != null, fp32) step k writes row k + 1
+// of pol.action / value / logp and reads row k + 1 of pol.noise -- pol.action may be `actions` itself (solorl_rollout: the tail of step
+// k writes the action that step k + 1 reads, on the same lane) -- and the last step has no tail unless pol_last.
+template <typename T> struct RolloutArgs {
+  T* sf; int* si; const T* snf; const int* sni; int M;
+  Layout L; int N; EnvParams P; PhysParams<T> pp;
+  const float* actions; Outputs out;
+  int mode;            // (MODE_STEP, but a kernel argument: a constant would fold step_team's branches differently from step_kernel_team's)
+  int K, pol_last;
+};
+template <typename T> SD T* row_adv(T* p, size_t n) { return p ? p + n : p; }
+template <typename T, int ROBOT>
+__global__ void __launch_bounds__(64, sizeof(T) == 8 ? 1 : SOLO_WAVES_PER_SIMD)
+rollout_kernel_team(const RolloutArgs<T> args) {
+  using RA = RolloutArgs<T>;
+  typedef const __attribute__((address_space(4))) char* kptr;
+  constexpr size_t A = Robot<ROBOT>::NQ;
+  const int K = args.K;
+#pragma unroll 1
+  for (int k = 0; k < K; k++) {
+    // the arguments through a pointer the compiler cannot prove loop-invariant: each is loaded where step_team uses it, as in
+    // step_kernel_team.  (Read as kernel parameters, all of them were hoisted out of the loop and held across it: 150 spilled VGPRs.)
+    kptr ap = (kptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ap));
+    const RA& a = *(const RA*)ap;
+    const size_t r = (size_t)k * (size_t)a.N, O = (size_t)(a.L.D * (1 + a.L.H));
+    Outputs o = a.out;
+    o.obs += r * O; o.rew += r; o.done += r;
+    o.timeout = row_adv(o.timeout, r); o.success = row_adv(o.success, r); o.nan_reset = row_adv(o.nan_reset, r);
+    o.ep_len = row_adv(o.ep_len, r); o.ep_rew = row_adv(o.ep_rew, r); o.goals = row_adv(o.goals, r);
+    o.dr0 = row_adv(o.dr0, r); o.dr1 = row_adv(o.dr1, r); o.dr2 = row_adv(o.dr2, r); o.dr3 = row_adv(o.dr3, r); o.dr4 = row_adv(o.dr4, r);
+    o.tau = row_adv(o.tau, r * A);
+    if (o.pol.value) {                       // (uniform: kernel arguments and the loop counter)
+      if (k + 1 < K || a.pol_last) {
+        const size_t r1 = r + (size_t)a.N;
+        o.pol.value += r1; o.pol.logp += r1; o.pol.action += r1 * A; o.pol.noise = row_adv(o.pol.noise, r1 * A);
+      } else o.pol.value = nullptr;
+    }
+    step_team<T, ROBOT>(a.sf, a.si, a.snf, a.sni, a.M, a.L, a.N, a.P, a.pp, a.actions + r * A, o, a.mode);
+    // Between launches the kernel boundary ordered every hand-off from one lane to another; here the next step's reads must stay
+    // behind this step's writes: a reset stores state field f on lane f mod 16 and the next step loads the impulse cache, the env
+    // scalars and the history on other lanes (those blocks do not start on a multiple of 16), history levels 3 and 4 are shifted in
+    // HBM, and the policy tail's activations live in the row storage the next step's sweep rebuilds.
+    TEAM_SYNC();
+  }
+}
+
 template <typename T, int ROBOT>
 __global__ void reset_kernel(T* sf, int* si, const T* snf, const int* sni, int M, Layout L, int N, EnvParams P, float* obs) {
   const idx_t e = (idx_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1202,6 +1254,24 @@ static int check_lds_base(const void* kernel, bool& checked) {
   return 0;
 }
 
+// team mode: grid (a multiple of 8: XCD-contiguous env ranges, step_team), LDS bytes, and the physics parameters with the sweep
+// variant of this batch size
+template <typename T, int ROBOT>
+PhysParams<T> team_launch_shape(const solorl_env* h, int N, dim3& grid, size_t& smem) {
+  grid = dim3((((N + 3) / 4) + 7) & ~7);
+  using TeamLds = RowLds<T, 4>;
+  smem = TeamCtx<T, ROBOT, TeamLds>::bytes;
+  static_assert(sizeof(T) == 8 || TeamCtx<T, ROBOT, TeamLds>::bytes <= 20480, "team-mode LDS must allow 8 workgroups per CU (two wavefronts per SIMD)");
+  PhysParams<T> pp = make_phys<T>(h->cfg);
+  // Pipelined sweep while every wavefront has a SIMD to itself, plain sweep above that (pgs_team_variant: 8192 envs 0.226 ->
+  // 0.210 ms per step).  The two are re-associations of the same sums, so an env's last bits depend on which side of
+  // h->simds workgroups its batch is; SOLORL_PGS_PIPE=1 (or 0) pins one variant for every batch size.
+  bool pipe = (int)grid.x <= h->simds;
+  if (h->pipe_override >= 0) pipe = h->pipe_override != 0;
+  pp.mode = (pp.mode & ~PhysParams<T>::M_PIPE) | (pipe ? PhysParams<T>::M_PIPE : 0);
+  return pp;
+}
+
 template <typename T, int ROBOT>
 int launch_step(solorl_env* h, T* sf, int* si, int N, const float* actions, const Outputs& out, int mode, hipStream_t st) {
   static bool lds_checked[2] = {false, false};
@@ -1209,17 +1279,9 @@ int launch_step(solorl_env* h, T* sf, int* si, int N, const float* actions, cons
                               lds_checked[h->team ? 1 : 0])) return rc;
   if (h->team) {
     auto kt = step_kernel_team<T, ROBOT>;
-    dim3 grid((((N + 3) / 4) + 7) & ~7), block(64);      // multiple of 8: XCD-contiguous env ranges (step_body)
-    using TeamLds = RowLds<T, 4>;
-    const size_t team_smem = TeamCtx<T, ROBOT, TeamLds>::bytes;
-    static_assert(sizeof(T) == 8 || TeamCtx<T, ROBOT, TeamLds>::bytes <= 20480, "team-mode LDS must allow 8 workgroups per CU (two wavefronts per SIMD)");
-    PhysParams<T> pp = make_phys<T>(h->cfg);
-    // Pipelined sweep while every wavefront has a SIMD to itself, plain sweep above that (pgs_team_variant: 8192 envs 0.226 ->
-    // 0.210 ms per step).  The two are re-associations of the same sums, so an env's last bits depend on which side of
-    // h->simds workgroups its batch is; SOLORL_PGS_PIPE=1 (or 0) pins one variant for every batch size.
-    bool pipe = (int)grid.x <= h->simds;
-    if (h->pipe_override >= 0) pipe = h->pipe_override != 0;
-    pp.mode = (pp.mode & ~PhysParams<T>::M_PIPE) | (pipe ? PhysParams<T>::M_PIPE : 0);
+    dim3 grid, block(64);
+    size_t team_smem = 0;
+    const PhysParams<T> pp = team_launch_shape<T, ROBOT>(h, N, grid, team_smem);
     hipLaunchKernelGGL(kt, grid, block, team_smem, st, sf, si, (const T*)h->snf, (const int*)h->sni, h->M, h->L, N,
                        make_env_params(h), pp, actions, out, mode);
     HIP_TRY(hipGetLastError());
@@ -1245,6 +1307,22 @@ int launch_step(solorl_env* h, T* sf, int* si, int N, const float* actions, cons
   return 0;
 }
 
+// K team-mode steps in one launch (rollout_kernel_team); the caller has checked h->team && !h->sort
+template <typename T, int ROBOT>
+int launch_rollout(solorl_env* h, T* sf, int* si, int N, const float* actions, const Outputs& out, int K, int pol_last, hipStream_t st) {
+  static bool lds_checked = false;
+  if (int rc = check_lds_base(reinterpret_cast<const void*>(rollout_kernel_team<T, ROBOT>), lds_checked)) return rc;
+  dim3 grid, block(64);
+  RolloutArgs<T> a;
+  size_t smem = 0;
+  a.pp = team_launch_shape<T, ROBOT>(h, N, grid, smem);
+  a.sf = sf; a.si = si; a.snf = (const T*)h->snf; a.sni = (const int*)h->sni; a.M = h->M; a.L = h->L; a.N = N; a.P = make_env_params(h);
+  a.actions = actions; a.out = out; a.mode = MODE_STEP; a.K = K; a.pol_last = pol_last;
+  hipLaunchKernelGGL((rollout_kernel_team<T, ROBOT>), grid, block, smem, st, a);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 }  // namespace
 
 // ---- translation-unit split (build time only; solorl_amd/build.py).  The step kernels' phase functions are what takes minutes to
@@ -1259,9 +1337,19 @@ __attribute__((visibility("hidden"))) int solorl_launch_part1(SOLO_LAUNCH_ARGS);
 __attribute__((visibility("hidden"))) int solorl_launch_part2(SOLO_LAUNCH_ARGS);
 __attribute__((visibility("hidden"))) int solorl_launch_part3(SOLO_LAUNCH_ARGS);
 }
+// the K-step launch (solorl_step_n / solorl_rollout) of the same instantiation, in the same part
+#define SOLO_ROLLOUT_ARGS solorl_env* h, void* sf, int* si, int N, const float* actions, const void* out, int K, int pol_last, void* st
+extern "C" {
+__attribute__((visibility("hidden"))) int solorl_rollout_part0(SOLO_ROLLOUT_ARGS);
+__attribute__((visibility("hidden"))) int solorl_rollout_part1(SOLO_ROLLOUT_ARGS);
+__attribute__((visibility("hidden"))) int solorl_rollout_part2(SOLO_ROLLOUT_ARGS);
+__attribute__((visibility("hidden"))) int solorl_rollout_part3(SOLO_ROLLOUT_ARGS);
+}
 #define SOLO_DEFINE_PART(K_, T_, R_) \
   extern "C" int solorl_launch_part##K_(SOLO_LAUNCH_ARGS) { \
-    return launch_step<T_, R_>(h, (T_*)sf, si, N, actions, *(const Outputs*)out, mode, (hipStream_t)st); }
+    return launch_step<T_, R_>(h, (T_*)sf, si, N, actions, *(const Outputs*)out, mode, (hipStream_t)st); } \
+  extern "C" int solorl_rollout_part##K_(SOLO_ROLLOUT_ARGS) { \
+    return launch_rollout<T_, R_>(h, (T_*)sf, si, N, actions, *(const Outputs*)out, K, pol_last, (hipStream_t)st); }
 #if SOLO_TU_PART == -1 || SOLO_TU_PART == 0
 SOLO_DEFINE_PART(0, float, 0)
 #endif
@@ -1282,6 +1370,43 @@ int dispatch_step(solorl_env* h, void* sf, int* si, int N, const float* actions,
   const bool s12 = h->cfg.robot == SOLORL_ROBOT_SOLO12;
   if (!h->f64) return s12 ? solorl_launch_part1(h, sf, si, N, actions, &out, mode, st) : solorl_launch_part0(h, sf, si, N, actions, &out, mode, st);
   return s12 ? solorl_launch_part3(h, sf, si, N, actions, &out, mode, st) : solorl_launch_part2(h, sf, si, N, actions, &out, mode, st);
+}
+
+// solorl_step_n / solorl_rollout take one launch exactly where solorl_step is one team-mode launch on a fixed state buffer
+bool step_n_one_launch(const solorl_env* h) { return h->team && !h->sort; }
+
+int dispatch_rollout(solorl_env* h, const float* actions, const Outputs& out, int K, int pol_last, hipStream_t st) {
+  const bool s12 = h->cfg.robot == SOLORL_ROBOT_SOLO12;
+  void* sf = h->sf; int* si = h->si; const int N = h->N;
+  if (!h->f64) return s12 ? solorl_rollout_part1(h, sf, si, N, actions, &out, K, pol_last, st) : solorl_rollout_part0(h, sf, si, N, actions, &out, K, pol_last, st);
+  return s12 ? solorl_rollout_part3(h, sf, si, N, actions, &out, K, pol_last, st) : solorl_rollout_part2(h, sf, si, N, actions, &out, K, pol_last, st);
+}
+
+Outputs make_outputs(float* obs_out, float* reward_out, uint8_t* done_out, const solorl_info_soa* info) {
+  Outputs o; memset(&o, 0, sizeof o);
+  o.obs = obs_out; o.rew = reward_out; o.done = done_out;
+  if (info) {
+    o.timeout = info->timeout; o.success = info->success; o.nan_reset = info->nan_reset; o.ep_len = info->episode_length;
+    o.ep_rew = info->episode_reward; o.goals = info->goals_reached; o.dr0 = info->dr_stand; o.dr1 = info->dr_joint_pose;
+    o.dr2 = info->dr_torque; o.dr3 = info->dr_balance; o.dr4 = info->dr_progress; o.ep_stats = info->ep_stats;
+    o.tau = info->applied_torque;
+  }
+  return o;
+}
+
+// the policy tail's prerequisites (solorl_step_act, solorl_rollout)
+int check_policy_tail(const solorl_env* h, const solorl_policy_params* p, const char* who) {
+  const std::string w(who);
+  if (h->f64 || !h->team || h->sort) return fail(SOLORL_ERR_INVALID, w + " needs the fp32 team-mode engine without contact-count sorting (the defaults)");
+  if (p->hidden != 64 || p->obs_dim != h->O || p->act_dim != h->n || (h->O & 3) || h->O > 88)
+    return fail(SOLORL_ERR_INVALID, w + ": the policy must be the MLP of hidden size 64 on this env's observation / action sizes, obs_dim a multiple of 4 "
+                                        "and at most 88 (zero or one history level)");
+  const void* ptrs[] = {p->critic_w0, p->critic_b0, p->critic_w1, p->critic_b1, p->critic_w2, p->critic_b2, p->actor_w0, p->actor_b0, p->actor_w1, p->actor_b1,
+                        p->mean_w, p->mean_b, p->logstd};
+  for (const void* q : ptrs) if (!q) return fail(SOLORL_ERR_INVALID, w + ": null policy parameter pointer");
+  const void* vec[] = {p->critic_w0, p->critic_w1, p->critic_w2, p->actor_w0, p->actor_w1, p->mean_w};
+  for (const void* q : vec) if (reinterpret_cast<uintptr_t>(q) & 15u) return fail(SOLORL_ERR_INVALID, w + ": weight matrices must be 16-byte aligned (rows are read as float4)");
+  return 0;
 }
 
 template <typename T> int build_snapshots_t(solorl_env* h) {
@@ -1501,6 +1626,7 @@ int solorl_get_property(const solorl_env* h, const char* name, double* value) {
   } else if (n == "max_contacts") *value = MAX_CONTACTS;
   else if (n == "max_limit_rows") *value = MAX_LIMITS;
   else if (n == "f64") *value = h->f64 ? 1 : 0;
+  else if (n == "step_n_one_launch") *value = step_n_one_launch(h) ? 1 : 0;
   else return fail(SOLORL_ERR_INVALID, "unknown property: " + n);
   return 0;
 }
@@ -1530,14 +1656,7 @@ int solorl_step(solorl_env* h, const float* actions, float* obs_out, float* rewa
   if (!h->reset_called) return fail(SOLORL_ERR_STATE, "env.reset() must be called before step");   // baseEnv.py:43
   if (!actions || !obs_out || !reward_out || !done_out) return fail(SOLORL_ERR_INVALID, "null array argument");
   HIP_TRY(hipSetDevice(h->device));
-  Outputs o; memset(&o, 0, sizeof o);
-  o.obs = obs_out; o.rew = reward_out; o.done = done_out;
-  if (info) {
-    o.timeout = info->timeout; o.success = info->success; o.nan_reset = info->nan_reset; o.ep_len = info->episode_length;
-    o.ep_rew = info->episode_reward; o.goals = info->goals_reached; o.dr0 = info->dr_stand; o.dr1 = info->dr_joint_pose;
-    o.dr2 = info->dr_torque; o.dr3 = info->dr_balance; o.dr4 = info->dr_progress; o.ep_stats = info->ep_stats;
-    o.tau = info->applied_torque;
-  }
+  Outputs o = make_outputs(obs_out, reward_out, done_out, info);
   if (h->sort) {   // re-sort the state by last contact count (stable), into the spare buffer
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(sort_perm_kernel, dim3(1), dim3(256), 0, st, (const int*)h->si, h->N, h->perm);
@@ -1554,29 +1673,68 @@ int solorl_step_act(solorl_env* h, const float* actions, float* obs_out, float* 
                     const solorl_policy_params* p, const float* noise, float* value_out, float* action_out, float* logp_out, void* stream) {
   if (!h) return fail(SOLORL_ERR_INVALID, "null handle");
   if (!p || !value_out || !action_out || !logp_out) return fail(SOLORL_ERR_INVALID, "solorl_step_act: null policy argument");
-  if (h->f64 || !h->team || h->sort) return fail(SOLORL_ERR_INVALID, "solorl_step_act needs the fp32 team-mode engine without contact-count sorting (the defaults)");
-  if (p->hidden != 64 || p->obs_dim != h->O || p->act_dim != h->n || (h->O & 3) || h->O > 88)
-    return fail(SOLORL_ERR_INVALID, "solorl_step_act: the policy must be the MLP of hidden size 64 on this env's observation / action sizes, obs_dim a multiple of 4 "
-                                    "and at most 88 (zero or one history level)");
-  const void* ptrs[] = {p->critic_w0, p->critic_b0, p->critic_w1, p->critic_b1, p->critic_w2, p->critic_b2, p->actor_w0, p->actor_b0, p->actor_w1, p->actor_b1,
-                        p->mean_w, p->mean_b, p->logstd};
-  for (const void* q : ptrs) if (!q) return fail(SOLORL_ERR_INVALID, "solorl_step_act: null policy parameter pointer");
-  const void* vec[] = {p->critic_w0, p->critic_w1, p->critic_w2, p->actor_w0, p->actor_w1, p->mean_w};
-  for (const void* q : vec) if (reinterpret_cast<uintptr_t>(q) & 15u) return fail(SOLORL_ERR_INVALID, "solorl_step_act: weight matrices must be 16-byte aligned (rows are read as float4)");
+  if (int rc = check_policy_tail(h, p, "solorl_step_act")) return rc;
   if (!h->reset_called) return fail(SOLORL_ERR_STATE, "env.reset() must be called before step");
   if (!actions || !obs_out || !reward_out || !done_out) return fail(SOLORL_ERR_INVALID, "null array argument");
   HIP_TRY(hipSetDevice(h->device));
-  Outputs o; memset(&o, 0, sizeof o);
-  o.obs = obs_out; o.rew = reward_out; o.done = done_out;
-  if (info) {
-    o.timeout = info->timeout; o.success = info->success; o.nan_reset = info->nan_reset; o.ep_len = info->episode_length;
-    o.ep_rew = info->episode_reward; o.goals = info->goals_reached; o.dr0 = info->dr_stand; o.dr1 = info->dr_joint_pose;
-    o.dr2 = info->dr_torque; o.dr3 = info->dr_balance; o.dr4 = info->dr_progress; o.ep_stats = info->ep_stats;
-    o.tau = info->applied_torque;
-  }
+  Outputs o = make_outputs(obs_out, reward_out, done_out, info);
   o.pol = PolicyTail{p->critic_w0, p->critic_b0, p->critic_w1, p->critic_b1, p->critic_w2, p->critic_b2, p->actor_w0, p->actor_b0, p->actor_w1, p->actor_b1,
                      p->mean_w, p->mean_b, p->logstd, noise, value_out, action_out, logp_out};
   return dispatch_step(h, h->sf, h->si, h->N, actions, o, MODE_STEP, (hipStream_t)stream);
+}
+
+// per-step rows of the caller's info block for the host-issued form of solorl_step_n (ep_stats is not a per-step field)
+static solorl_info_soa info_row(const solorl_info_soa& in, size_t r, size_t A) {
+  solorl_info_soa o = in;
+  auto adv = [r](auto* p) { return p ? p + r : p; };
+  o.timeout = adv(in.timeout); o.success = adv(in.success); o.nan_reset = adv(in.nan_reset); o.episode_length = adv(in.episode_length);
+  o.episode_reward = adv(in.episode_reward); o.goals_reached = adv(in.goals_reached); o.dr_stand = adv(in.dr_stand);
+  o.dr_joint_pose = adv(in.dr_joint_pose); o.dr_torque = adv(in.dr_torque); o.dr_balance = adv(in.dr_balance); o.dr_progress = adv(in.dr_progress);
+  o.applied_torque = in.applied_torque ? in.applied_torque + r * A : nullptr;
+  return o;
+}
+
+int solorl_step_n(solorl_env* h, int K, const float* actions, float* obs_out, float* reward_out, uint8_t* done_out, const solorl_info_soa* info,
+                  void* stream) {
+  if (K < 1) return fail(SOLORL_ERR_INVALID, "solorl_step_n: K must be >= 1");
+  if (!h) return fail(SOLORL_ERR_INVALID, "null handle");
+  if (!h->reset_called) return fail(SOLORL_ERR_STATE, "env.reset() must be called before step");
+  if (!actions || !obs_out || !reward_out || !done_out) return fail(SOLORL_ERR_INVALID, "null array argument");
+  if (!step_n_one_launch(h)) {
+    // lane mode and contact-count sorting have no K-step kernel: K ordinary steps, the same results by construction
+    const size_t N = (size_t)h->N, O = (size_t)h->O, A = (size_t)h->n;
+    for (int k = 0; k < K; k++) {
+      const size_t r = (size_t)k * N;
+      solorl_info_soa ik;
+      if (info) ik = info_row(*info, r, A);
+      if (int rc = solorl_step(h, actions + r * A, obs_out + r * O, reward_out + r, done_out + r, info ? &ik : nullptr, stream)) return rc;
+    }
+    return 0;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  // (K = 1: the one-step kernel itself, so that a one-step call is solorl_step exactly)
+  if (K == 1) return dispatch_step(h, h->sf, h->si, h->N, actions, make_outputs(obs_out, reward_out, done_out, info), MODE_STEP, (hipStream_t)stream);
+  return dispatch_rollout(h, actions, make_outputs(obs_out, reward_out, done_out, info), K, 0, (hipStream_t)stream);
+}
+
+int solorl_rollout(solorl_env* h, int K, float* actions, float* obs_out, float* reward_out, uint8_t* done_out, const solorl_info_soa* info,
+                   const solorl_policy_params* p, const float* noise, float* value_out, float* logp_out, int policy_after_last, void* stream) {
+  if (K < 1) return fail(SOLORL_ERR_INVALID, "solorl_rollout: K must be >= 1");
+  if (!h) return fail(SOLORL_ERR_INVALID, "null handle");
+  if (!p || !value_out || !logp_out) return fail(SOLORL_ERR_INVALID, "solorl_rollout: null policy argument");
+  if (int rc = check_policy_tail(h, p, "solorl_rollout")) return rc;
+  if (!h->reset_called) return fail(SOLORL_ERR_STATE, "env.reset() must be called before step");
+  if (!actions || !obs_out || !reward_out || !done_out) return fail(SOLORL_ERR_INVALID, "null array argument");
+  HIP_TRY(hipSetDevice(h->device));
+  Outputs o = make_outputs(obs_out, reward_out, done_out, info);
+  o.pol = PolicyTail{p->critic_w0, p->critic_b0, p->critic_w1, p->critic_b1, p->critic_w2, p->critic_b2, p->actor_w0, p->actor_b0, p->actor_w1, p->actor_b1,
+                     p->mean_w, p->mean_b, p->logstd, noise, value_out, actions, logp_out};
+  if (K == 1) {              // = solorl_step_act (policy after the step) or solorl_step, as in solorl_step_n
+    if (policy_after_last) { o.pol.value = value_out + h->N; o.pol.logp = logp_out + h->N; o.pol.action = actions + (size_t)h->N * h->n; if (noise) o.pol.noise = noise + (size_t)h->N * h->n; }
+    else o.pol = PolicyTail{};
+    return dispatch_step(h, h->sf, h->si, h->N, actions, o, MODE_STEP, (hipStream_t)stream);
+  }
+  return dispatch_rollout(h, actions, o, K, policy_after_last != 0, (hipStream_t)stream);
 }
 
 int solorl_get_observation(solorl_env* h, float* obs_out, void* stream) {

@@ -66,6 +66,27 @@ def kernel_static_lds(lib_path):
     return out
 
 
+def kernel_resources(lib_path):
+    """{kernel name: {"vgpr_count", "agpr_count", "sgpr_count", "private_segment_fixed_size", "group_segment_fixed_size", ...}} from the
+    code objects' metadata (one record per kernel: a list item that starts with its first key)."""
+    with tempfile.TemporaryDirectory() as d:
+        notes = "\n".join(subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True) for co in _code_objects(lib_path, d))
+    out, cur, col = {}, None, None
+    for line in notes.splitlines():
+        m = re.match(r"^(\s*-?\s*)\.([a-z_]+):\s*(\S*)\s*$", line)
+        if not m:
+            continue
+        if m.group(1).strip() == "-" and m.group(2) == "agpr_count":      # (keys are sorted: a kernel's record starts here)
+            cur, col = {}, len(m.group(1))
+        if cur is None or len(m.group(1)) != col:                          # (the argument records below a kernel have a .name too)
+            continue
+        if m.group(2) == "name":
+            out[m.group(3)] = cur
+        elif m.group(3).isdigit():
+            cur[m.group(2)] = int(m.group(3))
+    return out
+
+
 def function_stats(lib_path):
     """{mangled name: {"insts", "scratch", "flat", "global"}}"""
     out, cur = {}, None

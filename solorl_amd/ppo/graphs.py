@@ -9,6 +9,7 @@ gradient all-reduce between them when world > 1).
 
   GraphedRollout  act -> solorl_step (the C-ABI launch is captured like any other kernel: it is enqueued on
                   torch's capturing stream and never synchronises) -> storage.append, T times
+                  (opt-in, chunk = K: windows of K closed-loop steps, one solorl_rollout launch each)
   GraphedPPO      PPO.update with identical arithmetic (agents/ppo/ppo.py:34-89); mini-batch indices are
                   read on the device from a permutation buffer at a device-side offset, so a replay needs
                   no host-side argument
@@ -97,8 +98,13 @@ class GraphedRollout:
     """One graph = num_steps x (policy.act, env.step, storage.append).  Episode statistics need nothing here: the step
     kernel accumulates them on the device (include/solorl.h `ep_stats`), replayed or not."""
 
-    def __init__(self, envs, actor_critic, storage, num_steps):
+    def __init__(self, envs, actor_critic, storage, num_steps, chunk=None):
         self.envs, self.ac, self.storage, self.T = envs, actor_critic, storage, num_steps
+        # chunk = K > 0: the rollout as ceil(T / K) windows of K closed-loop steps, ONE launch each (solorl_rollout: no wavefront waits
+        # for another between the steps of a window), where the handle supports it.  Default SOLORL_ROLLOUT_CHUNK, 0 = one launch per step.
+        import os
+        self.chunk = int(os.environ.get("SOLORL_ROLLOUT_CHUNK", "0")) if chunk is None else int(chunk)
+        self.windows = None          # the window lengths the captured body used (None: not chunked)
         self.graph = None
 
     def _body(self):
@@ -119,6 +125,20 @@ class GraphedRollout:
         import os
         self.step_act = bool(fused and os.environ.get("SOLORL_STEP_ACT", "1") != "0" and hasattr(self.envs, "step_act_supported")
                              and self.envs.step_act_supported(self._pp))
+        if fused and self.chunk > 0 and hasattr(self.envs, "rollout_supported") and self.envs.rollout_supported(self._pp):
+            # row 0's action from its own policy launch, then windows of K steps straight into storage rows; every window but the last
+            # also evaluates the policy after its last step (row t0 + K: the next window's first action)
+            policy_act(self._pp, st.obs[0], noise[0], st.value_preds[0], st.actions[0], st.action_log_probs[0])
+            self.windows = []
+            for t0 in range(0, self.T, self.chunk):
+                K = min(self.chunk, self.T - t0)
+                pal = 1 if t0 + K < self.T else 0
+                R = K + pal
+                self.envs.rollout_inplace(st.actions[t0:t0 + R], self._pp, noise[t0:t0 + R], st.value_preds[t0:t0 + R], st.action_log_probs[t0:t0 + R],
+                                          obs_out=st.obs[t0 + 1:t0 + 1 + K], rew_out=st.rewards[t0:t0 + K], done_out=done[t0:t0 + K], policy_after_last=pal)
+                self.windows.append(K)
+            torch.sub(torch.ones((), device=st.device), done, out=st.masks[1:].view(self.T, st.num_agents))
+            return
         for t in range(self.T):
             if self.step_act:
                 if t == 0:

@@ -4,6 +4,7 @@
 
   reset() -> Tensor[N, O] f32                                  (envs.py:198-200)
   step(actions Tensor[N, A]) -> (obs[N,O], reward[N,1], done[N] f32, infos)   (envs.py:189-196)
+  step_n(actions Tensor[K, N, A]) -> (obs[K,N,O], reward[K,N,1], done[K,N] f32, infos)  (K steps, one launch: no reference counterpart)
   get_observation(), increment_curriculum(), close(), observation_space, action_space, nenvs
 
 torch is plumbing only: it owns the device buffers and the stream; all arithmetic happens in
@@ -122,6 +123,7 @@ class SoloVecEnv:
         # graph captured earlier would keep replaying the NULL it was captured with)
         self._tau = torch.zeros((N, self.act_dim), dtype=torch.float32, **kw) if applied_torque else None
         self._steps_issued = 0
+        self._kbuf = {}             # engine-owned [K, ...] rows of step_n_inplace / rollout_inplace, per K
         self._info_c = InfoSoA(ep_stats=self._ep_stats.data_ptr(), applied_torque=None if self._tau is None else self._tau.data_ptr(),
                                **{k: self._info[k].data_ptr() for k in _INFO_KEYS})
         self.ob_rms = None          # VecNormalize(ob=False): agents/ppo/envs.py:26, read at train.py:126
@@ -211,6 +213,90 @@ class SoloVecEnv:
             _native.check(self.L.solorl_step_act(self._h, a, po, pr, C.c_void_p(d.data_ptr()), C.byref(self._info_c), C.byref(params), pn, pv, pa, pl,
                                                  self._stream()))
         return o, r, d, self._info
+
+    def _k_rows(self, K):
+        """Engine-owned output rows [K, N, ...] and their info block (every per-step field [K, N], applied torques [K, N, A] when
+        recorded, ep_stats shared with step()), allocated at the first call with this K."""
+        b = self._kbuf.get(K)
+        if b is None or (b["tau"] is None) != (self._tau is None):
+            N, kw = self.nenvs, dict(device=self.device)
+            # (empty, not zeros: every step writes every field of every env, and a fill would be one more launch in a captured graph)
+            info = {k: torch.empty((K, N), dtype=v.dtype, **kw) for k, v in self._info.items()}
+            tau = None if self._tau is None else torch.empty((K, N, self.act_dim), dtype=torch.float32, **kw)
+            if tau is not None:
+                info["applied_torque"] = tau
+            c = InfoSoA(ep_stats=self._ep_stats.data_ptr(), applied_torque=None if tau is None else tau.data_ptr(),
+                        **{k: info[k].data_ptr() for k in _INFO_KEYS})
+            b = dict(obs=None, info=info, tau=tau, c=c)
+            self._kbuf[K] = b
+        return b
+
+    def _rows_out(self, b, K, obs_out, rew_out, done_out):
+        if b["obs"] is None and (obs_out is None or rew_out is None or done_out is None):      # (engine-owned rows: on first use only)
+            kw = dict(device=self.device)
+            b.update(obs=torch.empty((K, self.nenvs, self.obs_dim), dtype=torch.float32, **kw), rew=torch.empty((K, self.nenvs), dtype=torch.float32, **kw),
+                     done=torch.empty((K, self.nenvs), dtype=torch.uint8, **kw))
+        o = b["obs"] if obs_out is None else obs_out
+        r = b["rew"] if rew_out is None else rew_out
+        d = b["done"] if done_out is None else done_out
+        po = self._raw("obs_out", o, (K, self.nenvs, self.obs_dim))
+        pr = self._raw("rew_out", r, tuple(r.shape) if tuple(r.shape) in ((K, self.nenvs), (K, self.nenvs, 1)) else (K, self.nenvs))
+        if not (d.is_cuda and d.device == self.device and d.dtype == torch.uint8 and d.is_contiguous() and tuple(d.shape) == (K, self.nenvs)):
+            raise AssertionError("done_out must be a contiguous uint8 [%d, %d] tensor on %s" % (K, self.nenvs, self.device))
+        return o, r, d, po, pr, C.c_void_p(d.data_ptr())
+
+    def step_n(self, actions):
+        """K control steps (include/solorl.h solorl_step_n; one launch where get_property("step_n_one_launch") is 1): actions [K, N, A]
+        -> (obs [K, N, O], reward [K, N, 1], done [K, N] float, infos: dict of per-step [K, N] tensors, "done" among them)."""
+        if actions.dim() != 3 or actions.shape[1:] != (self.nenvs, self.act_dim) or actions.shape[0] < 1:
+            raise AssertionError("actions must be [K, %d, %d]" % (self.nenvs, self.act_dim))
+        a = actions.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        o, r, d, info = self.step_n_inplace(a)
+        t = {k: v.clone() for k, v in info.items()}
+        t["done"] = d.clone()
+        return o.clone(), r.clone().unsqueeze(-1), t["done"].float(), t
+
+    def step_n_inplace(self, actions, obs_out=None, rew_out=None, done_out=None):
+        """step_inplace for K steps: actions [K, N, A] (float32, contiguous, on this device); returns views of engine-owned rows
+        (overwritten by the next call with the same K) -- or writes observations [K, N, O] / rewards [K, N] or [K, N, 1] / done flags
+        (uint8 [K, N]) straight into caller-owned tensors such as rollout-storage rows.  Host-side checks only, capturable."""
+        K = int(actions.shape[0]) if actions.dim() == 3 else 0
+        if K < 1:
+            raise AssertionError("actions must be [K, %d, %d] with K >= 1" % (self.nenvs, self.act_dim))
+        pa = self._raw("actions", actions, (K, self.nenvs, self.act_dim))
+        b = self._k_rows(K)
+        o, r, d, po, pr, pd = self._rows_out(b, K, obs_out, rew_out, done_out)
+        self._steps_issued += K
+        with torch.cuda.device(self.device):
+            _native.check(self.L.solorl_step_n(self._h, K, pa, po, pr, pd, C.byref(b["c"]), self._stream()))
+        return o, r, d, b["info"]
+
+    def rollout_supported(self, params):
+        """solorl_rollout (include/solorl.h) on this handle: K steps in one launch (team mode, no sorting: as the handle was created,
+        whatever the environment says now), fp32, and solorl_step_act's policy shapes."""
+        return (self.get_property("step_n_one_launch") == 1 and self.get_property("f64") == 0 and self.obs_dim % 4 == 0 and self.obs_dim <= 88
+                and params.obs_dim == self.obs_dim and params.act_dim == self.act_dim and params.hidden == 64)
+
+    def rollout_inplace(self, actions, params, noise, value_out, logp_out, obs_out=None, rew_out=None, done_out=None, policy_after_last=False):
+        """K closed-loop steps in one launch (solorl_rollout), in rollout-storage rows: actions [K (+1), N, A] -- row 0 drives the
+        first step, rows 1.. are written by the policy on the observations the steps produce (row K too with policy_after_last: the
+        first action of the next window); noise [K (+1), N, A] or None (actions = the mean); value_out / logp_out [K (+1), N] or
+        [K (+1), N, 1], rows from 1 written; obs_out [K, N, O], rew_out [K, N] or [K, N, 1], done_out uint8 [K, N] as step_n_inplace."""
+        pal = 1 if policy_after_last else 0
+        R = int(actions.shape[0]) if actions.dim() == 3 else 0
+        K = R - pal
+        if K < 1:
+            raise AssertionError("actions must be [K%s, %d, %d] with K >= 1" % (" + 1" if pal else "", self.nenvs, self.act_dim))
+        pa = self._raw("actions", actions, (R, self.nenvs, self.act_dim))
+        pn = C.c_void_p(0) if noise is None else self._raw("noise", noise, (R, self.nenvs, self.act_dim))
+        pv = self._raw("value_out", value_out, tuple(value_out.shape) if tuple(value_out.shape) in ((R, self.nenvs), (R, self.nenvs, 1)) else (R, self.nenvs))
+        pl = self._raw("logp_out", logp_out, tuple(logp_out.shape) if tuple(logp_out.shape) in ((R, self.nenvs), (R, self.nenvs, 1)) else (R, self.nenvs))
+        b = self._k_rows(K)
+        o, r, d, po, pr, pd = self._rows_out(b, K, obs_out, rew_out, done_out)
+        self._steps_issued += K
+        with torch.cuda.device(self.device):
+            _native.check(self.L.solorl_rollout(self._h, K, pa, po, pr, pd, C.byref(b["c"]), C.byref(params), pn, pv, pl, pal, self._stream()))
+        return o, r, d, b["info"]
 
     def get_observation(self):
         with torch.cuda.device(self.device):
