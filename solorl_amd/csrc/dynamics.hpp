@@ -1843,92 +1843,186 @@ SNI void pgs_team_variant(int iterations_v, const LDS lds, int t) {
   // K7 early exit, per env as in the reference (one Bullet world per env): a team whose sweep changed no row by more
   // than the threshold is finished -- its result is written back right then (it keeps sweeping along with its wavefront,
   // which costs nothing and is never read) -- and the wavefront leaves the loop once all four teams are finished.
-  // Bookkeeping per sweep: the lanes' flags are OR-ed over the team with four DPP steps and one compare / branch decides whether
-  // any team became quiet in this sweep (round 2 split the wave's ballot into four team masks on the scalar unit: ~25 instructions
-  // per sweep, a twelfth of a 6-slot sweep; now ~9).
-  bool fin = false;                                                   // this lane's team is finished (uniform within the team)
+  // Bookkeeping per sweep, all of it on the scalar unit: the rows' compares write wave masks (64 bits, one 16-bit field per team) that
+  // are OR-ed together, and "a team that is not finished yet has an all-zero field" is one has-a-zero-field test and a branch.  Which
+  // team, and its write-back, are in the cold block.  (Round 2 split the ballot into four team masks: ~25 instructions per sweep;
+  // rounds 3-5 OR-ed the lanes' flags over the team with four DPP steps: ~22 with the selects and lane-mask merges around them.)
+  // finm: the finished teams as all-ones fields (lanes that are not running count as finished)
+  unsigned long long finm = 0; (void)finm;
+  if constexpr (EXIT) finm = ~__builtin_amdgcn_ballot_w64(true);
 #if defined(SOLO_WAVE_TIMING) && defined(SOLO_DEAD_STATS)      // (its own switch: the wave-wide test in every friction slot slows the sweep by a tenth)
   unsigned long long fr_tot = 0, fr_dead = 0;                         // friction-slot visits / those with zero bound and zero impulse in every lane
 #endif
   int it_done = 0; (void)it_done;
 #pragma unroll 1                                                    // (unrolled by two: no change, measured)
-  for (int it = 0; it < iterations; it++) {
+  for (int it = iterations; it > 0; it--) {                         // (a uniform down-counter: no vector instruction; the early exit zeroes it)
 #if defined(SOLO_WAVE_TIMING) && defined(SOLO_SWEEP_STATS)
-    it_done = it + 1;
+    it_done++;
 #endif
-    bool viol = false;
+    unsigned long long violm = 0; (void)violm;   // (K7) wave mask: lanes whose limit / normal row changed by more than its threshold
+    T vmax = T(0); (void)vmax;           // (K7, cone) running maximum of the friction pairs' |residual entry|, tested once per sweep
     static_for<n>([&](auto ic) {
       constexpr int i = decltype(ic)::value, in = (i + 1) % n;
       constexpr bool fric = i >= LIM + NNS;
       // next slot's reduction on the accumulators as they are now (without this slot's update)
-      T dnext = T(0), d;
-      if constexpr (PIPE) {
-        dnext = jdot(in, J0[in], J1[in], J2[in], rh[in]);
-        d = fm(ex[i], delxp, fm(eo[i], delp, dpre));
-      } else d = jdot(i, J0[i], J1[i], J2[i], rh[i]);     // plain in-order reduction
-      T hi = T(0);
-      if constexpr (fric) {   // impulse of this contact's normal row: normal slot c/2, half c&1
-        constexpr int c = i - LIM - NNS;
-        // fp32: one DPP broadcast from the lane that owns the normal row (row_newbcast: lane 0 of the team for even contacts, lane 8 for odd
-        // ones) instead of a select between the own impulse and a running copy of the partner's (one add per normal slot and four registers less)
-        if constexpr (sizeof(T) == 4) hi = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(lm[LIM + (c >> 1)]), 0x150 + 8 * (c & 1), 0xF, 0xF, true));
-        else hi = (half == (c & 1)) ? lm[LIM + (c >> 1)] : lmo[c >> 1];
-      }
-      auto clampb = [&](T x) -> T {
-        if constexpr (!fric) return x > T(0) ? x : T(0);
-        else if constexpr (sizeof(T) == 4) return __builtin_amdgcn_fmed3f(x, -hi, hi);
-        else return x < -hi ? -hi : (x > hi ? hi : x);
-      };
+      T dnext = T(0), d = T(0), sv, del, delx, tx = T(0);
+      (void)d; (void)tx;
+      // SCHED: the cone slots of the fp32 pipelined sweep are issued in the order written here, segment by segment (a
+      // sched_barrier(0) lets nothing cross).  A DPP instruction may read a register two issue slots after the instruction that
+      // wrote it at the earliest; the scheduler does not model that, and once the per-slot compares and register copies were gone --
+      // they had filled those slots by accident -- it put the three DPP adds of the next slot's reduction right behind each other
+      // and the hazard recogniser padded them with two s_nop per slot.  Here every DPP read has two useful instructions of the
+      // slot's other chain in front of it.  Same operations on the same operands as the generic path below, only their order.
 #if defined(SOLO_WAVE_TIMING) && defined(SOLO_DEAD_STATS)
-      if constexpr (fric) { fr_tot++; if (!__any(hi != T(0) || lm[i] != T(0))) fr_dead++; }
-#endif
-      T sp = lm[i] - d;
-      T sv;
-      if constexpr (CONE && fric) {
-        // both directions' unclamped sums (own: sp, partner: spx), scaled onto the disc of radius hi = lambda_n (rows are in units of mu)
-        const T spx = half_swap(sp);
-        const T s2 = fm(sp, sp, fm(spx, spx, T(1e-30)));                       // (+ 1e-30: a pair at rest scales by hi * 1e15 -> 1, not by 0 * inf)
-        T sc;
-        if constexpr (sizeof(T) == 4) {
-#ifndef SOLO_HOST_SHIM
-          // v_rsq_f32 (1 ulp: the scale only matters at the level of the sweep's other roundings); min(scale, 1) as med3(x, 0, 1), which
-          // the compiler folds into the multiply's clamp modifier (hi >= 0)
-          sc = __builtin_amdgcn_fmed3f(hi * __builtin_amdgcn_rsqf(s2), 0.0f, 1.0f);
+      constexpr bool SCHED = false, SCHEDN = false;
 #else
-          sc = hi / sqrt(s2); sc = sc < T(1) ? sc : T(1);
+      constexpr bool SCHED = PIPE && CONE && fric && sizeof(T) == 4;
+      constexpr bool SCHEDN = PIPE && !fric && sizeof(T) == 4;         // the limit and normal slots, in the same way
 #endif
-        } else { sc = hi / sqrt(s2); sc = sc < T(1) ? sc : T(1); }
+#define SOLO_SB() __builtin_amdgcn_sched_barrier(0)
+#define SOLO_DPP_ADD(x_, ctrl_) ((x_) + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x_), ctrl_, 0xF, 0xF, true)))
+      if constexpr (SCHED) {
+        constexpr int c = i - LIM - NNS;
+        SOLO_SB();
+        d = fm(ex[i], delxp, fm(eo[i], delp, dpre));
+        const T sp = lm[i] - d;
+        SOLO_SB();
+        dnext = fm(J0[in], a01.x, fm(J1[in], a01.y, fm(J2[in], a2, rh[in])));      // jdot(in), its three DPP adds spread out below
+        SOLO_SB();
+        const T spx = half_swap(sp);
+        T s2 = fm(spx, spx, T(1e-30));
+        SOLO_SB();
+        dnext = SOLO_DPP_ADD(dnext, 0xB1);
+        SOLO_SB();
+        s2 = fm(sp, sp, s2);
+        const T rs = __builtin_amdgcn_rsqf(s2);
+        SOLO_SB();
+        dnext = SOLO_DPP_ADD(dnext, 0x4E);
+        SOLO_SB();
+        const T hi = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(lm[LIM + (c >> 1)]), 0x150 + 8 * (c & 1), 0xF, 0xF, true));
+        const T sc = __builtin_amdgcn_fmed3f(hi * rs, 0.0f, 1.0f);
+        del = fm(sp, sc, -lm[i]);           // (the old impulse's last use, before the product: see the generic path)
+        SOLO_SB();
+        dnext = SOLO_DPP_ADD(dnext, 0x141);
         sv = sp * sc;
-      } else {
-        // position 2k (half 0) is final after the first clamp; 2k+1 (half 1) then sees its delta through c'
-        // (cp = 0 in half 0, whose second clamp therefore repeats the first)
-        const T dfirst = clampb(sp) - lm[i];
+        if constexpr (EXIT) tx = del * th[i];
+        SOLO_SB();
+        delx = half_swap(del);
+        SOLO_SB();
+      } else if constexpr (SCHEDN) {
+        SOLO_SB();
+        d = fm(ex[i], delxp, fm(eo[i], delp, dpre));
+        T sp = lm[i] - d;
+        const T dfirst = (sp > T(0) ? sp : T(0)) - lm[i];
+        SOLO_SB();
+        dnext = fm(J0[in], a01.x, fm(J1[in], a01.y, fm(J2[in], a2, rh[in])));
+        SOLO_SB();
         sp = fm(-cp[i], half_swap(dfirst), sp);
-        sv = clampb(sp);
+        SOLO_SB();
+        dnext = SOLO_DPP_ADD(dnext, 0xB1);
+        SOLO_SB();
+        sv = sp > T(0) ? sp : T(0);
+        del = sv - lm[i];
+        SOLO_SB();
+        dnext = SOLO_DPP_ADD(dnext, 0x4E);
+        a01 = fm(B01[i], P2{del, del}, a01);          // (the first half of the accumulator update, see below)
+        SOLO_SB();
+        delx = half_swap(del);
+        SOLO_SB();
+        dnext = SOLO_DPP_ADD(dnext, 0x141);
+        SOLO_SB();
+      } else {
+        if constexpr (PIPE) {
+          dnext = jdot(in, J0[in], J1[in], J2[in], rh[in]);
+          d = fm(ex[i], delxp, fm(eo[i], delp, dpre));
+        } else d = jdot(i, J0[i], J1[i], J2[i], rh[i]);     // plain in-order reduction
+        T hi = T(0);
+        if constexpr (fric) {   // impulse of this contact's normal row: normal slot c/2, half c&1
+          constexpr int c = i - LIM - NNS;
+          // fp32: one DPP broadcast from the lane that owns the normal row (row_newbcast: lane 0 of the team for even contacts, lane 8 for odd
+          // ones) instead of a select between the own impulse and a running copy of the partner's (one add per normal slot and four registers less)
+          if constexpr (sizeof(T) == 4) hi = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(lm[LIM + (c >> 1)]), 0x150 + 8 * (c & 1), 0xF, 0xF, true));
+          else hi = (half == (c & 1)) ? lm[LIM + (c >> 1)] : lmo[c >> 1];
+        }
+        auto clampb = [&](T x) -> T {
+          if constexpr (!fric) return x > T(0) ? x : T(0);
+          else if constexpr (sizeof(T) == 4) return __builtin_amdgcn_fmed3f(x, -hi, hi);
+          else return x < -hi ? -hi : (x > hi ? hi : x);
+        };
+#if defined(SOLO_WAVE_TIMING) && defined(SOLO_DEAD_STATS)
+        if constexpr (fric) { fr_tot++; if (!__any(hi != T(0) || lm[i] != T(0))) fr_dead++; }
+#endif
+        T sp = lm[i] - d;
+        if constexpr (CONE && fric) {
+          // both directions' unclamped sums (own: sp, partner: spx), scaled onto the disc of radius hi = lambda_n (rows are in units of mu)
+          const T spx = half_swap(sp);
+          const T s2 = fm(sp, sp, fm(spx, spx, T(1e-30)));                       // (+ 1e-30: a pair at rest scales by hi * 1e15 -> 1, not by 0 * inf)
+          T sc;
+          if constexpr (sizeof(T) == 4) {
+#ifndef SOLO_HOST_SHIM
+            // v_rsq_f32 (1 ulp: the scale only matters at the level of the sweep's other roundings); min(scale, 1) as med3(x, 0, 1), which
+            // the compiler folds into the multiply's clamp modifier (hi >= 0)
+            sc = __builtin_amdgcn_fmed3f(hi * __builtin_amdgcn_rsqf(s2), 0.0f, 1.0f);
+#else
+            sc = hi / sqrt(s2); sc = sc < T(1) ? sc : T(1);
+#endif
+          } else { sc = hi / sqrt(s2); sc = sc < T(1) ? sc : T(1); }
+          // the change of a cone row is one fused multiply-add of the same product (the contraction the compiler chose for sv - lm, kept
+          // explicit).  It is the old impulse's last use: issued BEFORE the product, the new impulse is written over the old one and the
+          // loop carries no register copy (the empty asm only makes the product's operand wait for del, which orders the two)
+          del = fm(sp, sc, -lm[i]);
+          if constexpr (sizeof(T) == 4) asm("" : "+v"(sp) : "v"(del));
+          sv = sp * sc;
+        } else {
+          // position 2k (half 0) is final after the first clamp; 2k+1 (half 1) then sees its delta through c'
+          // (cp = 0 in half 0, whose second clamp therefore repeats the first)
+          const T dfirst = clampb(sp) - lm[i];
+          sp = fm(-cp[i], half_swap(dfirst), sp);
+          sv = clampb(sp);
+          del = sv - lm[i];
+        }
+        delx = half_swap(del);
+        if constexpr (EXIT && CONE && fric) tx = del * th[i];
       }
-      const T del = sv - lm[i];
       lm[i] = sv;
-      const T delx = half_swap(del);
       if constexpr (EXIT) {
-        if constexpr (CONE && fric) viol = viol || (fabs(fm(delx, thx[i - LIM - NNS], del * th[i])) > T(1));
-        else viol = viol || (fabs(del) > th[i]);
+        // cone pairs: |x| > 1 for any of them <=> max |x| > 1 (a NaN is "not violating" either way: the maximum drops it): one v_max3_f32
+        // per two slots instead of a compare into a scalar pair and a scalar OR per slot.  Limit and normal rows keep their compare (a
+        // threshold per row; scaling by a reciprocal would not be the same predicate).
+        if constexpr (CONE && fric) {
+          const T x = fabs(fm(delx, thx[i - LIM - NNS], tx));
+          if constexpr (sizeof(T) == 4) vmax = __builtin_fmaxf(vmax, x); else vmax = __builtin_fmax(vmax, x);
+        } else violm |= __builtin_amdgcn_ballot_w64(fabs(del) > th[i]);
       }
       if constexpr (sizeof(T) != 4 && i >= LIM && i < LIM + NNS) lmo[i - LIM] += delx;
-      a01 = fm(X01[i], P2{delx, delx}, fm(B01[i], P2{del, del}, a01));
+      if constexpr (SCHEDN) a01 = fm(X01[i], P2{delx, delx}, a01);
+      else a01 = fm(X01[i], P2{delx, delx}, fm(B01[i], P2{del, del}, a01));
       a2 = fm(X2[i], delx, fm(B2[i], del, a2));
       dpre = dnext; delp = del; delxp = delx;
+#undef SOLO_DPP_ADD
+#undef SOLO_SB
     });
+    // (a use of the first slot's reduction inside the sweep: left to itself, the last add of its DPP butterfly is moved behind the exit
+    // test, where it can no longer be folded into its DPP move -- one more instruction per sweep)
+    if constexpr (PIPE && sizeof(T) == 4) asm volatile("" :: "v"(dpre));
     if constexpr (EXIT) {
-      const bool quiet = team_or16(viol ? 1 : 0) == 0;                 // no lane of this team saw a change above its row's threshold
-      const bool nw = quiet && !fin;
-      if (__any(nw)) {                                               // (wave-uniform branch, taken at most once per team)
+      if constexpr (CONE && NFS > 0) violm |= __builtin_amdgcn_ballot_w64(vmax > T(1));
+      // a field of vm is zero <=> no lane of that team saw a change above its row's threshold, and the team is not finished yet;
+      // some field is zero <=> (vm - 0x0001..) & ~vm & 0x8000.. != 0
+      const unsigned long long vm = violm | finm;
+      if (((vm - 0x0001000100010001ull) & ~vm & 0x8000800080008000ull) != 0) {     // (wave-uniform branch, taken at most once per team)
+        const int row = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) & 48;      // first lane of this lane's team
+        const bool nw = ((unsigned)(vm >> row) & 0xFFFFu) == 0;        // this lane's team became quiet in this sweep
         if (nw) SOLO_PGS_WRITE_BACK();
-        fin = fin || quiet;
-        if (__all(fin)) break;
+        finm |= __builtin_amdgcn_ballot_w64(nw);
+        if (finm == ~0ull) it = 1;                                     // all four teams are finished: the wavefront leaves
       }
     }
   }
-  if constexpr (EXIT) { if (!fin) SOLO_PGS_WRITE_BACK(); }     // teams that ran all the iterations
+  if constexpr (EXIT) {                                        // teams that ran all the iterations
+    const int ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    if (!((finm >> ln) & 1)) SOLO_PGS_WRITE_BACK();
+  }
   else SOLO_PGS_WRITE_BACK();
 #if defined(SOLO_WAVE_TIMING) && defined(SOLO_SWEEP_STATS)       // sweeps the wavefront ran / solves (instead of the dead-slot counters)
   if (threadIdx.x == 0 && blockIdx.x < SOLO_WT_WAVES) { solo_wave_times[blockIdx.x][26] += (unsigned long long)it_done; solo_wave_times[blockIdx.x][27] += 1ull; }

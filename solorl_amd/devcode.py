@@ -109,8 +109,10 @@ def function_stats(lib_path):
 
 def loop_stats(lib_path, name_filter):
     """For every function whose mangled name contains `name_filter`: the widest backward branch (spanning more than
-    200 bytes) is taken as THE loop; returns {name: {"insts", "scratch", "scratch_in_loop", "valu_in_loop", "lds_in_loop"}}.
-    Used to pin that the PGS sweep loops touch no memory at all (callee-saved registers are saved around them)."""
+    200 bytes) is taken as THE loop; returns {name: {"insts", "scratch", "insts_in_loop", "s_nop_in_loop", "scratch_in_loop",
+    "valu_in_loop", "lds_in_loop", ...}}.  Used to pin that the PGS sweep loops touch no memory at all (callee-saved registers are
+    saved around them) and what a sweep issues: a lone wavefront pays ~4 cycles for EVERY instruction of the span, whatever it does
+    (`insts_in_loop`: all of them, the cold blocks inside the span included; `s_nop_in_loop`: the hazard fillers among them)."""
     funcs, cur = {}, None
     for line in disassemble(lib_path).splitlines():
         m = re.match(r"^[0-9a-f]+ <([^>]+)>:", line)
@@ -139,6 +141,7 @@ def loop_stats(lib_path, name_filter):
                         lo, hi = int(mt.group(1), 16), off
         inl = [op for off, op in rows if lo is not None and lo <= off <= hi]
         out[name] = dict(insts=len(rows), scratch=sum(op.startswith("scratch_") for _, op in rows), loop=(lo, hi),
+                         insts_in_loop=len(inl), s_nop_in_loop=sum(op.startswith("s_nop") for op in inl),
                          scratch_in_loop=sum(op.startswith("scratch_") for op in inl), valu_in_loop=sum(op.startswith("v_") for op in inl),
                          lds_in_loop=sum(op.startswith("ds_") for op in inl), lds_reads_in_loop=sum(op.startswith("ds_read") for op in inl),
                          vmem_in_loop=sum(op.startswith(("global_", "flat_", "buffer_")) for op in inl))
