@@ -1122,6 +1122,9 @@ SNI void phase_pgs(CH ch, int iterations, T resid_thr, const LDS lds) {
 #pragma unroll
   for (int k = 0; k < 9; k++) pend.W[k] = T(0);
   bool conv = false, viol = false;
+#ifdef SOLO_K7_SWEEP_HOOK     // (a counting tool on the host, tools/dev/k7_gate_share.cpp: did a limit / normal row alone keep the solve going?)
+  bool viol_ln = false;
+#endif
   auto fetch = [&](int rr, Row& R) {
     const Chunk* p = corev + __mul24(rr, NCH * LN);
 #pragma unroll
@@ -1177,6 +1180,9 @@ SNI void phase_pgs(CH ch, int iterations, T resid_thr, const LDS lds) {
       delta = sum - R.lam;
       const T dvel = fabs(delta) / R.c[19];                  // K7 residual: |delta impulse| / jacDiagABInv
       viol = viol || (dvel > resid_thr);
+#ifdef SOLO_K7_SWEEP_HOOK
+      if (!fr) viol_ln = viol_ln || (dvel > resid_thr);
+#endif
       w.a.x += R.c[9] * delta; w.a.y += R.c[10] * delta; w.a.z += R.c[11] * delta;
       w.l.x += R.c[12] * delta; w.l.y += R.c[13] * delta; w.l.z += R.c[14] * delta;
       y0 = R.y0 + R.c[15] * delta; y1 = R.y1 + R.c[16] * delta; y2 = R.y2 + R.c[17] * delta;
@@ -1194,11 +1200,17 @@ SNI void phase_pgs(CH ch, int iterations, T resid_thr, const LDS lds) {
     Row A, B;
     fetch(0, A);
     viol = false;
+#ifdef SOLO_K7_SWEEP_HOOK
+    viol_ln = false;
+#endif
 #pragma unroll 1
     for (int r = 0; r < wmax; r += 2) {  // ping-pong: no register rotation
       step(r, A, B);
       step(r + 1, B, A);
     }
+#ifdef SOLO_K7_SWEEP_HOOK
+    if (!conv) SOLO_K7_SWEEP_HOOK(nlt, nc, viol_ln, viol);
+#endif
     conv = conv || !viol;               // K7: this lane's solve ends after the first sweep within the residual threshold
     if (!__any(!conv)) break;
   }
@@ -1681,6 +1693,9 @@ template <typename T> SD T team_red8(T x) {      // sum over the 8 lanes of a ha
 #ifndef SOLO_SETUP_GROUP_F64
 #define SOLO_SETUP_GROUP_F64 1
 #endif
+#ifndef SOLO_K7_GATE_MIN_NFS
+#define SOLO_K7_GATE_MIN_NFS 1     // fewest friction slots of a gated K7 cone sweep (see GATE in pgs_team_variant): all of them
+#endif
 // CONE (solorl_config friction_model = cone): Bullet's implicit friction cone [K].  A friction slot already holds the two directions of
 //   one contact, one per half; both halves take their unclamped sums against the pre-update accumulators (no Gauss-Seidel coupling c'
 //   between the two), exchange them, and scale the pair by min(1, mu lambda_n / |pair|) -- resolveConeFrictionConstraintRows' atan2 / sin /
@@ -1845,8 +1860,8 @@ SNI void pgs_team_variant(int iterations_v, const LDS lds, int t) {
   // which costs nothing and is never read) -- and the wavefront leaves the loop once all four teams are finished.
   // Bookkeeping per sweep, all of it on the scalar unit: the rows' compares write wave masks (64 bits, one 16-bit field per team) that
   // are OR-ed together, and "a team that is not finished yet has an all-zero field" is one has-a-zero-field test and a branch.  Which
-  // team, and its write-back, are in the cold block.  (Round 2 split the ballot into four team masks: ~25 instructions per sweep;
-  // rounds 3-5 OR-ed the lanes' flags over the team with four DPP steps: ~22 with the selects and lane-mask merges around them.)
+  // team, and its write-back, are in the cold block -- and, in the gated sweeps (GATE below), the friction pairs' part of the test.
+  // (Round 2 split the ballot into four team masks: ~25 instructions per sweep; rounds 3-5 OR-ed the lanes' flags over the team with four DPP steps: ~22 with the selects and lane-mask merges around them.)
   // finm: the finished teams as all-ones fields (lanes that are not running count as finished)
   unsigned long long finm = 0; (void)finm;
   if constexpr (EXIT) finm = ~__builtin_amdgcn_ballot_w64(true);
@@ -1854,13 +1869,19 @@ SNI void pgs_team_variant(int iterations_v, const LDS lds, int t) {
   unsigned long long fr_tot = 0, fr_dead = 0;                         // friction-slot visits / those with zero bound and zero impulse in every lane
 #endif
   int it_done = 0; (void)it_done;
+  // GATE (K7, cone, fp32): the friction pairs' entries are not formed in the slots.  They only matter for a team whose limit and normal rows
+  // were all quiet in this sweep, so the has-a-zero-field test is made on the limit / normal mask alone and the pairs' entries are formed
+  // in the cold block, from the slots' changes kept in registers (2.5 instructions per cone slot and two per sweep less on the common
+  // path; the block is entered in ~1/6 of the heavy wavefronts' sweeps: DESIGN section 4, "The K7 gate").
+  constexpr bool GATE = EXIT && CONE && NFS >= SOLO_K7_GATE_MIN_NFS && sizeof(T) == 4;
 #pragma unroll 1                                                    // (unrolled by two: no change, measured)
   for (int it = iterations; it > 0; it--) {                         // (a uniform down-counter: no vector instruction; the early exit zeroes it)
 #if defined(SOLO_WAVE_TIMING) && defined(SOLO_SWEEP_STATS)
     it_done++;
 #endif
     unsigned long long violm = 0; (void)violm;   // (K7) wave mask: lanes whose limit / normal row changed by more than its threshold
-    T vmax = T(0); (void)vmax;           // (K7, cone) running maximum of the friction pairs' |residual entry|, tested once per sweep
+    T vmax = T(0); (void)vmax;           // (K7, cone) running maximum of the friction pairs' |residual entry|, tested once per sweep (gated: once per cold block)
+    T dk[GATE ? NFS : 1], dkx[GATE ? NFS : 1]; (void)dk; (void)dkx;      // (K7, gated) each cone slot's change of this sweep, own and partner row
     static_for<n>([&](auto ic) {
       constexpr int i = decltype(ic)::value, in = (i + 1) % n;
       constexpr bool fric = i >= LIM + NNS;
@@ -1905,7 +1926,7 @@ SNI void pgs_team_variant(int iterations_v, const LDS lds, int t) {
         SOLO_SB();
         dnext = SOLO_DPP_ADD(dnext, 0x141);
         sv = sp * sc;
-        if constexpr (EXIT) tx = del * th[i];
+        if constexpr (EXIT && !GATE) tx = del * th[i];
         SOLO_SB();
         delx = half_swap(del);
         SOLO_SB();
@@ -1982,14 +2003,16 @@ SNI void pgs_team_variant(int iterations_v, const LDS lds, int t) {
           del = sv - lm[i];
         }
         delx = half_swap(del);
-        if constexpr (EXIT && CONE && fric) tx = del * th[i];
+        if constexpr (EXIT && CONE && fric && !GATE) tx = del * th[i];
       }
       lm[i] = sv;
       if constexpr (EXIT) {
         // cone pairs: |x| > 1 for any of them <=> max |x| > 1 (a NaN is "not violating" either way: the maximum drops it): one v_max3_f32
         // per two slots instead of a compare into a scalar pair and a scalar OR per slot.  Limit and normal rows keep their compare (a
-        // threshold per row; scaling by a reciprocal would not be the same predicate).
-        if constexpr (CONE && fric) {
+        // threshold per row; scaling by a reciprocal would not be the same predicate).  A gated sweep only keeps the pair's two changes
+        // here and forms x, the maximum and its compare in the cold block: same operations on the same operands, in the sweeps that need them.
+        if constexpr (CONE && fric && GATE) { dk[i - LIM - NNS] = del; dkx[i - LIM - NNS] = delx; }     // (no instruction: the registers stay as they are)
+        else if constexpr (CONE && fric) {
           const T x = fabs(fm(delx, thx[i - LIM - NNS], tx));
           if constexpr (sizeof(T) == 4) vmax = __builtin_fmaxf(vmax, x); else vmax = __builtin_fmax(vmax, x);
         } else violm |= __builtin_amdgcn_ballot_w64(fabs(del) > th[i]);
@@ -2006,13 +2029,24 @@ SNI void pgs_team_variant(int iterations_v, const LDS lds, int t) {
     // test, where it can no longer be folded into its DPP move -- one more instruction per sweep)
     if constexpr (PIPE && sizeof(T) == 4) asm volatile("" :: "v"(dpre));
     if constexpr (EXIT) {
-      if constexpr (CONE && NFS > 0) violm |= __builtin_amdgcn_ballot_w64(vmax > T(1));
+      if constexpr (CONE && NFS > 0 && !GATE) violm |= __builtin_amdgcn_ballot_w64(vmax > T(1));
       // a field of vm is zero <=> no lane of that team saw a change above its row's threshold, and the team is not finished yet;
-      // some field is zero <=> (vm - 0x0001..) & ~vm & 0x8000.. != 0
+      // some field is zero <=> (vm - 0x0001..) & ~vm & 0x8000.. != 0.  Gated: vm holds the limit and normal rows only -- a team with a
+      // non-zero field cannot be quiet whatever its friction pairs did -- and the pairs are OR-ed in below before a team is declared
+      // quiet (vmf); when they keep every candidate going, nw is false in every lane and nothing is published.
       const unsigned long long vm = violm | finm;
-      if (((vm - 0x0001000100010001ull) & ~vm & 0x8000800080008000ull) != 0) {     // (wave-uniform branch, taken at most once per team)
+      if (((vm - 0x0001000100010001ull) & ~vm & 0x8000800080008000ull) != 0) {     // (wave-uniform branch; ungated: taken at most once per team)
+        unsigned long long vmf = vm;
+        if constexpr (GATE) {        // the friction pairs' entries of this sweep, as the ungated sweep forms them in its slots
+          static_for<NFS>([&](auto cc) {
+            constexpr int c = decltype(cc)::value;
+            const T x = fabs(fm(dkx[c], thx[c], dk[c] * th[LIM + NNS + c]));
+            vmax = __builtin_fmaxf(vmax, x);
+          });
+          vmf |= __builtin_amdgcn_ballot_w64(vmax > T(1));
+        }
         const int row = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) & 48;      // first lane of this lane's team
-        const bool nw = ((unsigned)(vm >> row) & 0xFFFFu) == 0;        // this lane's team became quiet in this sweep
+        const bool nw = ((unsigned)(vmf >> row) & 0xFFFFu) == 0;        // this lane's team became quiet in this sweep
         if (nw) SOLO_PGS_WRITE_BACK();
         finm |= __builtin_amdgcn_ballot_w64(nw);
         if (finm == ~0ull) it = 1;                                     // all four teams are finished: the wavefront leaves

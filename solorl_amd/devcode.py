@@ -107,14 +107,10 @@ def function_stats(lib_path):
     return out
 
 
-def loop_stats(lib_path, name_filter):
-    """For every function whose mangled name contains `name_filter`: the widest backward branch (spanning more than
-    200 bytes) is taken as THE loop; returns {name: {"insts", "scratch", "insts_in_loop", "s_nop_in_loop", "scratch_in_loop",
-    "valu_in_loop", "lds_in_loop", ...}}.  Used to pin that the PGS sweep loops touch no memory at all (callee-saved registers are
-    saved around them) and what a sweep issues: a lone wavefront pays ~4 cycles for EVERY instruction of the span, whatever it does
-    (`insts_in_loop`: all of them, the cold blocks inside the span included; `s_nop_in_loop`: the hazard fillers among them)."""
+def _function_rows(text, name_filter):
+    """{mangled name: [(byte offset in the function, instruction text)]} of the functions whose name contains `name_filter`"""
     funcs, cur = {}, None
-    for line in disassemble(lib_path).splitlines():
+    for line in text.splitlines():
         m = re.match(r"^[0-9a-f]+ <([^>]+)>:", line)
         if m:
             cur = funcs.setdefault(m.group(1), [])
@@ -132,19 +128,88 @@ def loop_stats(lib_path, name_filter):
             mo = off_re.search(l)
             if mo:
                 rows.append((int(mo.group(1), 16) - base, l.split("\t")[1].strip() if len(l.split("\t")) > 1 else ""))
+        out[name] = rows
+    return out
+
+
+def _branch_target(op):
+    if not op.startswith(("s_cbranch", "s_branch")):
+        return None
+    mt = re.search(r"<[^>]*\+0x([0-9a-f]+)>", op)
+    return int(mt.group(1), 16) if mt else None
+
+
+def loop_stats(lib_path, name_filter, text=None):
+    """For every function whose mangled name contains `name_filter`: the widest backward branch (spanning more than
+    200 bytes) is taken as THE loop; returns {name: {"insts", "scratch", "insts_in_loop", "s_nop_in_loop", "scratch_in_loop",
+    "valu_in_loop", "lds_in_loop", ..., "ops_in_loop": [mnemonics of the span, in address order]}}.  Used to pin that the PGS sweep loops touch no memory at all (callee-saved registers are
+    saved around them) and what a sweep issues: a lone wavefront pays ~4 cycles for EVERY instruction of the span, whatever it does
+    (`insts_in_loop`: all of them, the cold blocks inside the span included; `s_nop_in_loop`: the hazard fillers among them).
+    `text`: a disassembly to use instead of the library's."""
+    out = {}
+    for name, rows in _function_rows(disassemble(lib_path) if text is None else text, name_filter).items():
         lo = hi = None
         for off, op in rows:
-            if op.startswith(("s_cbranch", "s_branch")):
-                mt = re.search(r"<[^>]*\+0x([0-9a-f]+)>", op)
-                if mt and int(mt.group(1), 16) < off and off - int(mt.group(1), 16) > 200:
-                    if lo is None or off - int(mt.group(1), 16) > hi - lo:         # the widest backward branch = the sweep loop
-                        lo, hi = int(mt.group(1), 16), off
+            tgt = _branch_target(op)
+            if tgt is not None and tgt < off and off - tgt > 200:
+                if lo is None or off - tgt > hi - lo:         # the widest backward branch = the sweep loop
+                    lo, hi = tgt, off
         inl = [op for off, op in rows if lo is not None and lo <= off <= hi]
         out[name] = dict(insts=len(rows), scratch=sum(op.startswith("scratch_") for _, op in rows), loop=(lo, hi),
-                         insts_in_loop=len(inl), s_nop_in_loop=sum(op.startswith("s_nop") for op in inl),
+                         ops_in_loop=[op.split(" ")[0] for op in inl], insts_in_loop=len(inl), s_nop_in_loop=sum(op.startswith("s_nop") for op in inl),
                          scratch_in_loop=sum(op.startswith("scratch_") for op in inl), valu_in_loop=sum(op.startswith("v_") for op in inl),
                          lds_in_loop=sum(op.startswith("ds_") for op in inl), lds_reads_in_loop=sum(op.startswith("ds_read") for op in inl),
                          vmem_in_loop=sum(op.startswith(("global_", "flat_", "buffer_")) for op in inl))
+    return out
+
+
+# what only the K7 early exit puts on a sweep's path: the rows' compares and the friction pairs' running maximum, the scalar merges of
+# their wave masks with the has-a-zero-field test, and the branch on it (the fixed-iteration sweeps issue none of these)
+_K7_ONLY = ("v_cmp_", "v_max3_f32", "s_or_b64", "s_and_b64", "s_andn2_b64", "s_sub_u32", "s_subb_u32", "s_cmp_eq_u64", "s_cmp_lg_u64")
+
+
+def hot_path_stats(lib_path, name_filter, text=None):
+    """The COMMON path of every sweep loop found by `name_filter` -- what a sweep issues when no team leaves in it, which is all but
+    four of a solve's sweeps (`loop_stats` counts the whole span, the cold block that publishes a team's result included, and keeps
+    that meaning).  The loop is the one closed by the widest backward branch on a scalar condition (the down-counter's); the path runs
+    from that branch's target to the first forward branch -- the one that skips the cold block -- continues at its target, the counter
+    block, and ends with the back edge: found as the SHORTEST instruction path from the loop head to the back edge over forward
+    branches, which is that path wherever the block layout puts the cold block.  Returns {name: {"head", "back_edge", "insts",
+    "s_nop", "k7_only", "ops": [mnemonics in path order]}}; `k7_only` counts the instructions left on the path that only the early
+    exit needs (_K7_ONLY and the branch over the cold block)."""
+    out = {}
+    for name, rows in _function_rows(disassemble(lib_path) if text is None else text, name_filter).items():
+        head = back = None
+        for k, (off, op) in enumerate(rows):
+            tgt = _branch_target(op)
+            if tgt is not None and op.startswith("s_cbranch_scc") and tgt < off and off - tgt > 200:
+                if head is None or off - tgt > rows[back][0] - head:
+                    head, back = tgt, k
+        if head is None:
+            out[name] = dict(head=None, back_edge=None, insts=0, s_nop=0, k7_only=0, ops=[])
+            continue
+        index = {off: k for k, (off, _) in enumerate(rows)}
+        INF = float("inf")
+        best, nxt = [INF] * (len(rows) + 1), [None] * (len(rows) + 1)
+        best[back] = 1
+        for k in range(back - 1, index[head] - 1, -1):       # forward edges only: one pass from the back edge up
+            off, op = rows[k]
+            tgt = _branch_target(op)
+            succ = []
+            if not op.startswith(("s_branch", "s_endpgm", "s_setpc")):
+                succ.append(k + 1)
+            if tgt is not None and off < tgt <= rows[back][0] and tgt in index:
+                succ.append(index[tgt])
+            for j in succ:
+                if best[j] + 1 < best[k]:
+                    best[k], nxt[k] = best[j] + 1, j
+        ops, k = [], index[head]
+        while k is not None and best[k] < INF:
+            ops.append(rows[k][1].split(" ")[0])
+            k = nxt[k]
+        skip = sum(1 for a, b in zip(ops, ops[1:]) if a.startswith("s_cbranch")) if ops else 0     # (branches on the path that are not its end)
+        out[name] = dict(head=head, back_edge=rows[back][0], insts=len(ops), s_nop=sum(o.startswith("s_nop") for o in ops),
+                         k7_only=sum(o.startswith(_K7_ONLY) for o in ops) + skip, ops=ops)
     return out
 
 
