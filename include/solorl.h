@@ -206,7 +206,11 @@ int solorl_increment_curriculum(solorl_env* env, double value);
  * software-pipelined / plain -- chosen by grid size when solver_residual_threshold = 0 unless SOLORL_PGS_PIPE pins it, the last bits
  * of an env then depend on which side of one wavefront per SIMD its batch is), "max_contacts", "max_limit_rows", "f64",
  * "step_n_one_launch" (1: solorl_step_n / solorl_rollout run K steps in one launch; 0: lane mode or contact-count sorting, where
- * solorl_step_n issues K ordinary steps and solorl_rollout is refused).
+ * solorl_step_n issues K ordinary steps and solorl_rollout is refused), "helper_wave" (1: solorl_step, solorl_step_act and a
+ * one-step solorl_step_n launch two wavefronts per workgroup, the second one running the collision front of every sub-step beside the
+ * first one's leg dynamics -- fp32 team mode without sorting while the batch gives every SIMD at most one workgroup, unless
+ * SOLORL_HELPER_WAVE=0 pins it off; results are bitwise the same either way.  SOLORL_HELPER_WAVE=1 beyond that rule makes
+ * solorl_create fail with SOLORL_ERR_INVALID).
  * Unknown name: SOLORL_ERR_INVALID. */
 int solorl_get_property(const solorl_env* env, const char* name, double* value);
 

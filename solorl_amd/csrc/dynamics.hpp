@@ -726,7 +726,11 @@ template <typename T> SD LegSign<T> leg_sign(int L) {
     else if constexpr (b_ == a_ && c_ == -a_ && d_ == -a_) return T(a_) * (g).sx; \
     else if constexpr (b_ == -a_ && c_ == -a_ && d_ == a_) return T(a_) * (g).sxy; \
     else return T(a_) + T(b_ - a_) * (g).m1 + T(c_ - a_) * (g).m2 + T(d_ - a_) * (g).m3; }())
-template <typename T, int ROBOT, typename LDS, typename CH, bool UI>
+// DUO (duo_kernel_team, two wavefronts per workgroup): the collision front of this sub-step runs on the helper wavefront WHILE this
+// function computes the leg dynamics, which need only the state, sin/cos and C.R0; workgroup barrier B below, in front of the first
+// read of the front's results, is where the two meet.  It is passed by every lane's wavefront unconditionally: the DUO caller calls
+// this function for ALL lanes (an idle team computes on whatever its context holds and parks nothing, its selectors are zero).
+template <typename T, int ROBOT, typename LDS, typename CH, bool UI, bool DUO = false>
 SNI_SCALAR void phase_leg_rt(CH ch, const PhysParams<T>& pp, const T* lam_prev, unsigned nstride, const LDS lds, int L, int sub) {   // (pp by reference:
                                                                      // ten more live argument registers made this phase spill 101 VGPRs)
   // Round 4 (SOLO_LEG_QUAD): leg L runs on the FOUR lanes of quad L (sub = lane & 3) instead of one.  Kinematics, link terms, the
@@ -738,6 +742,9 @@ SNI_SCALAR void phase_leg_rt(CH ch, const PhysParams<T>& pp, const T* lam_prev, 
   using RB = Robot<ROBOT>;
   constexpr int NJ = RB::NJ;
   constexpr int ST = NJ + 1;   // links per leg
+#if defined(SOLO_WAVE_TIMING)
+  const long long wt_leg0_ = clock64();
+#endif
   // every field of pp this phase uses, read HERE: pp arrives by reference (a FLAT load from the kernel's stack, ~700 cycles), and read where it is
   // used -- inside the blocks of the contact rows -- each touching primitive waited for its own round trip
   const T kd = pp.damping, pp_qlim = pp.qlim, pp_slop = pp.slop, pp_warm = pp.warm, pp_tm_mu = pp.tm_mu;
@@ -893,6 +900,10 @@ SNI_SCALAR void phase_leg_rt(CH ch, const PhysParams<T>& pp, const T* lam_prev, 
   C.LR[L] = LR;
 #endif
   // joint-limit rows of this leg: the ones the collision phase selected (C.lsel), slots in joint order
+#if defined(SOLO_WAVE_TIMING)
+  if (threadIdx.x == 0) solo_pt_acc[9] += (unsigned long long)(clock64() - wt_leg0_);      // the leg dynamics alone (no drain: in flight as in the plain build)
+#endif
+  if constexpr (DUO) WG_SYNC();                 // barrier B (not splittable here: Sk, LR, Minv live in registers across it)
   const int lsel = C.lsel;
   if (sub == 0 && ((lsel >> (2 * NJ * L)) & ((1 << (2 * NJ)) - 1))) {
     static_for<NJ>([&](auto kc) {
@@ -1347,7 +1358,9 @@ SD int team_or16(int x) {
 // Collision detection, team mode (replaces phase_detect): the four legs' support points on lanes 0..3, the
 // twelve base points on lanes 4..15, joint-limit tests one joint per lane; masks are OR-reduced over the team.
 // The leader then records the counts and starts the articulated-inertia accumulation with the base link.
-template <typename T, int ROBOT, typename LDS, typename CH, bool UI>
+// DUO: run by the helper wavefront of duo_kernel_team between the sub-step's two workgroup barriers; C.R0 is then the main
+// wavefront's (substep_team), which the leg phase reads while this one runs.
+template <typename T, int ROBOT, typename LDS, typename CH, bool UI, bool DUO = false>
 SNI_SCALAR void phase_front_team(CH ch, const PhysParams<T> pp, const LDS lds, int t, bool valid, bool lead) {
   using RB = Robot<ROBOT>;
   constexpr int NJ = RB::NJ, NQ = RB::NQ, ST = NJ + 1;
@@ -1493,7 +1506,7 @@ SNI_SCALAR void phase_front_team(CH ch, const PhysParams<T> pp, const LDS lds, i
     });
   }
   if (!lead) return;
-  C.R0 = R0;
+  if constexpr (!DUO) C.R0 = R0;
   C.mask = mask; C.nc = __builtin_popcount(mask); C.nlim_total = nl; C.lsel = lbits;
   C.smask = sbits & mask;
   // base link terms start the articulated-inertia accumulation
@@ -2185,8 +2198,23 @@ template <typename T, int ROBOT, typename LDS> struct TeamCtx {
   static constexpr size_t bytes = TeamRows<T, LDS>::off_ctx + 4 * sizeof(SubCtx<T, ROBOT>);
 };
 
-// the leader's context C lives in LDS (see CtxLds); `C` is only dereferenced by leader lanes
+// Helper wavefront of duo_kernel_team, one sub-step: the collision front between workgroup barriers A and B, nothing else.
+// Barrier A is behind the main wavefront's integrate of the previous sub-step (state, impulse cache, the row storage the sweep
+// read) and its C.R0 / sin / cos of this one; barrier B hands the front's results (selectors, support points, distances, the
+// base contacts' rows, the base link terms) to the main wavefront's leg rows.  Two barriers per sub-step, none under a predicate.
 template <typename T, int ROBOT, typename LDS>
+SD void substep_team_helper(const PhysParams<T> pp, const LDS& lds, int t, bool lead, bool valid) {
+  using CH = typename TeamCtx<T, ROBOT, LDS>::type;
+  const CH ch{lds.lane};
+  WG_SYNC();                              // barrier A
+  if (pp.urdf_inertia()) phase_front_team<T, ROBOT, LDS, CH, true, true>(ch, pp, lds, t, valid, lead);
+  else phase_front_team<T, ROBOT, LDS, CH, false, true>(ch, pp, lds, t, valid, lead);
+  WG_SYNC();                              // barrier B (the main wavefront's is inside phase_leg_rt)
+}
+
+// the leader's context C lives in LDS (see CtxLds); `C` is only dereferenced by leader lanes
+// DUO (main wavefront of duo_kernel_team): the front is the helper's (substep_team_helper), see there; C.R0 comes from here
+template <typename T, int ROBOT, typename LDS, bool DUO = false>
 SD int substep_team(const PhysParams<T> pp, T* lam_prev, unsigned nstride, const LDS& lds, int t, bool lead, bool valid) {
   constexpr int LN = LDS::LANES;
   using TRW = TeamRows<T, LDS>;
@@ -2194,6 +2222,9 @@ SD int substep_team(const PhysParams<T> pp, T* lam_prev, unsigned nstride, const
   const CH ch{lds.lane};
   SOLO_PT_DECL();
   SOLO_PT_BEGIN();
+  if constexpr (DUO) {
+    if (lead) { SubCtx<T, ROBOT>& C = ch.get(); C.R0 = quat_to_mat(C.ps.qx, C.ps.qy, C.ps.qz, C.ps.qw); }
+  }
   if (valid && t < Robot<ROBOT>::NQ) {   // sin/cos of joint t on lane t
     SubCtx<T, ROBOT>& C = ch.get();
     T sn, cs;
@@ -2202,15 +2233,20 @@ SD int substep_team(const PhysParams<T> pp, T* lam_prev, unsigned nstride, const
   }
   SOLO_PT(0);
   const bool ui = pp.urdf_inertia();     // (uniform) K2: URDF tensors instead of the box rule
-  if (ui) phase_front_team<T, ROBOT, LDS, CH, true>(ch, pp, lds, t, valid, lead);
+  if constexpr (DUO) WG_SYNC();            // barrier A
+  else if (ui) phase_front_team<T, ROBOT, LDS, CH, true>(ch, pp, lds, t, valid, lead);
   else phase_front_team<T, ROBOT, LDS, CH, false>(ch, pp, lds, t, valid, lead);
   SOLO_PT(1);
 #if SOLO_LEG_QUAD
-  if (valid) {                                                                              // four legs on four quads (phase_leg_rt)
+  if constexpr (DUO) {                                                                      // every lane: barrier B is inside
+    if (ui) phase_leg_rt<T, ROBOT, LDS, CH, true, true>(ch, pp, lam_prev, nstride, lds, t >> 2, t & 3);
+    else phase_leg_rt<T, ROBOT, LDS, CH, false, true>(ch, pp, lam_prev, nstride, lds, t >> 2, t & 3);
+  } else if (valid) {                                                                              // four legs on four quads (phase_leg_rt)
     if (ui) phase_leg_rt<T, ROBOT, LDS, CH, true>(ch, pp, lam_prev, nstride, lds, t >> 2, t & 3);
     else phase_leg_rt<T, ROBOT, LDS, CH, false>(ch, pp, lam_prev, nstride, lds, t >> 2, t & 3);
   }
 #else
+  static_assert(!DUO, "the helper wavefront's barrier B is in the quad leg phase");
   if (valid && t < 4) {                                                                     // four legs on four lanes
     if (ui) phase_leg_rt<T, ROBOT, LDS, CH, true>(ch, pp, lam_prev, nstride, lds, t, 0);
     else phase_leg_rt<T, ROBOT, LDS, CH, false>(ch, pp, lam_prev, nstride, lds, t, 0);

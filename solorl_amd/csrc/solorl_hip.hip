@@ -615,7 +615,10 @@ SD void policy_tail_team(const PolicyTail& P, int O, int col, int t, idx_t env, 
   }
 }
 
-template <typename T, int ROBOT>
+// DUO (duo_kernel_team): the workgroup has a second wavefront, the HELPER, which runs nothing but the collision front of every
+// sub-step (substep_team_helper) while this one, the main wavefront, computes the leg dynamics; both address the workgroup's one LDS
+// block with the lane index threadIdx.x & 63.  The helper loads nothing from HBM and stores nothing to it.
+template <typename T, int ROBOT, bool DUO = false>
 SD void step_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict__ snf, const int* __restrict__ sni, int M,
                   const Layout& L, int N, const EnvParams& P, const PhysParams<T>& pp, const float* __restrict__ actions,
                   const Outputs& out, int mode) {
@@ -632,7 +635,8 @@ SD void step_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict_
   __syncthreads();
   wts_[0] = clock64();
 #endif
-  const int t = threadIdx.x & 15, col = threadIdx.x >> 4;
+  const unsigned wlane = DUO ? (threadIdx.x & 63u) : threadIdx.x;      // lane of the wavefront (DUO: two wavefronts share the block)
+  const int t = wlane & 15, col = wlane >> 4;
   // a workgroup touches only 16 B of each state field, so eight consecutive workgroups share every 128-B line; workgroup
   // ids go round-robin over the 8 XCDs (each with its own L2), hence give every XCD one CONTIGUOUS eighth of the env range
   // instead of every eighth workgroup (grid is a multiple of 8).
@@ -649,12 +653,25 @@ SD void step_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict_
   if (P.lds_poison_on) {
     using TC = TeamCtx<T, ROBOT, LDS>;
     unsigned* w = reinterpret_cast<unsigned*>(solo_smem);
-    for (unsigned k = threadIdx.x; k < TC::bytes / 4; k += 64) w[k] = P.lds_poison;
+    for (unsigned k = wlane; k < TC::bytes / 4; k += 64) w[k] = P.lds_poison;     // (DUO: both wavefronts, the same words)
     __syncthreads();
   }
   const CH ch{col};
   SubCtx<T, ROBOT>& C = ch.get();
   T* const psv = reinterpret_cast<T*>(&C.ps);
+  if constexpr (DUO) {
+    // Workgroup barriers of a step, per role: 2 x frame_skip (A and B of every sub-step; main: A in substep_team, B in phase_leg_rt;
+    // helper: both in substep_team_helper) -- plus the one behind the LDS poison fill above when that test hook is on, and, in a
+    // -DSOLO_WAVE_TIMING build, the one behind the counters' reset.  All of them sit on paths that depend on kernel arguments only.
+    if (blk * 4u >= (unsigned)N) return;              // a workgroup of the padded grid without an env: both wavefronts leave here
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) {          // ---- the helper wavefront
+#pragma unroll 1
+      for (int ss = 0; ss < P.frame_skip; ss++) substep_team_helper<T, ROBOT>(pp, lds, t, lead, valid);
+      return;
+    }
+    // an idle team of a workgroup that has envs runs the leg phase with the others (barrier B is inside): it parks nothing
+    if (!valid && t == 0) { C.mask = 0; C.nc = 0; C.nlim_total = 0; C.lsel = 0; C.smask = 0; }
+  }
   idx_t env = 0;
   // ---- the env's state, HBM -> LDS, all lanes (the state is stored by slot: slot e holds env `env`)
   T a_t = T(0);
@@ -717,7 +734,7 @@ SD void step_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict_
   for (int ss = 0; ss < P.frame_skip; ss++) {
     const T sc = (ss == 0 || P.hold_torque) ? T(1) : T(0);   // K8: Bullet clears applied torques every step
     if (valid && t < NQ) C.tau[t] = C.tau_base[t] * sc;
-    const int m = substep_team<T, ROBOT>(pp, sf + SX(L.lam, e, L.NF), 4u, lds, t, lead, valid);
+    const int m = substep_team<T, ROBOT, LDS, DUO>(pp, sf + SX(L.lam, e, L.NF), 4u, lds, t, lead, valid);
     if (lead) C.irec[IR_MASK] = m;
   }
   WT_STAMP(4);
@@ -944,6 +961,17 @@ __global__ void __launch_bounds__(64, sizeof(T) == 8 ? 1 : SOLO_WAVES_PER_SIMD)
 step_kernel_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict__ snf, const int* __restrict__ sni, int M,
                  Layout L, int N, EnvParams P, PhysParams<T> pp, const float* __restrict__ actions, Outputs out, int mode) {
   step_team<T, ROBOT>(sf, si, snf, sni, M, L, N, P, pp, actions, out, mode);
+}
+
+// Helper wavefront: step_kernel_team with a second wavefront per workgroup that runs the collision front of
+// each sub-step beside the main wavefront's leg dynamics.  Same grid, same dynamic LDS (the two share the block), same register
+// bound; chosen by launch_step while every SIMD can hold both wavefronts of its workgroup.  fp32 only.
+template <typename T, int ROBOT>
+__global__ void __launch_bounds__(128, SOLO_WAVES_PER_SIMD)
+duo_kernel_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict__ snf, const int* __restrict__ sni, int M,
+                Layout L, int N, EnvParams P, PhysParams<T> pp, const float* __restrict__ actions, Outputs out, int mode) {
+  static_assert(sizeof(T) == 4, "the helper wavefront is an fp32 kernel");
+  step_team<T, ROBOT, true>(sf, si, snf, sni, M, L, N, P, pp, actions, out, mode);
 }
 
 // K control steps in one launch (solorl_step_n, solorl_rollout): each wavefront runs step_team K times for its own four envs, and no
@@ -1212,6 +1240,7 @@ struct solorl_env {
   int lds_poison_on = 0; unsigned lds_poison = 0;   // SOLORL_POISON_LDS test hook
   int simds = 1024;          // SIMDs of the device (4 per CU): grids up to this size have a SIMD per wavefront
   int pipe_override = -1;    // SOLORL_PGS_PIPE=0/1 (dev A/B)
+  int helper_override = -1;  // SOLORL_HELPER_WAVE=0/1: pin the helper wavefront (duo_kernel_team) off / on
 };
 
 namespace {
@@ -1254,6 +1283,14 @@ static int check_lds_base(const void* kernel, bool& checked) {
   return 0;
 }
 
+// Helper wavefront (duo_kernel_team): fp32 team mode on a fixed state buffer, while the batch's grid gives every SIMD at most one
+// workgroup -- its two wavefronts then have the SIMD's two slots to themselves; SOLORL_HELPER_WAVE=0 pins it off (=1 is checked
+// against the same rule at create and refused beyond it)
+inline bool helper_wave_allowed(const solorl_env* h) {
+  return h->team && !h->f64 && !h->sort && ((((h->N + 3) / 4) + 7) & ~7) <= h->simds;
+}
+inline bool helper_wave_rule(const solorl_env* h) { return h->helper_override != 0 && helper_wave_allowed(h); }
+
 // team mode: grid (a multiple of 8: XCD-contiguous env ranges, step_team), LDS bytes, and the physics parameters with the sweep
 // variant of this batch size
 template <typename T, int ROBOT>
@@ -1274,7 +1311,7 @@ PhysParams<T> team_launch_shape(const solorl_env* h, int N, dim3& grid, size_t& 
 
 template <typename T, int ROBOT>
 int launch_step(solorl_env* h, T* sf, int* si, int N, const float* actions, const Outputs& out, int mode, hipStream_t st) {
-  static bool lds_checked[2] = {false, false};
+  static bool lds_checked[3] = {false, false, false};
   if (int rc = check_lds_base(h->team ? reinterpret_cast<const void*>(step_kernel_team<T, ROBOT>) : reinterpret_cast<const void*>(step_kernel<T, ROBOT>),
                               lds_checked[h->team ? 1 : 0])) return rc;
   if (h->team) {
@@ -1282,6 +1319,17 @@ int launch_step(solorl_env* h, T* sf, int* si, int N, const float* actions, cons
     dim3 grid, block(64);
     size_t team_smem = 0;
     const PhysParams<T> pp = team_launch_shape<T, ROBOT>(h, N, grid, team_smem);
+    if constexpr (sizeof(T) == 4) {
+      // two wavefronts per workgroup while every SIMD can hold both (the size rule of the pipelined sweep); h->N, not this launch's N:
+      // what solorl_get_property "helper_wave" reports is what every launch of the handle takes
+      if (helper_wave_rule(h)) {
+        if (int rc = check_lds_base(reinterpret_cast<const void*>(duo_kernel_team<T, ROBOT>), lds_checked[2])) return rc;
+        hipLaunchKernelGGL((duo_kernel_team<T, ROBOT>), grid, dim3(128), team_smem, st, sf, si, (const T*)h->snf, (const int*)h->sni, h->M, h->L, N,
+                           make_env_params(h), pp, actions, out, mode);
+        HIP_TRY(hipGetLastError());
+        return 0;
+      }
+    }
     hipLaunchKernelGGL(kt, grid, block, team_smem, st, sf, si, (const T*)h->snf, (const int*)h->sni, h->M, h->L, N,
                        make_env_params(h), pp, actions, out, mode);
     HIP_TRY(hipGetLastError());
@@ -1553,6 +1601,7 @@ int solorl_create(const solorl_config* cfg, int num_envs, int device_id, uint64_
     h->team = true;   // measured (tools/dev/bench_n.py): team mode wins at every batch size, 1k .. 262k envs; lane mode: SOLORL_TEAM=0
     if (const char* ev = getenv("SOLORL_TEAM")) h->team = atoi(ev) != 0;
     if (const char* ev = getenv("SOLORL_PGS_PIPE")) h->pipe_override = atoi(ev) != 0;
+    if (const char* ev = getenv("SOLORL_HELPER_WAVE")) h->helper_override = atoi(ev) != 0;
     { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device_id) == hipSuccess && prop.multiProcessorCount > 0) h->simds = 4 * prop.multiProcessorCount; }
     if (const char* ev = getenv("SOLORL_POISON_LDS")) { h->lds_poison_on = 1; h->lds_poison = (unsigned)strtoul(ev, nullptr, 0); }
     h->epw = epw;
@@ -1574,6 +1623,9 @@ int solorl_create(const solorl_config* cfg, int num_envs, int device_id, uint64_
   h->sort = false;   // measured with the team-mode sweep (tools/dev/bench_sort.sh): the sort + gather launches cost more than the
                      // padding they save at every batch size (65 536 envs: 29.5 M vs 23.8 M env-steps/s); SOLORL_SORT=1 enables it
   if (const char* ev = getenv("SOLORL_SORT")) h->sort = atoi(ev) != 0 && num_envs >= 2;
+  if (h->helper_override == 1 && !helper_wave_allowed(h))
+    return cleanup(fail(SOLORL_ERR_INVALID, "SOLORL_HELPER_WAVE=1 needs the fp32 team-mode engine without contact-count sorting and a batch of at most "
+                                            "one workgroup (four envs) per SIMD of the device: " + std::to_string(4 * h->simds) + " envs here"));
   if (h->sort) {
     if (hipMalloc(&h->sf2, h->tsize * h->L.NF * Np) != hipSuccess) return cleanup(fail(SOLORL_ERR_HIP, "hipMalloc state2"));
     if (hipMalloc(&h->si2, sizeof(int) * NI * Np) != hipSuccess) return cleanup(fail(SOLORL_ERR_HIP, "hipMalloc istate2"));
@@ -1627,6 +1679,7 @@ int solorl_get_property(const solorl_env* h, const char* name, double* value) {
   else if (n == "max_limit_rows") *value = MAX_LIMITS;
   else if (n == "f64") *value = h->f64 ? 1 : 0;
   else if (n == "step_n_one_launch") *value = step_n_one_launch(h) ? 1 : 0;
+  else if (n == "helper_wave") *value = helper_wave_rule(h) ? 1 : 0;
   else return fail(SOLORL_ERR_INVALID, "unknown property: " + n);
   return 0;
 }

@@ -20,6 +20,11 @@
 // branch, which the SIMT lowering can run first (found with the NaN-poisoned-LDS build, tools/dev/zero_region.sh).
 // Hand-offs across the non-inlined phase calls need nothing: a call orders all memory operations.
 #define TEAM_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
+// Workgroup barrier between the two wavefronts of duo_kernel_team: __syncthreads() spelled out (release fence, s_barrier, acquire
+// fence).  The library function itself cannot be inlined into a function with other target features (SNI_SCALAR): it became a call
+// in the middle of the leg phase, with the registers live across it saved around it.
+#define WG_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_s_barrier(); \
+                       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); } while (0)
 #endif
 
 namespace solo {

@@ -88,12 +88,14 @@ def kernel_resources(lib_path):
 
 
 def function_stats(lib_path):
-    """{mangled name: {"insts", "scratch", "flat", "global"}}"""
+    """{mangled name: {"insts", "body", "barriers", "scratch", "flat", "global"}}.  `insts` counts every disassembled word up to the next
+    symbol, the s_nop run that pads the function to the next one's alignment included (up to 63 for a kernel: it changes with the
+    layout of the code object, not with the function); `body` stops at the function's last instruction that is not such a filler."""
     out, cur = {}, None
     for line in disassemble(lib_path).splitlines():
         m = re.match(r"^[0-9a-f]+ <([^>]+)>:", line)
         if m:
-            cur = out.setdefault(m.group(1), dict(insts=0, scratch=0, flat=0, **{"global": 0})) if ".dup" not in m.group(1) else None
+            cur = out.setdefault(m.group(1), dict(insts=0, body=0, barriers=0, scratch=0, flat=0, **{"global": 0})) if ".dup" not in m.group(1) else None
             continue
         if cur is None or "\t" not in line:
             continue
@@ -101,6 +103,8 @@ def function_stats(lib_path):
         if not op:
             continue
         cur["insts"] += 1
+        if op != "s_nop": cur["body"] = cur["insts"]
+        if op == "s_barrier": cur["barriers"] += 1
         if op.startswith("scratch_"): cur["scratch"] += 1
         elif op.startswith("flat_"): cur["flat"] += 1
         elif op.startswith("global_"): cur["global"] += 1

@@ -341,7 +341,8 @@ class SoloVecEnv:
         _native.check(self.L.solorl_increment_curriculum(self._h, float(value)))
 
     def get_property(self, name):
-        """Read-only handle properties (include/solorl.h solorl_get_property): lanes_per_env, sweep_variant, max_contacts, ..."""
+        """Read-only handle properties (include/solorl.h solorl_get_property): lanes_per_env, sweep_variant, max_contacts,
+        max_limit_rows, f64, step_n_one_launch, helper_wave"""
         v = C.c_double()
         _native.check(self.L.solorl_get_property(self._h, name.encode(), C.byref(v)))
         return v.value

@@ -41,8 +41,9 @@ R = np.stack(recs)                      # [launch][wave][field]
 tot = R[:, :, 0] + R[:, :, 1] + R[:, :, 2]
 tick_ns = R[:, :, 3].sum() * 10.0 / tot.sum()           # ns per clock64() tick (s_memrealtime: 100 MHz); measured 1.0 on gfx950:
 us = lambda ticks: ticks * tick_ns * 1e-3               # clock64() is a constant-rate counter here, not the 2.4 GHz shader clock
-print("step_kernel_team<float, solo12>, %d envs, %d wavefronts, 40 launches at steady state; launch (HIP events, eager) %.1f us; clock64 tick %.3f ns" % (
-    N, nw, np.mean(wall), tick_ns))
+hw = env.get_property("helper_wave")
+print("%s<float, solo12>, %d envs, %d wavefronts%s, 40 launches at steady state; launch (HIP events, eager) %.1f us; clock64 tick %.3f ns" % (
+    "duo_kernel_team" if hw else "step_kernel_team", N, nw, " (the main ones; each has a helper beside it)" if hw else "", np.mean(wall), tick_ns))
 print("wavefront duration: mean %.1f us  median %.1f  p90 %.1f  p99 %.1f  slowest of a launch: mean %.1f (min %.1f max %.1f)" % (
     us(tot.mean()), us(np.median(tot)), us(np.percentile(tot, 90)), us(np.percentile(tot, 99)), us(tot.max(axis=1).mean()),
     us(tot.max(axis=1).min()), us(tot.max(axis=1).max())))
@@ -62,6 +63,10 @@ if "SOLO_SWEEP_STATS" in os.environ.get("SOLORL_BUILD_DEFINES", "") and fr > 0:
 elif fr > 0: print("friction-slot visits with zero bound and zero impulse in every lane of the wavefront (a skip would be value-exact): %.1f %% of all, %.1f %% in the slowest 1 %% of the wavefronts" % (
     100.0 * R[:, :, 27].sum() / max(fr, 1), 100.0 * R[:, :, 27][slow_].sum() / max(frs, 1)))
 phases = ["sin/cos", "collision front", "legs (4 lanes)", "leg sum", "base solve (leader)", "leg rates", "row finish", "PGS sweep", "integrate"]
+if hw:      # duo_kernel_team: the stamps are the main wavefront's; the front runs on the helper between barriers A and B
+    phases[0], phases[1], phases[2] = "R0 + sin/cos", "barrier A", "front || legs (to barrier B) + leg rows"
+phases.append("  of the legs: dynamics above the lsel read (not drained)")
+print("helper wavefront: %s (SOLORL_HELPER_WAVE=0/1 pins it)" % ("on" if hw else "off"))
 print("phases of the sub-steps, summed over a step's %d sub-steps (us; mean over all wavefronts | over the slowest 1 %%; timing build drains the memory counters at every stamp):" % c.frame_skip)
 for i, n_ in enumerate(phases):
     print("  %-28s %7.2f | %7.2f" % (n_, us(R[:, :, 16 + i].mean()), us(R[:, :, 16 + i][slow_].mean())))
