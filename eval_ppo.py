@@ -3,7 +3,8 @@
 loads `<checkpoint-dir>/solo.pt` (same dict keys as the reference's checkpoint, agents/ppo/train.py:121-131),
 rolls it out on the HIP engine until --num-runs episodes have ended and prints
 `mean length / mean reward / mean success` (test_ppo.py:147).  In place of the GUI, --dump writes env 0's
-trajectory (base pose, joint angles, action, reward, done) to an .npz."""
+trajectory (base pose, joint angles, action, reward, done) to an .npz.  --push-interval K --push-max-vel V kicks the base of every env
+every K control steps with an xy velocity drawn uniformly from +-V m/s (robustness evaluation; SoloVecEnv.push)."""
 import argparse
 import os
 import sys
@@ -22,6 +23,8 @@ def main(argv=None):
     p.add_argument("--deterministic", action="store_true")
     p.add_argument("--seed", type=int, default=7)
     p.add_argument("--dump", default=None, help="write env 0's trajectory to this .npz")
+    p.add_argument("--push-interval", type=int, default=0, help="kick every env's base velocity every K control steps (0 = never)")
+    p.add_argument("--push-max-vel", type=float, default=0.0, help="a kick's x and y velocity change is uniform in +-V m/s")
     a = p.parse_args(argv)
 
     import numpy as np
@@ -45,7 +48,16 @@ def main(argv=None):
     ret = torch.zeros(a.num_agents, device=dev)
     traj = dict(pos=[], quat=[], q=[], action=[], reward=[], done=[])
     obs = env.reset()
+    push_gen, steps = None, 0
+    if a.push_interval > 0:
+        push_gen = torch.Generator(device=dev); push_gen.manual_seed(a.seed)
+        dv = torch.zeros((a.num_agents, 3), device=dev)
     while len(ep_len) < a.num_runs:
+        if push_gen is not None and steps > 0 and steps % a.push_interval == 0:
+            dv[:, :2] = (torch.rand((a.num_agents, 2), device=dev, generator=push_gen) * 2 - 1) * a.push_max_vel
+            env.push(dv)
+            obs = env.get_observation()          # the policy sees the kicked velocities
+        steps += 1
         with torch.no_grad():
             _, action, _ = policy.act(obs, deterministic=a.deterministic)
         if a.dump:

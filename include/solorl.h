@@ -27,6 +27,12 @@
  *   solorl_step_n / solorl_rollout : K x solorl_step / solorl_step_act in one launch (no reference counterpart: the reference's
  *                             send-all / receive-all of agents/ppo/envs.py:91-95 is a barrier between every two steps)
  *   solorl_get_state / solorl_set_state / solorl_get_property : no reference counterpart (parity-test hooks, run records)
+ *   solorl_get_states / solorl_set_states / solorl_reset_masked : the whole batch's state as ONE DEVICE array of solorl_env_state
+ *                             rows, read and written by a kernel on the caller's stream (no reference counterpart: the reference
+ *                             reaches an env's state only inside its worker process).  What pushes (kick the base velocity of every
+ *                             env), starts from a chosen state distribution, branching one env into many, resetting a chosen subset,
+ *                             saving / restoring a batch and logging a batch reduce to.  Row i is env i of the handle; a byte mask
+ *                             selects envs, SOLORL_SF_* bits select member groups on write.  No host synchronisation: capturable.
  *   solorl_destroy         <- agents/ppo/envs.py:129-135 (close)
  *
  * Plain pointers and sizes only; no torch types.  All array arguments are DEVICE pointers
@@ -160,7 +166,8 @@ typedef struct solorl_info_soa {
 #define SOLORL_EPSTAT_FIELDS 10
 
 /* Physical + bookkeeping state of ONE env in a fixed, precision-independent (double) layout;
- * used by solorl_get_state/solorl_set_state (HOST pointers) for parity tests. */
+ * used by solorl_get_state/solorl_set_state (HOST pointers) for parity tests, and as the row type of the batched
+ * solorl_get_states / solorl_set_states (DEVICE rows). */
 #define SOLORL_STATE_MAX_DOF 12
 #define SOLORL_STATE_MAX_PRIMS 24
 #define SOLORL_STATE_MAX_OBS 42
@@ -216,6 +223,38 @@ int solorl_get_property(const solorl_env* env, const char* name, double* value);
 
 int solorl_get_state(solorl_env* env, int env_index, solorl_env_state* out /* host */);
 int solorl_set_state(solorl_env* env, int env_index, const solorl_env_state* in /* host */);
+
+/* Batched state access: the state of every env of the handle as `solorl_env_state rows[num_envs]` in DEVICE memory, moved by one kernel
+ * launch on `stream`.  No host synchronisation, no allocation (capturable in a HIP graph, unlike solorl_get_state / solorl_set_state).
+ *   Row i is ENV i of the handle (whatever storage slot the engine keeps it in; with contact-count sorting the kernel reads the
+ *   slot -> env map itself).  mask: [num_envs] bytes on the device, or NULL = every env; a row whose mask byte is 0 is neither read
+ *   nor written, in either direction.
+ *   Values exactly as the per-env functions give and take them: an fp32 handle rounds each double to float on write and widens on
+ *   read, an fp64 handle copies bits; `tau`, the joints 8..11 of a Solo8 handle and history levels the handle does not store read 0
+ *   and are ignored on write.
+ * solorl_set_states copies the member groups named by `fields` and leaves everything else of the env as it is:
+ *   POSE pos, quat (and the engine's previous-xy, set to pos xy as solorl_set_state does) | VEL lin_vel, ang_vel | JOINT_POS q |
+ *   JOINT_VEL qd | CONTACT lambda_prev, contact_mask | HISTORY hist | TASK goal, potential, progress, goals_reached,
+ *   env_goals_reached, dr, treadmill_y | COUNTERS timestep, need_reset, rng_counter.
+ *   NOTHING ELSE IS DERIVED on a partial write: a caller who moves a pointgoal env with POSE also writes `potential` (the distance to the
+ *   goal the next step's `progress` is measured from) with TASK; one who changes q leaves the history's old angles unless it writes
+ *   HISTORY.  fields == 0 or bits outside SOLORL_SF_ALL: SOLORL_ERR_INVALID.
+ *   "Has been reset": solorl_set_states(mask = NULL, fields = SOLORL_SF_ALL) gives every env a complete state and marks the handle as
+ *   reset, whatever the rows' need_reset members say -- the host cannot read them without synchronising, so they are the caller's
+ *   business (solorl_set_state, which sees its one host row, marks the handle only when that row's need_reset is 0).  Any other
+ *   solorl_set_states, and solorl_reset_masked, return SOLORL_ERR_STATE on a handle that has not been reset.  solorl_get_states is
+ *   always allowed.
+ * solorl_reset_masked: solorl_reset for the envs whose mask byte is non-zero -- the same snapshot draw from the env's own Philox counter
+ *   that a full reset or an in-step auto-reset of that env would make next.  obs_out ([N*O], or NULL): rows of the selected envs only.
+ * Null handle, out, in, or (solorl_reset_masked) mask: SOLORL_ERR_INVALID, the message names the function. */
+enum { SOLORL_SF_POSE = 1, SOLORL_SF_VEL = 2, SOLORL_SF_JOINT_POS = 4, SOLORL_SF_JOINT_VEL = 8, SOLORL_SF_CONTACT = 16,
+       SOLORL_SF_HISTORY = 32, SOLORL_SF_TASK = 64, SOLORL_SF_COUNTERS = 128, SOLORL_SF_ALL = 255 };
+int solorl_get_states(solorl_env* env, const uint8_t* mask /* [N] device, or NULL = all */,
+                      solorl_env_state* out /* [N] DEVICE rows */, void* stream);
+int solorl_set_states(solorl_env* env, const uint8_t* mask, const solorl_env_state* in /* [N] DEVICE rows */,
+                      uint32_t fields, void* stream);
+int solorl_reset_masked(solorl_env* env, const uint8_t* mask /* [N] device, not NULL */,
+                        float* obs_out /* [N*O] or NULL */, void* stream);
 
 /* Fused return computation over a rollout of T steps x N envs (device arrays, time-major [t][n]).
  * use_gae != 0:  value_preds[T][:] = next_value;  delta_t = r_t + gamma V_{t+1} m_{t+1} - V_t;

@@ -16,7 +16,8 @@ LIB_PATH = os.environ.get("SOLORL_LIB") or os.path.join(os.path.dirname(os.path.
 SYMBOLS = ("solorl_default_config", "solorl_create", "solorl_destroy", "solorl_dims", "solorl_reset", "solorl_step",
            "solorl_get_observation", "solorl_increment_curriculum", "solorl_get_state", "solorl_set_state", "solorl_get_property",
            "solorl_compute_returns", "solorl_ppo_loss", "solorl_policy_act", "solorl_ppo_grad_stage1", "solorl_ppo_grad_stage2", "solorl_ppo_grad_count", "solorl_ppo_clip_adam", "solorl_last_error", "solorl_version",
-           "solorl_abi_version", "solorl_step_act", "solorl_ppo_scratch_count", "solorl_step_n", "solorl_rollout")
+           "solorl_abi_version", "solorl_step_act", "solorl_ppo_scratch_count", "solorl_step_n", "solorl_rollout",
+           "solorl_get_states", "solorl_set_states", "solorl_reset_masked")
 
 
 class PolicyParams(C.Structure):            # solorl_policy_params
@@ -74,6 +75,12 @@ def lib():
         L.solorl_increment_curriculum.argtypes = [C.c_void_p, C.c_double]
         L.solorl_get_state.argtypes = [C.c_void_p, C.c_int, C.POINTER(EnvState)]
         L.solorl_set_state.argtypes = [C.c_void_p, C.c_int, C.POINTER(EnvState)]
+        # batched state access: mask, rows and observations are device pointers
+        L.solorl_get_states.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.solorl_set_states.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.solorl_reset_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        for f in (L.solorl_get_states, L.solorl_set_states, L.solorl_reset_masked):
+            f.restype = C.c_int
         L.solorl_get_property.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]
         L.solorl_ppo_loss.argtypes = [C.c_void_p] * 8 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_int, C.c_void_p]

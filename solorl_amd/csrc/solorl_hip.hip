@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1116,6 +1117,121 @@ __global__ void gather_state_kernel(const T* __restrict__ sf, const int* __restr
   else di[SX(f - NF, (idx_t)j, NI)] = si[SX(f - NF, (idx_t)src, NI)];
 }
 
+// ---- batched state access (solorl_get_states / solorl_set_states): the whole batch as [N] rows of solorl_env_state on the device
+// The two sides of the copy have different shapes: the state is AoSoA-4 (SX: a slot group is one contiguous block of NF x 4 values),
+// a row is 255 eight-byte words.  A thread per env walking its row would put 2040 B between neighbouring lanes on every row access
+// (one 64-B sector per lane and instruction), so: one workgroup per slot group, the group's block staged in LDS; on the state side the
+// lanes walk the block itself (whole [field][4] sectors), on the row side they stride over the 4 x 255 words of the group's four rows
+// -- consecutive words of a row, and with linear ids of four adjacent rows.  What a word is comes from a 255-entry table the host
+// builds once per handle from its Layout (build_state_table): bits 0..15 = a state field, or one of the codes below; bits 16..23 = the
+// SOLORL_SF_* group(s) it belongs to.  Entries 256.. of the same array: the group of every state FIELD (xyprev: POSE), which selects
+// what the set kernel writes back.  The static LDS below is these kernels' own (the step kernels' rule is per kernel, check_lds_base).
+constexpr int ST_WORDS = sizeof(solorl_env_state) / 8;      // 255: 253 doubles + four int32
+constexpr int ST_MAXNF = 256;                               // largest Layout::NF (Solo12, four history levels); solorl_create checks
+enum : unsigned { ST_ZERO = 0xFFFFu, ST_INT_A = 0xFFFEu /* timestep, need_reset */, ST_INT_B = 0xFFFDu /* contact_mask, rng_counter */ };
+static_assert(sizeof(solorl_env_state) == 8 * ST_WORDS && ST_WORDS <= 256, "rows are walked as 8-byte words");
+
+// env id (= row) of the group's slot t, or -1 where the slot lies beyond N or its env is masked out: such a row is never touched
+SD int state_row_of(const int* gi, unsigned g, unsigned t, int N, int linear_ids, const unsigned char* mask) {
+  const unsigned slot = 4u * g + t;
+  if (slot >= (unsigned)N) return -1;
+  const int env = linear_ids ? (int)slot : gi[(I_ENVID << 2) + t];
+  return (mask && !mask[env]) ? -1 : env;
+}
+SD void state_word_of(int k, int& s, int& w) { s = (k >= ST_WORDS) + (k >= 2 * ST_WORDS) + (k >= 3 * ST_WORDS); w = k - ST_WORDS * s; }
+
+template <typename T>
+__global__ void __launch_bounds__(256) get_states_kernel(const T* __restrict__ sf, const int* __restrict__ si, int NF, int N, int linear_ids,
+                                                         const unsigned* __restrict__ tab, const unsigned char* __restrict__ mask,
+                                                         unsigned long long* __restrict__ out) {
+  __shared__ T stage[ST_MAXNF * 4];
+  __shared__ int ints[NI * 4];
+  __shared__ int rowof[4];
+  const unsigned g = blockIdx.x, t = threadIdx.x;
+  const T* gf = sf + (size_t)g * (size_t)(NF << 2);
+  const int* gi = si + (size_t)g * (NI << 2);
+  if (t < 4) rowof[t] = state_row_of(gi, g, t, N, linear_ids, mask);
+  __syncthreads();
+  if ((rowof[0] & rowof[1] & rowof[2] & rowof[3]) < 0) return;      // no row of this group is wanted (the whole workgroup leaves): a read of a few envs loads only their groups
+  for (int k = t; k < (NF << 2); k += 256) stage[k] = gf[k];
+  if (t < NI * 4) ints[t] = gi[t];
+  __syncthreads();
+  for (int k = t; k < 4 * ST_WORDS; k += 256) {
+    int s, w; state_word_of(k, s, w);
+    const int env = rowof[s];
+    if (env < 0) continue;
+    const unsigned code = tab[w] & 0xFFFFu;
+    unsigned long long bits = 0ull;                       // ST_ZERO: tau, joints / history levels the handle does not have
+    if (code < ST_INT_B) bits = (unsigned long long)__double_as_longlong((double)stage[(code << 2) + s]);
+    else if (code == ST_INT_A) bits = (unsigned)ints[(I_TIMESTEP << 2) + s] | ((unsigned long long)(unsigned)ints[(I_NEEDRESET << 2) + s] << 32);
+    else if (code == ST_INT_B) bits = (unsigned)ints[(I_MASK << 2) + s] | ((unsigned long long)(unsigned)ints[(I_RNG << 2) + s] << 32);
+    out[(size_t)env * ST_WORDS + w] = bits;
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) set_states_kernel(T* __restrict__ sf, int* __restrict__ si, int NF, int N, int linear_ids,
+                                                         const unsigned* __restrict__ tab, const unsigned char* __restrict__ mask,
+                                                         const unsigned long long* __restrict__ in, unsigned fields, int xyprev) {
+  __shared__ T stage[ST_MAXNF * 4];
+  __shared__ int ints[NI * 4];
+  __shared__ int rowof[4];
+  const unsigned g = blockIdx.x, t = threadIdx.x;
+  T* gf = sf + (size_t)g * (size_t)(NF << 2);
+  int* gi = si + (size_t)g * (NI << 2);
+  if (t < 4) rowof[t] = state_row_of(gi, g, t, N, linear_ids, mask);
+  __syncthreads();
+  // rows -> the group's block in LDS: only the words of selected groups of selected rows are read
+  for (int k = t; k < 4 * ST_WORDS; k += 256) {
+    int s, w; state_word_of(k, s, w);
+    const int env = rowof[s];
+    if (env < 0) continue;
+    const unsigned e = tab[w];
+    if (!((e >> 16) & fields)) continue;                  // (ST_ZERO entries belong to no group)
+    const unsigned code = e & 0xFFFFu;
+    const unsigned long long bits = in[(size_t)env * ST_WORDS + w];
+    if (code < ST_INT_B) {
+      const T v = (T)__longlong_as_double((long long)bits);
+      stage[(code << 2) + s] = v;
+      if (w < 2) stage[((xyprev + w) << 2) + s] = v;      // pos x, y are a row's words 0, 1: xyprev = pos xy, as solorl_set_state
+    } else if (code == ST_INT_A) {
+      ints[(I_TIMESTEP << 2) + s] = (int)(unsigned)bits; ints[(I_NEEDRESET << 2) + s] = (int)(unsigned)(bits >> 32);
+    } else {                                              // contact_mask (CONTACT) and rng_counter (COUNTERS) share a word
+      if (fields & SOLORL_SF_CONTACT) ints[(I_MASK << 2) + s] = (int)(unsigned)bits;
+      if (fields & SOLORL_SF_COUNTERS) ints[(I_RNG << 2) + s] = (int)(unsigned)(bits >> 32);
+    }
+  }
+  __syncthreads();
+  // LDS -> state: exactly the elements written above (same selection, by field), in the block's own order
+  const unsigned* ftab = tab + 256;
+  for (int k = t; k < (NF << 2); k += 256)
+    if (rowof[k & 3] >= 0 && (ftab[k >> 2] & fields)) gf[k] = stage[k];
+  if (t < NI * 4) {
+    const unsigned kk = t >> 2;
+    const unsigned grp = kk == I_MASK ? SOLORL_SF_CONTACT : (kk == I_ENVID ? 0u : SOLORL_SF_COUNTERS);
+    if (rowof[t & 3] >= 0 && (grp & fields)) gi[t] = ints[t];
+  }
+}
+static_assert(offsetof(solorl_env_state, pos) == 0, "set_states_kernel derives xyprev from a row's words 0 and 1");
+
+// solorl_reset_masked: reset_kernel for the envs whose mask byte is set (same draws from the env's own Philox counter).  A copy of
+// reset_kernel with the mask test in front rather than a nullable argument to it, on purpose: reset_kernel and solorl_reset stay the
+// code they were, instruction for instruction.
+template <typename T, int ROBOT>
+__global__ void reset_masked_kernel(T* sf, int* si, const T* snf, const int* sni, int M, Layout L, int N, EnvParams P,
+                                    const unsigned char* mask, float* obs) {
+  const idx_t e = (idx_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (idx_t)N) return;
+  const idx_t env = (idx_t)si[SX(I_ENVID, e, NI)];
+  if (!mask[env]) return;
+  Env<T, Robot<ROBOT>::NQ> E;
+  load_env(E, sf, si, L, (idx_t)N, e);
+  reset_from_snapshot<T, ROBOT>(E, sf, L, (idx_t)N, e, env, snf, sni, M, P);
+  if (obs) write_obs<T, ROBOT>(E, sf, L, (idx_t)N, e, env, P.task, obs);
+  store_env(E, sf, si, L, (idx_t)N, e);
+  si[SX(I_NEEDRESET, e, NI)] = 0;
+}
+
 // ---- fused GAE / discounted returns (agents/ppo/storage.py:35-55): one thread per env walks the rollout
 // backwards; every access is coalesced across envs.  HBM-bound: 16 B per (t, env) sample.
 __global__ void returns_kernel(const float* __restrict__ rew, float* __restrict__ val, const float* __restrict__ msk,
@@ -1234,6 +1350,7 @@ struct solorl_env {
   uint64_t seed = 0; int64_t id0 = 0;
   double goal_radius = 2.0;
   double* dyn = nullptr;   // device copy of the mutable parameters (EnvParams::dyn)
+  unsigned* stab = nullptr;   // device copy of the row-word / field-group table of get_states_kernel / set_states_kernel (build_state_table)
   int epw = 64;   // envs per wavefront (lanes per workgroup)
   bool spread = true;
   bool team = false;   // 16 lanes per env (set at create: default true)
@@ -1481,6 +1598,37 @@ template <typename T> int build_snapshots_t(solorl_env* h) {
   return 0;
 }
 
+// The table of get_states_kernel / set_states_kernel (see there): entry w < 255 says what word w of a solorl_env_state row is -- a state
+// field of this handle's Layout, an integer pair, or nothing (reads 0, ignored on write) -- and which SOLORL_SF_* group it belongs to;
+// entry 256 + f is the group of state field f.  The members' places come from the struct itself (offsetof).
+void build_state_table(const Layout& L, int n, std::vector<unsigned>& tab) {
+  tab.assign(512, 0u);
+  for (int w = 0; w < 256; w++) tab[w] = ST_ZERO;
+  auto put = [&](size_t offset, int count, int field, unsigned group) {
+    for (int k = 0; k < count; k++) {
+      tab[offset / 8 + k] = (unsigned)(field + k) | (group << 16);
+      tab[256 + field + k] = group;
+    }
+  };
+#define ST_PUT(member, count, field, group) put(offsetof(solorl_env_state, member), count, field, group)
+  ST_PUT(pos, 3, L.pos, SOLORL_SF_POSE); ST_PUT(quat, 4, L.quat, SOLORL_SF_POSE);
+  ST_PUT(lin_vel, 3, L.v, SOLORL_SF_VEL); ST_PUT(ang_vel, 3, L.w, SOLORL_SF_VEL);
+  ST_PUT(q, n, L.q, SOLORL_SF_JOINT_POS); ST_PUT(qd, n, L.qd, SOLORL_SF_JOINT_VEL);
+  ST_PUT(lambda_prev, NPRIM, L.lam, SOLORL_SF_CONTACT);
+  for (int hh = 0; hh < (L.H > 2 ? L.H : 2); hh++)      // the levels the handle stores
+    put(offsetof(solorl_env_state, hist) + sizeof(double) * DMAX * hh, DMAX, L.hist + hh * HSTRIDE, SOLORL_SF_HISTORY);
+  ST_PUT(goal, 2, L.goal, SOLORL_SF_TASK); ST_PUT(potential, 1, L.pot, SOLORL_SF_TASK); ST_PUT(progress, 1, L.prog, SOLORL_SF_TASK);
+  ST_PUT(goals_reached, 1, L.goals, SOLORL_SF_TASK); ST_PUT(env_goals_reached, 1, L.egoals, SOLORL_SF_TASK);
+  ST_PUT(dr, 5, L.dr, SOLORL_SF_TASK); ST_PUT(treadmill_y, 1, L.tmy, SOLORL_SF_TASK);
+#undef ST_PUT
+  tab[256 + L.xyprev] = tab[256 + L.xyprev + 1] = SOLORL_SF_POSE;
+  tab[offsetof(solorl_env_state, timestep) / 8] = ST_INT_A | ((unsigned)SOLORL_SF_COUNTERS << 16);
+  tab[offsetof(solorl_env_state, contact_mask) / 8] = ST_INT_B | ((unsigned)(SOLORL_SF_CONTACT | SOLORL_SF_COUNTERS) << 16);
+}
+static_assert(offsetof(solorl_env_state, need_reset) == offsetof(solorl_env_state, timestep) + 4 && offsetof(solorl_env_state, timestep) % 8 == 0 &&
+              offsetof(solorl_env_state, rng_counter) == offsetof(solorl_env_state, contact_mask) + 4 && NPRIM <= SOLORL_STATE_MAX_PRIMS,
+              "the integer members are two 8-byte words: (timestep, need_reset), (contact_mask, rng_counter)");
+
 int check_cfg(const solorl_config* c) {
   if (!c) return fail(SOLORL_ERR_INVALID, "null config");
   if (c->robot != SOLORL_ROBOT_SOLO8 && c->robot != SOLORL_ROBOT_SOLO12) return fail(SOLORL_ERR_INVALID, "robot must be SOLO8 or SOLO12");
@@ -1620,6 +1768,13 @@ int solorl_create(const solorl_config* cfg, int num_envs, int device_id, uint64_
     if (hipMalloc(&h->dyn, sizeof dyn0) != hipSuccess) return cleanup(fail(SOLORL_ERR_HIP, "hipMalloc dyn"));
     if (hipMemcpy(h->dyn, dyn0, sizeof dyn0, hipMemcpyHostToDevice) != hipSuccess) return cleanup(fail(SOLORL_ERR_HIP, "hipMemcpy dyn"));
   }
+  {
+    if (h->L.NF > ST_MAXNF) return cleanup(fail(SOLORL_ERR_INVALID, "state layout wider than the batched state kernels' staging block"));
+    std::vector<unsigned> tab;
+    build_state_table(h->L, h->n, tab);
+    if (hipMalloc(&h->stab, sizeof(unsigned) * tab.size()) != hipSuccess) return cleanup(fail(SOLORL_ERR_HIP, "hipMalloc state table"));
+    if (hipMemcpy(h->stab, tab.data(), sizeof(unsigned) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) return cleanup(fail(SOLORL_ERR_HIP, "hipMemcpy state table"));
+  }
   h->sort = false;   // measured with the team-mode sweep (tools/dev/bench_sort.sh): the sort + gather launches cost more than the
                      // padding they save at every batch size (65 536 envs: 29.5 M vs 23.8 M env-steps/s); SOLORL_SORT=1 enables it
   if (const char* ev = getenv("SOLORL_SORT")) h->sort = atoi(ev) != 0 && num_envs >= 2;
@@ -1652,6 +1807,7 @@ int solorl_destroy(solorl_env* h) {
   if (h->si2) hipFree(h->si2);
   if (h->perm) hipFree(h->perm);
   if (h->dyn) hipFree(h->dyn);
+  if (h->stab) hipFree(h->stab);
   delete h;
   return 0;
 }
@@ -1892,6 +2048,61 @@ int solorl_set_state(solorl_env* h, int i, const solorl_env_state* in) {
   }
   HIP_TRY(hipMemcpy2D((char*)h->si + sizeof(int) * slot0i, sizeof(int) * 4, iv, sizeof(int), sizeof(int), NI, hipMemcpyHostToDevice));
   if (!in->need_reset) h->reset_called = true;
+  return 0;
+}
+
+// ---- the whole batch's state as one device array (get_states_kernel / set_states_kernel above): no host synchronisation, no
+// allocation, no slot lookup on the host -- under contact-count sorting every slot's thread reads its env id, as reset_kernel does
+static dim3 state_grid(const solorl_env* h) { return dim3((unsigned)((h->N + 3) / 4)); }
+
+int solorl_get_states(solorl_env* h, const uint8_t* mask, solorl_env_state* out, void* stream) {
+  if (!h) return fail(SOLORL_ERR_INVALID, "solorl_get_states: null handle");
+  if (!out) return fail(SOLORL_ERR_INVALID, "solorl_get_states: null out array");
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (h->f64) hipLaunchKernelGGL(get_states_kernel<double>, state_grid(h), dim3(256), 0, st, (const double*)h->sf, (const int*)h->si, h->L.NF, h->N, h->sort ? 0 : 1,
+                                 (const unsigned*)h->stab, mask, (unsigned long long*)out);
+  else hipLaunchKernelGGL(get_states_kernel<float>, state_grid(h), dim3(256), 0, st, (const float*)h->sf, (const int*)h->si, h->L.NF, h->N, h->sort ? 0 : 1,
+                          (const unsigned*)h->stab, mask, (unsigned long long*)out);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int solorl_set_states(solorl_env* h, const uint8_t* mask, const solorl_env_state* in, uint32_t fields, void* stream) {
+  if (!h) return fail(SOLORL_ERR_INVALID, "solorl_set_states: null handle");
+  if (!in) return fail(SOLORL_ERR_INVALID, "solorl_set_states: null in array");
+  if (fields == 0 || (fields & ~(uint32_t)SOLORL_SF_ALL)) return fail(SOLORL_ERR_INVALID, "solorl_set_states: fields must be a non-empty set of SOLORL_SF_* bits");
+  const bool whole = !mask && fields == (uint32_t)SOLORL_SF_ALL;
+  if (!whole && !h->reset_called)
+    return fail(SOLORL_ERR_STATE, "solorl_set_states: a partial write (a mask, or fewer than all field groups) needs a handle that has been reset");
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (h->f64) hipLaunchKernelGGL(set_states_kernel<double>, state_grid(h), dim3(256), 0, st, (double*)h->sf, h->si, h->L.NF, h->N, h->sort ? 0 : 1,
+                                 (const unsigned*)h->stab, mask, (const unsigned long long*)in, (unsigned)fields, h->L.xyprev);
+  else hipLaunchKernelGGL(set_states_kernel<float>, state_grid(h), dim3(256), 0, st, (float*)h->sf, h->si, h->L.NF, h->N, h->sort ? 0 : 1,
+                          (const unsigned*)h->stab, mask, (const unsigned long long*)in, (unsigned)fields, h->L.xyprev);
+  HIP_TRY(hipGetLastError());
+  if (whole) h->reset_called = true;      // every env now holds a caller-given state (the rows' own need_reset values are the caller's business)
+  return 0;
+}
+
+int solorl_reset_masked(solorl_env* h, const uint8_t* mask, float* obs_out, void* stream) {
+  if (!h) return fail(SOLORL_ERR_INVALID, "solorl_reset_masked: null handle");
+  if (!mask) return fail(SOLORL_ERR_INVALID, "solorl_reset_masked: null mask");
+  if (!h->reset_called) return fail(SOLORL_ERR_STATE, "solorl_reset_masked: needs a handle that has been reset");
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  EnvParams P = make_env_params(h);
+  dim3 g((h->N + 255) / 256), b(256);
+  const bool s12 = h->cfg.robot == SOLORL_ROBOT_SOLO12;
+  if (h->f64) {
+    if (s12) hipLaunchKernelGGL((reset_masked_kernel<double, 1>), g, b, 0, st, (double*)h->sf, h->si, (const double*)h->snf, (const int*)h->sni, h->M, h->L, h->N, P, mask, obs_out);
+    else hipLaunchKernelGGL((reset_masked_kernel<double, 0>), g, b, 0, st, (double*)h->sf, h->si, (const double*)h->snf, (const int*)h->sni, h->M, h->L, h->N, P, mask, obs_out);
+  } else {
+    if (s12) hipLaunchKernelGGL((reset_masked_kernel<float, 1>), g, b, 0, st, (float*)h->sf, h->si, (const float*)h->snf, (const int*)h->sni, h->M, h->L, h->N, P, mask, obs_out);
+    else hipLaunchKernelGGL((reset_masked_kernel<float, 0>), g, b, 0, st, (float*)h->sf, h->si, (const float*)h->snf, (const int*)h->sni, h->M, h->L, h->N, P, mask, obs_out);
+  }
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 

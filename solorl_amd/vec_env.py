@@ -6,6 +6,8 @@
   step(actions Tensor[N, A]) -> (obs[N,O], reward[N,1], done[N] f32, infos)   (envs.py:189-196)
   step_n(actions Tensor[K, N, A]) -> (obs[K,N,O], reward[K,N,1], done[K,N] f32, infos)  (K steps, one launch: no reference counterpart)
   get_observation(), increment_curriculum(), close(), observation_space, action_space, nenvs
+  get_states(mask) -> StateBatch, set_states(states, mask, fields), reset_masked(mask) -> obs, push(dv, mask)   (the whole batch's state as
+      one device array, include/solorl.h solorl_get_states ...: no reference counterpart)
 
 torch is plumbing only: it owns the device buffers and the stream; all arithmetic happens in
 ``libsolorl_hip.so`` on the caller's current HIP stream (no host synchronisation in step()).
@@ -17,6 +19,7 @@ import torch
 
 from . import _native
 from .config import SoloConfig, EnvState, InfoSoA, config_from_dict, EPSTAT_FIELDS, EPSTAT_NAMES
+from .state import StateBatch, field_bits, SF_VEL
 
 
 class Box:
@@ -123,6 +126,7 @@ class SoloVecEnv:
         # graph captured earlier would keep replaying the NULL it was captured with)
         self._tau = torch.zeros((N, self.act_dim), dtype=torch.float32, **kw) if applied_torque else None
         self._steps_issued = 0
+        self._push_states = None    # engine-owned StateBatch of push(), allocated at its first call
         self._kbuf = {}             # engine-owned [K, ...] rows of step_n_inplace / rollout_inplace, per K
         self._info_c = InfoSoA(ep_stats=self._ep_stats.data_ptr(), applied_torque=None if self._tau is None else self._tau.data_ptr(),
                                **{k: self._info[k].data_ptr() for k in _INFO_KEYS})
@@ -354,6 +358,72 @@ class SoloVecEnv:
 
     def set_state(self, i, s):
         _native.check(self.L.solorl_set_state(self._h, int(i), C.byref(s)))
+
+    # ---- the whole batch's state on the device (include/solorl.h solorl_get_states / solorl_set_states / solorl_reset_masked):
+    # one launch each on the current stream, no host synchronisation -- capturable in a HIP graph
+    def _mask(self, mask):
+        """None, or a [N] torch.bool / torch.uint8 tensor on this device -> (tensor kept alive for the call, pointer)"""
+        if mask is None:
+            return None, C.c_void_p(0)
+        if not (mask.is_cuda and mask.device == self.device and mask.dtype in (torch.bool, torch.uint8) and mask.is_contiguous()
+                and tuple(mask.shape) == (self.nenvs,)):
+            raise AssertionError("mask must be a contiguous torch.bool or torch.uint8 [%d] tensor on %s" % (self.nenvs, self.device))
+        m = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+        return m, C.c_void_p(m.data_ptr())
+
+    def _rows(self, name, states):
+        if not isinstance(states, StateBatch):
+            raise AssertionError("%s must be a StateBatch" % name)
+        d = states.data
+        if not (d.is_cuda and d.device == self.device and d.shape[0] == self.nenvs):
+            raise AssertionError("%s must hold %d rows on %s, got %d on %s" % (name, self.nenvs, self.device, d.shape[0], d.device))
+        return C.c_void_p(d.data_ptr())
+
+    def get_states(self, mask=None, out=None):
+        """The state of every env (row i = env i) as a StateBatch on this device.  ``mask``: rows of unselected envs are left as they
+        are in ``out`` (zeros in a fresh one)."""
+        if out is None:
+            out = StateBatch(self.nenvs, self.device)
+        m, pm = self._mask(mask)
+        with torch.cuda.device(self.device):
+            _native.check(self.L.solorl_get_states(self._h, pm, self._rows("out", out), self._stream()))
+        return out
+
+    def set_states(self, states, mask=None, fields="all"):
+        """Writes the member groups ``fields`` (a name, an iterable of names -- pose, vel, joint_pos, joint_vel, contact, history, task,
+        counters, all -- or an int of SOLORL_SF_* bits) of the selected envs from ``states``; everything else stays.  Nothing is derived
+        on a partial write except the engine's previous-xy from ``pos`` (include/solorl.h): teleporting a pointgoal env needs
+        ``potential`` rewritten too.  Without mask and with all groups it also counts as the handle's reset."""
+        m, pm = self._mask(mask)
+        with torch.cuda.device(self.device):
+            _native.check(self.L.solorl_set_states(self._h, pm, self._rows("states", states), field_bits(fields), self._stream()))
+
+    def reset_masked(self, mask):
+        """reset() for the envs selected by ``mask`` only (each draws from its own Philox counter, as at a full or an in-step reset)
+        -> obs [N, O]: the rows of the selected envs are their reset observations, every other row is that env's CURRENT observation
+        (the observation buffer is refilled by solorl_get_observation first)."""
+        m, pm = self._mask(mask)
+        if m is None:
+            raise AssertionError("reset_masked needs a mask (reset() resets every env)")
+        with torch.cuda.device(self.device):
+            _native.check(self.L.solorl_get_observation(self._h, C.c_void_p(self._obs.data_ptr()), self._stream()))
+            _native.check(self.L.solorl_reset_masked(self._h, pm, C.c_void_p(self._obs.data_ptr()), self._stream()))
+        return self._obs.clone()
+
+    def push(self, dv, mask=None):
+        """Kicks the base velocity of the selected envs: ``dv`` [N, 3] is added to the linear velocity, [N, 6] to (linear, angular),
+        world frame.  get_states -> add -> set_states(fields = vel) on an engine-owned StateBatch (allocated at the first call, so a
+        HIP graph captured after a warm-up call keeps using it); nothing but the two velocities is written."""
+        if dv.dim() != 2 or dv.shape[0] != self.nenvs or dv.shape[1] not in (3, 6) or dv.device != self.device:
+            raise AssertionError("dv must be [%d, 3] or [%d, 6] on %s" % (self.nenvs, self.nenvs, self.device))
+        if self._push_states is None:
+            self._push_states = StateBatch(self.nenvs, self.device)
+        s = self._push_states
+        self.get_states(mask, out=s)
+        s.lin_vel.add_(dv[:, :3])
+        if dv.shape[1] == 6:
+            s.ang_vel.add_(dv[:, 3:])
+        self.set_states(s, mask, SF_VEL)
 
     def close(self):
         if not self.closed and getattr(self, "_h", None):
