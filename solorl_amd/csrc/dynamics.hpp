@@ -304,7 +304,13 @@ template <typename T> SD void sincos_t(T x, T& s, T& c) {
     const float sp = fmaf(fmaf(fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f), z * r, r);
     const float cp = fmaf(fmaf(fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f), z * z,
                           fmaf(-0.5f, z, 1.0f));
+#ifdef SOLO_HOST_SHIM
+    // host test build only: k is NaN / huge for a non-finite angle and C++ leaves that conversion undefined.  The device's
+    // v_cvt_i32_f32 is defined for every input (NaN -> 0, saturating) and q only picks a quadrant, it indexes nothing.
+    const int q = (fabsf(k) < 2147483520.0f ? (int)k : 0) & 3;
+#else
     const int q = (int)k & 3;
+#endif
     const float ss = (q & 1) ? cp : sp, cc = (q & 1) ? sp : cp;
     s = (q & 2) ? -ss : ss;
     c = ((q + 1) & 2) ? -cc : cc;

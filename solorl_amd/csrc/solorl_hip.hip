@@ -1585,8 +1585,8 @@ template <typename T> int build_snapshots_t(solorl_env* h) {
   for (int side = 0; side < (h->cfg.use_treadmill ? 2 : 1); side++) {
     const T tmy = h->cfg.use_treadmill ? (T)(side == 0 ? h->cfg.treadmill_offset : -h->cfg.treadmill_offset) : T(0);
     hipLaunchKernelGGL(init_pose_kernel<T>, dim3(1), dim3(64), 0, 0, tf, ti, h->L, 1, tmy);
-    for (int k = 1; k <= h->cfg.settle_max; k++) {
-      int rc = dispatch_step(h, tf, ti, 1, nullptr, none, MODE_SETTLE, 0);
+    for (int k = 0; k <= h->cfg.settle_max; k++) {      // (k = 0: the reset pose itself is the snapshot when settle_min = 0)
+      int rc = k > 0 ? dispatch_step(h, tf, ti, 1, nullptr, none, MODE_SETTLE, 0) : 0;
       if (rc) return rc;
       if (k >= h->cfg.settle_min)
         hipLaunchKernelGGL(copy_env_kernel<T>, dim3((h->L.NF + 63) / 64), dim3(64), 0, 0, (const T*)tf, (const int*)ti, 1, 0,

@@ -41,7 +41,21 @@ static void run(solorl_env_state* s, const solorl_config* c, int apply_tau) {
   s->contact_mask = mask;
 }
 
+// HARNESS_ONLY_ROBOT and HARNESS_ONLY_FLOAT (0 or 1 each; both or neither): build one of the four instantiations only -- a sanitizer build of all four in
+// one translation unit takes minutes (tests/host/nonfinite_main.cpp builds them side by side); the others then do nothing.
+#if defined(HARNESS_ONLY_ROBOT) != defined(HARNESS_ONLY_FLOAT)
+#error "HARNESS_ONLY_ROBOT and HARNESS_ONLY_FLOAT come as a pair"
+#endif
+#ifdef HARNESS_ONLY_ROBOT
+#define HARNESS_RUN(T, R, F) do { if ((R) == HARNESS_ONLY_ROBOT && (F) == HARNESS_ONLY_FLOAT) run<T, HARNESS_ONLY_ROBOT>(s, c, 1); } while (0)
+#else
+#define HARNESS_RUN(T, R, F) run<T, R>(s, c, 1)
+#endif
 extern "C" void harness_substep(solorl_env_state* s, const solorl_config* c, int use_float) {
-  if (c->robot == SOLORL_ROBOT_SOLO12) { if (use_float) run<float, 1>(s, c, 1); else run<double, 1>(s, c, 1); }
-  else { if (use_float) run<float, 0>(s, c, 1); else run<double, 0>(s, c, 1); }
+#if !defined(HARNESS_ONLY_FLOAT) || HARNESS_ONLY_FLOAT == 1
+  if (use_float) { if (c->robot == SOLORL_ROBOT_SOLO12) HARNESS_RUN(float, 1, 1); else HARNESS_RUN(float, 0, 1); }
+#endif
+#if !defined(HARNESS_ONLY_FLOAT) || HARNESS_ONLY_FLOAT == 0
+  if (!use_float) { if (c->robot == SOLORL_ROBOT_SOLO12) HARNESS_RUN(double, 1, 0); else HARNESS_RUN(double, 0, 0); }
+#endif
 }
