@@ -212,6 +212,7 @@ int solorl_increment_curriculum(solorl_env* env, double value);
  * (2: PGS sweep with the K7 residual exit -- the default, one variant at every batch size; 1 / 0: fixed-iteration sweep,
  * software-pipelined / plain -- chosen by grid size when solver_residual_threshold = 0 unless SOLORL_PGS_PIPE pins it, the last bits
  * of an env then depend on which side of one wavefront per SIMD its batch is), "max_contacts", "max_limit_rows", "f64",
+ * "sort" (1: contact-count sorting, SOLORL_SORT=1 at solorl_create with at least two envs: solorl_step ping-pongs two state buffers),
  * "step_n_one_launch" (1: solorl_step_n / solorl_rollout run K steps in one launch; 0: lane mode or contact-count sorting, where
  * solorl_step_n issues K ordinary steps and solorl_rollout is refused), "helper_wave" (1: solorl_step, solorl_step_act and a
  * one-step solorl_step_n launch two wavefronts per workgroup, the second one running the collision front of every sub-step beside the

@@ -21,6 +21,7 @@
 #pragma once
 #include <utility>
 
+#include "../../include/solorl.h"
 #include "../../include/solorl_model_data.h"
 #include "spatial.hpp"
 
@@ -116,6 +117,19 @@ template <typename T> struct PhysParams {
     mode = (pipe ? M_PIPE : 0) | (urdf ? M_URDF : 0) | (cone_ ? M_CONE : 0) | (treadmill ? M_TREADMILL : 0);
   }
 };
+// solorl_config -> PhysParams (host side): the one field list, for the engine's launches and for the CPU harnesses that run this
+// file's code (tests/host/host_harness.cpp, tools/dev/k7_gate_share.cpp).  M_PIPE is set; team_launch_shape picks it per batch size.
+template <typename T> PhysParams<T> make_phys(const solorl_config& c) {
+  PhysParams<T> p;
+  p.dt = (T)c.sim_dt; p.gravity = (T)c.gravity; p.erp = (T)c.erp; p.slop = (T)c.linear_slop; p.warm = (T)c.warmstart;
+  p.damping = (T)c.damping; p.vmax = (T)c.max_velocity; p.qlim = (T)c.joint_limit; p.inv_dt = (T)(1.0 / c.sim_dt);
+  p.iterations = c.solver_iterations;
+  p.tm_hw = (T)c.treadmill_half_width; p.tm_mu = (T)c.treadmill_friction;
+  p.resid_thr = c.solver_residual_threshold > 0 ? (T)std::sqrt(c.solver_residual_threshold) : T(-1);
+  p.cerp = (T)c.contact_erp; p.cmargin = (T)c.collision_margin;
+  p.set_mode(true, c.use_urdf_inertia != 0, c.friction_model == SOLORL_FRICTION_CONE, c.use_treadmill != 0);
+  return p;
+}
 // bit 24+f of a sub-step's returned mask: foot f's contact lies on the treadmill strip (foot primitive = 13 + 2f)
 SD int strip_feet_bits(int smask) {
   return (((smask >> 13) & 1) << 24) | (((smask >> 15) & 1) << 25) | (((smask >> 17) & 1) << 26) | (((smask >> 19) & 1) << 27);

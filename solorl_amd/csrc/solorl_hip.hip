@@ -205,29 +205,102 @@ SD void sample_goal(Env<T, NQ>& E, const EnvParams& P, long long gid) {   // sol
   E.goal[0] = (r[2] & 1u) ? x : -x; E.goal[1] = (r[3] & 1u) ? y : -y;
 }
 
-// SoloBaseEnv.reset (baseEnv.py:70-82) in O(1): load the pre-simulated post-settle state.
+// ---- the scalar env logic of a control step: one copy, run by lane mode's lane (step_body) and by team mode's leader (step_team)
+template <typename T, int NQ>
+SD void pointgoal_progress(Env<T, NQ>& E, const EnvParams& P, long long gid) {   // solo.py:266-272
+  T dx = E.ps.pos.x - E.goal[0], dy = E.ps.pos.y - E.goal[1];
+  T np = sqrt(dx * dx + dy * dy);
+  E.prog = -(np - E.pot); E.pot = np;
+  if (np < T(0.5)) { E.goals += T(1); sample_goal(E, P, gid); }
+}
+// A7 reward, NaN guard, A8 termination, A1 terminal reward override, every per-env output and the ep_stats accumulators; returns done.
+// asq: sum of the raw action squares; N: envs of the launch (the ep_stats column stride)
+template <typename T, int NQ>
+SD int reward_termination_outputs(Env<T, NQ>& E, const EnvParams& P, T asq, const Outputs& out, idx_t env, int N) {
+  // ---- A7 reward (baseEnv.py:91-157)
+  const T z = E.ps.pos.z;
+  T stand = z > T(0.2) ? T(0.5) : T(0), jp = T(0), balance = T(0), progress = T(0), torque = T(0);
+#pragma unroll
+  for (int j = 0; j < NQ; j++) jp += P.task == SOLORL_TASK_STAND ? fabs(E.ps.q[j]) : E.ps.q[j] * E.ps.q[j];
+  jp = T(-0.1) * jp / T(NQ);
+  if (P.task == SOLORL_TASK_WALK) {
+    if (z > T(0.2)) { T vx = E.ps.v.x; progress = T(2) * (vx > T(0) ? T(1) : (vx < T(0) ? T(-1) : T(0))) * vx * vx; }
+  } else if (P.task == SOLORL_TASK_POINTGOAL) {
+    T r, p, y; euler_zyx(E.ps.qx, E.ps.qy, E.ps.qz, E.ps.qw, r, p, y);
+    balance = T(-0.1) * (fabs(r) + fabs(p));
+    if (z > T(0.2)) progress = E.prog * T(1.0 / P.reward_dt);
+  }
+  if (P.control == SOLORL_CONTROL_TORQUE) torque = T(-0.01) * asq;
+  T reward = stand + jp + balance + progress + torque;
+  E.dr[0] += stand; E.dr[1] += jp; E.dr[2] += torque; E.dr[3] += balance; E.dr[4] += progress;
+
+  // ---- A8 termination (baseEnv.py:162-180) + NaN guard
+  int done = 0, to = 0, su = 0, nanr = 0;
+  {
+    T chk = E.ps.pos.x + E.ps.pos.y + E.ps.pos.z + E.ps.qw + E.ps.v.x + E.ps.v.y + E.ps.v.z + E.ps.w.x + E.ps.w.y + E.ps.w.z;
+#pragma unroll
+    for (int j = 0; j < NQ; j++) chk += E.ps.q[j] + E.ps.qd[j];
+    if (!(fabs(chk) < T(1e30))) { nanr = 1; done = 1; reward = T(0); }
+  }
+  if (!P.disable_termination && !nanr) {
+    if (E.timestep >= P.episode_length) { done = 1; to = 1; su = P.task != SOLORL_TASK_POINTGOAL; }
+    else if (z < T(0.05)) { done = 1; }
+    else if (P.task == SOLORL_TASK_POINTGOAL && E.goals > E.egoals) { E.egoals = E.goals; done = 1; su = 1; }
+  }
+  if (done && !nanr) {   // baseEnv.py:52-60
+    if (su) { if (P.task == SOLORL_TASK_POINTGOAL) reward = T(0.1) * T(P.episode_length - E.timestep); }
+    else if (!to) reward = T(-10);
+  }
+  out.rew[env] = (float)reward;
+  out.done[env] = (unsigned char)done;
+  if (out.timeout) out.timeout[env] = (unsigned char)to;
+  if (out.success) out.success[env] = (unsigned char)su;
+  if (out.nan_reset) out.nan_reset[env] = (unsigned char)nanr;
+  if (out.ep_len) out.ep_len[env] = E.timestep;
+  if (out.ep_rew) out.ep_rew[env] = (float)reward;
+  if (out.goals) out.goals[env] = (float)E.egoals;
+  if (out.dr0) out.dr0[env] = (float)E.dr[0];
+  if (out.dr1) out.dr1[env] = (float)E.dr[1];
+  if (out.dr2) out.dr2[env] = (float)E.dr[2];
+  if (out.dr3) out.dr3[env] = (float)E.dr[3];
+  if (out.dr4) out.dr4[env] = (float)E.dr[4];
+  if (done && out.ep_stats) {      // finished-episode accumulators, one column per env (agents/ppo/train.py:90-100)
+    float* s = out.ep_stats + env;
+    const idx_t NN = (idx_t)N;
+    if (nanr) s[9 * NN] += 1.0f;
+    else {
+      s[0] += 1.0f; s[NN] += (float)reward; s[2 * NN] += (float)E.timestep; s[3 * NN] += (float)su;
+#pragma unroll
+      for (int k = 0; k < 5; k++) s[(4 + k) * NN] += (float)E.dr[k];
+    }
+  }
+  return done;
+}
+// The draws of the auto-reset (agents/ppo/envs.py:39 -> baseEnv.py:70-82) from the env's own Philox counter, in the reference's order:
+// treadmill side (scene.reset inside robot.reset, solo.py:166-168), goal (robot.reset), settle count (env.reset).  Returns the snapshot slot.
+template <typename T, int NQ>
+SD int reset_draws(Env<T, NQ>& E, const EnvParams& P, long long gid) {
+  int side = 0;
+  if (P.use_treadmill) {
+    unsigned rt[4];
+    philox(P.seed_lo, P.seed_hi, (unsigned)gid, (unsigned)((unsigned long long)gid >> 32), (unsigned)E.rng++, 3u, rt);
+    side = (rt[0] & 1u) ? 0 : 1;               // 0: strip centred on +offset, 1: on -offset (second half of the snapshot table)
+  }
+  if (P.task == SOLORL_TASK_POINTGOAL) sample_goal(E, P, gid);
+  unsigned r[4];
+  philox(P.seed_lo, P.seed_hi, (unsigned)gid, (unsigned)((unsigned long long)gid >> 32), (unsigned)E.rng++, 2u, r);
+  return (int)(r[0] % (unsigned)P.nsettle) + side * P.nsettle;
+}
+
+// SoloBaseEnv.reset (baseEnv.py:70-82) in O(1): load the pre-simulated post-settle state of the slot reset_draws picks.
 template <typename T, int ROBOT>
 SD void reset_from_snapshot(Env<T, Robot<ROBOT>::NQ>& E, T* sf, const Layout& L, idx_t N, idx_t e, idx_t env, const T* snf,
                             const int* sni, int M, const EnvParams& P) {
   constexpr int NQ = Robot<ROBOT>::NQ;
-  const long long gid = P.id0 + (long long)env;
-  int rng = E.rng;
-  T g0 = E.goal[0], g1 = E.goal[1];
+  const int k = reset_draws(E, P, P.id0 + (long long)env);
+  const int rng = E.rng;
+  const T g0 = E.goal[0], g1 = E.goal[1];
   Env<T, NQ> S;
-  // order of draws as the reference: treadmill side (scene.reset inside robot.reset, solo.py:166-168), goal (robot.reset),
-  // then the settle count (env.reset)
-  int side = 0;
-  if (P.use_treadmill) {
-    unsigned rt[4];
-    philox(P.seed_lo, P.seed_hi, (unsigned)gid, (unsigned)((unsigned long long)gid >> 32), (unsigned)rng++, 3u, rt);
-    side = (rt[0] & 1u) ? 0 : 1;               // 0: strip centred on +offset, 1: on -offset (second half of the snapshot table)
-  }
-  E.rng = rng;
-  if (P.task == SOLORL_TASK_POINTGOAL) { sample_goal(E, P, gid); g0 = E.goal[0]; g1 = E.goal[1]; }
-  rng = E.rng;
-  unsigned r[4];
-  philox(P.seed_lo, P.seed_hi, (unsigned)gid, (unsigned)((unsigned long long)gid >> 32), (unsigned)rng++, 2u, r);
-  const int k = (int)(r[0] % (unsigned)P.nsettle) + side * P.nsettle;
   load_env(S, snf, sni, L, (idx_t)M, (idx_t)k);
   E = S;
   E.rng = rng; E.timestep = 0;
@@ -274,8 +347,9 @@ SD void write_obs(const Env<T, Robot<ROBOT>::NQ>& E, const T* sf, const Layout& 
 }
 
 // ---------------------------------------------------------------- lane mode (SOLORL_TEAM=0): one env per lane
-// 64 envs per wavefront, the env in registers, rows in LDS.  Kept as an independent second implementation of the same
-// step (GPU test: lane vs team vs sorted storage agree); the default is step_team below.
+// 64 envs per wavefront, the env in registers, rows in LDS.  Kept as an independent second implementation of the step's
+// physics and data movement (substep vs substep_team; GPU test: lane vs team vs sorted storage agree); the scalar env logic
+// above is shared with step_team below, the default, and has the oracle as its independent reference.
 template <typename T, int ROBOT>
 SD void step_body(T* __restrict__ sf, int* __restrict__ si, const T* __restrict__ snf, const int* __restrict__ sni, int M,
                   const Layout& L, int N, const EnvParams& P, const PhysParams<T>& pp, const float* __restrict__ actions,
@@ -336,72 +410,10 @@ SD void step_body(T* __restrict__ sf, int* __restrict__ si, const T* __restrict_
     }
     E.ps = C.ps;
   }
-  if (P.task == SOLORL_TASK_POINTGOAL && mode == MODE_STEP) {
-    T dx = E.ps.pos.x - E.goal[0], dy = E.ps.pos.y - E.goal[1];
-    T np = sqrt(dx * dx + dy * dy);
-    E.prog = -(np - E.pot); E.pot = np;
-    if (np < T(0.5)) { E.goals += T(1); sample_goal(E, P, P.id0 + (long long)env); }
-  }
+  if (P.task == SOLORL_TASK_POINTGOAL && mode == MODE_STEP) pointgoal_progress(E, P, P.id0 + (long long)env);
   if (mode == MODE_SETTLE) { store_env(E, sf, si, L, (idx_t)N, e); return; }
   E.timestep += 1;
-
-  // ---- A7 reward (baseEnv.py:91-157)
-  const T z = E.ps.pos.z;
-  T stand = z > T(0.2) ? T(0.5) : T(0), jp = T(0), balance = T(0), progress = T(0), torque = T(0);
-#pragma unroll
-  for (int j = 0; j < NQ; j++) jp += P.task == SOLORL_TASK_STAND ? fabs(E.ps.q[j]) : E.ps.q[j] * E.ps.q[j];
-  jp = T(-0.1) * jp / T(NQ);
-  if (P.task == SOLORL_TASK_WALK) {
-    if (z > T(0.2)) { T vx = E.ps.v.x; progress = T(2) * (vx > T(0) ? T(1) : (vx < T(0) ? T(-1) : T(0))) * vx * vx; }
-  } else if (P.task == SOLORL_TASK_POINTGOAL) {
-    T r, p, y; euler_zyx(E.ps.qx, E.ps.qy, E.ps.qz, E.ps.qw, r, p, y);
-    balance = T(-0.1) * (fabs(r) + fabs(p));
-    if (z > T(0.2)) progress = E.prog * T(1.0 / P.reward_dt);
-  }
-  if (P.control == SOLORL_CONTROL_TORQUE) torque = T(-0.01) * asq;
-  T reward = stand + jp + balance + progress + torque;
-  E.dr[0] += stand; E.dr[1] += jp; E.dr[2] += torque; E.dr[3] += balance; E.dr[4] += progress;
-
-  // ---- A8 termination (baseEnv.py:162-180) + NaN guard
-  int done = 0, to = 0, su = 0, nanr = 0;
-  {
-    T chk = E.ps.pos.x + E.ps.pos.y + E.ps.pos.z + E.ps.qw + E.ps.v.x + E.ps.v.y + E.ps.v.z + E.ps.w.x + E.ps.w.y + E.ps.w.z;
-#pragma unroll
-    for (int j = 0; j < NQ; j++) chk += E.ps.q[j] + E.ps.qd[j];
-    if (!(fabs(chk) < T(1e30))) { nanr = 1; done = 1; reward = T(0); }
-  }
-  if (!P.disable_termination && !nanr) {
-    if (E.timestep >= P.episode_length) { done = 1; to = 1; su = P.task != SOLORL_TASK_POINTGOAL; }
-    else if (z < T(0.05)) { done = 1; }
-    else if (P.task == SOLORL_TASK_POINTGOAL && E.goals > E.egoals) { E.egoals = E.goals; done = 1; su = 1; }
-  }
-  if (done && !nanr) {   // baseEnv.py:52-60
-    if (su) { if (P.task == SOLORL_TASK_POINTGOAL) reward = T(0.1) * T(P.episode_length - E.timestep); }
-    else if (!to) reward = T(-10);
-  }
-  out.rew[env] = (float)reward;
-  out.done[env] = (unsigned char)done;
-  if (out.timeout) out.timeout[env] = (unsigned char)to;
-  if (out.success) out.success[env] = (unsigned char)su;
-  if (out.nan_reset) out.nan_reset[env] = (unsigned char)nanr;
-  if (out.ep_len) out.ep_len[env] = E.timestep;
-  if (out.ep_rew) out.ep_rew[env] = (float)reward;
-  if (out.goals) out.goals[env] = (float)E.egoals;
-  if (out.dr0) out.dr0[env] = (float)E.dr[0];
-  if (out.dr1) out.dr1[env] = (float)E.dr[1];
-  if (out.dr2) out.dr2[env] = (float)E.dr[2];
-  if (out.dr3) out.dr3[env] = (float)E.dr[3];
-  if (out.dr4) out.dr4[env] = (float)E.dr[4];
-  if (done && out.ep_stats) {      // finished-episode accumulators, one column per env (agents/ppo/train.py:90-100)
-    float* s = out.ep_stats + env;
-    const idx_t NN = (idx_t)N;
-    if (nanr) s[9 * NN] += 1.0f;
-    else {
-      s[0] += 1.0f; s[NN] += (float)reward; s[2 * NN] += (float)E.timestep; s[3 * NN] += (float)su;
-#pragma unroll
-      for (int k = 0; k < 5; k++) s[(4 + k) * NN] += (float)E.dr[k];
-    }
-  }
+  const int done = reward_termination_outputs<T, NQ>(E, P, asq, out, env, N);     // A7, A8, A1, outputs
 
   // ---- auto-reset (agents/ppo/envs.py:39) and observation
   if (done) reset_from_snapshot<T, ROBOT>(E, sf, L, (idx_t)N, e, env, snf, sni, M, P);
@@ -646,7 +658,6 @@ SD void step_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict_
   const bool valid = e < (idx_t)N;
   if (!valid) e = (idx_t)N - 1;           // every lane stays alive for the wave-level exchanges
   const bool lead = valid && t == 0;
-  const idx_t NN = (idx_t)N;
   LDS lds; lds.lanes = 4; lds.lane = col;
   // test hook (SOLORL_POISON_LDS=<word>, read at create): pre-fill the whole dynamic LDS.  Two runs with different fill words
   // (NaN vs 0) must agree bitwise -- anything read before it is written in the launch breaks that
@@ -746,84 +757,11 @@ SD void step_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict_
     Env<T, NQ> E;
     env_from_lds<T, ROBOT>(E, C);
     int done = 0;
-    if (P.task == SOLORL_TASK_POINTGOAL && mode == MODE_STEP) {     // solo.py:266-272
-      T dx = E.ps.pos.x - E.goal[0], dy = E.ps.pos.y - E.goal[1];
-      T np = sqrt(dx * dx + dy * dy);
-      E.prog = -(np - E.pot); E.pot = np;
-      if (np < T(0.5)) { E.goals += T(1); sample_goal(E, P, P.id0 + (long long)env); }
-    }
+    if (P.task == SOLORL_TASK_POINTGOAL && mode == MODE_STEP) pointgoal_progress(E, P, P.id0 + (long long)env);
     if (mode == MODE_STEP) {
       E.timestep += 1;
-      // ---- A7 reward (baseEnv.py:91-157)
-      const T z = E.ps.pos.z;
-      T stand = z > T(0.2) ? T(0.5) : T(0), jp = T(0), balance = T(0), progress = T(0), torque = T(0);
-#pragma unroll
-      for (int j = 0; j < NQ; j++) jp += P.task == SOLORL_TASK_STAND ? fabs(E.ps.q[j]) : E.ps.q[j] * E.ps.q[j];
-      jp = T(-0.1) * jp / T(NQ);
-      if (P.task == SOLORL_TASK_WALK) {
-        if (z > T(0.2)) { T vx = E.ps.v.x; progress = T(2) * (vx > T(0) ? T(1) : (vx < T(0) ? T(-1) : T(0))) * vx * vx; }
-      } else if (P.task == SOLORL_TASK_POINTGOAL) {
-        T r, p, y; euler_zyx(E.ps.qx, E.ps.qy, E.ps.qz, E.ps.qw, r, p, y);
-        balance = T(-0.1) * (fabs(r) + fabs(p));
-        if (z > T(0.2)) progress = E.prog * T(1.0 / P.reward_dt);
-      }
-      if (P.control == SOLORL_CONTROL_TORQUE) torque = T(-0.01) * asq;
-      T reward = stand + jp + balance + progress + torque;
-      E.dr[0] += stand; E.dr[1] += jp; E.dr[2] += torque; E.dr[3] += balance; E.dr[4] += progress;
-      // ---- A8 termination (baseEnv.py:162-180) + NaN guard
-      int to = 0, su = 0, nanr = 0;
-      {
-        T chk = E.ps.pos.x + E.ps.pos.y + E.ps.pos.z + E.ps.qw + E.ps.v.x + E.ps.v.y + E.ps.v.z + E.ps.w.x + E.ps.w.y + E.ps.w.z;
-#pragma unroll
-        for (int j = 0; j < NQ; j++) chk += E.ps.q[j] + E.ps.qd[j];
-        if (!(fabs(chk) < T(1e30))) { nanr = 1; done = 1; reward = T(0); }
-      }
-      if (!P.disable_termination && !nanr) {
-        if (E.timestep >= P.episode_length) { done = 1; to = 1; su = P.task != SOLORL_TASK_POINTGOAL; }
-        else if (z < T(0.05)) { done = 1; }
-        else if (P.task == SOLORL_TASK_POINTGOAL && E.goals > E.egoals) { E.egoals = E.goals; done = 1; su = 1; }
-      }
-      if (done && !nanr) {   // baseEnv.py:52-60
-        if (su) { if (P.task == SOLORL_TASK_POINTGOAL) reward = T(0.1) * T(P.episode_length - E.timestep); }
-        else if (!to) reward = T(-10);
-      }
-      out.rew[env] = (float)reward;
-      out.done[env] = (unsigned char)done;
-      if (out.timeout) out.timeout[env] = (unsigned char)to;
-      if (out.success) out.success[env] = (unsigned char)su;
-      if (out.nan_reset) out.nan_reset[env] = (unsigned char)nanr;
-      if (out.ep_len) out.ep_len[env] = E.timestep;
-      if (out.ep_rew) out.ep_rew[env] = (float)reward;
-      if (out.goals) out.goals[env] = (float)E.egoals;
-      if (out.dr0) out.dr0[env] = (float)E.dr[0];
-      if (out.dr1) out.dr1[env] = (float)E.dr[1];
-      if (out.dr2) out.dr2[env] = (float)E.dr[2];
-      if (out.dr3) out.dr3[env] = (float)E.dr[3];
-      if (out.dr4) out.dr4[env] = (float)E.dr[4];
-      if (done && out.ep_stats) {      // finished-episode accumulators, one column per env (agents/ppo/train.py:90-100)
-        float* s = out.ep_stats + env;
-        if (nanr) s[9 * NN] += 1.0f;
-        else {
-          s[0] += 1.0f; s[NN] += (float)reward; s[2 * NN] += (float)E.timestep; s[3 * NN] += (float)su;
-#pragma unroll
-          for (int k = 0; k < 5; k++) s[(4 + k) * NN] += (float)E.dr[k];
-        }
-      }
-      // ---- auto-reset (agents/ppo/envs.py:39 -> baseEnv.py:70-82), part 1: the draws, in the reference's order -- treadmill
-      // side (scene.reset inside robot.reset, solo.py:166-168), goal (robot.reset), settle count (env.reset)
-      if (done) {
-        const long long gid = P.id0 + (long long)env;
-        int side = 0;
-        if (P.use_treadmill) {
-          unsigned rt[4];
-          philox(P.seed_lo, P.seed_hi, (unsigned)gid, (unsigned)((unsigned long long)gid >> 32), (unsigned)E.rng++, 3u, rt);
-          side = (rt[0] & 1u) ? 0 : 1;               // 0: strip centred on +offset, 1: on -offset (second half of the snapshot table)
-        }
-        if (P.task == SOLORL_TASK_POINTGOAL) sample_goal(E, P, gid);
-        unsigned r[4];
-        philox(P.seed_lo, P.seed_hi, (unsigned)gid, (unsigned)((unsigned long long)gid >> 32), (unsigned)E.rng++, 2u, r);
-        C.irec[IR_SNAP] = (int)(r[0] % (unsigned)P.nsettle) + side * P.nsettle;
-      }
+      done = reward_termination_outputs<T, NQ>(E, P, asq, out, env, N);     // A7, A8, A1, outputs
+      if (done) C.irec[IR_SNAP] = reset_draws(E, P, P.id0 + (long long)env);     // auto-reset, part 1: the draws
     }
     scalars_to_lds<T, ROBOT>(E, C);          // (a reset keeps the goal and the rng counter from here)
     C.irec[IR_DONE] = done;
@@ -1027,10 +965,14 @@ rollout_kernel_team(const RolloutArgs<T> args) {
   }
 }
 
-template <typename T, int ROBOT>
-__global__ void reset_kernel(T* sf, int* si, const T* snf, const int* sni, int M, Layout L, int N, EnvParams P, float* obs) {
+// solorl_reset (MASKED = false; mask is null and not read) and solorl_reset_masked (the envs whose mask byte is set; same draws from
+// the env's own Philox counter)
+template <typename T, int ROBOT, bool MASKED>
+__global__ void reset_kernel(T* sf, int* si, const T* snf, const int* sni, int M, Layout L, int N, EnvParams P, float* obs,
+                             const unsigned char* mask) {
   const idx_t e = (idx_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= (idx_t)N) return;
+  if constexpr (MASKED) { if (!mask[si[SX(I_ENVID, e, NI)]]) return; }      // (in front of the state's loads)
   Env<T, Robot<ROBOT>::NQ> E;
   load_env(E, sf, si, L, (idx_t)N, e);
   const idx_t env = (idx_t)si[SX(I_ENVID, e, NI)];
@@ -1214,24 +1156,6 @@ __global__ void __launch_bounds__(256) set_states_kernel(T* __restrict__ sf, int
 }
 static_assert(offsetof(solorl_env_state, pos) == 0, "set_states_kernel derives xyprev from a row's words 0 and 1");
 
-// solorl_reset_masked: reset_kernel for the envs whose mask byte is set (same draws from the env's own Philox counter).  A copy of
-// reset_kernel with the mask test in front rather than a nullable argument to it, on purpose: reset_kernel and solorl_reset stay the
-// code they were, instruction for instruction.
-template <typename T, int ROBOT>
-__global__ void reset_masked_kernel(T* sf, int* si, const T* snf, const int* sni, int M, Layout L, int N, EnvParams P,
-                                    const unsigned char* mask, float* obs) {
-  const idx_t e = (idx_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= (idx_t)N) return;
-  const idx_t env = (idx_t)si[SX(I_ENVID, e, NI)];
-  if (!mask[env]) return;
-  Env<T, Robot<ROBOT>::NQ> E;
-  load_env(E, sf, si, L, (idx_t)N, e);
-  reset_from_snapshot<T, ROBOT>(E, sf, L, (idx_t)N, e, env, snf, sni, M, P);
-  if (obs) write_obs<T, ROBOT>(E, sf, L, (idx_t)N, e, env, P.task, obs);
-  store_env(E, sf, si, L, (idx_t)N, e);
-  si[SX(I_NEEDRESET, e, NI)] = 0;
-}
-
 // ---- fused GAE / discounted returns (agents/ppo/storage.py:35-55): one thread per env walks the rollout
 // backwards; every access is coalesced across envs.  HBM-bound: 16 B per (t, env) sample.
 __global__ void returns_kernel(const float* __restrict__ rew, float* __restrict__ val, const float* __restrict__ msk,
@@ -1350,7 +1274,8 @@ struct solorl_env {
   uint64_t seed = 0; int64_t id0 = 0;
   double goal_radius = 2.0;
   double* dyn = nullptr;   // device copy of the mutable parameters (EnvParams::dyn)
-  unsigned* stab = nullptr;   // device copy of the row-word / field-group table of get_states_kernel / set_states_kernel (build_state_table)
+  std::vector<unsigned> stab_host;   // row-word / field-group table of a solorl_env_state row (build_state_table): solorl_get_state / solorl_set_state
+  unsigned* stab = nullptr;          // its device copy: get_states_kernel / set_states_kernel
   int epw = 64;   // envs per wavefront (lanes per workgroup)
   bool spread = true;
   bool team = false;   // 16 lanes per env (set at create: default true)
@@ -1374,17 +1299,6 @@ EnvParams make_env_params(const solorl_env* h) {
   P.use_treadmill = c.use_treadmill; P.tm_offset = (float)c.treadmill_offset;
   P.linear_ids = h->sort ? 0 : 1;
   return P;
-}
-template <typename T> PhysParams<T> make_phys(const solorl_config& c) {
-  PhysParams<T> p;
-  p.dt = (T)c.sim_dt; p.gravity = (T)c.gravity; p.erp = (T)c.erp; p.slop = (T)c.linear_slop; p.warm = (T)c.warmstart;
-  p.damping = (T)c.damping; p.vmax = (T)c.max_velocity; p.qlim = (T)c.joint_limit; p.inv_dt = (T)(1.0 / c.sim_dt);
-  p.iterations = c.solver_iterations;
-  p.tm_hw = (T)c.treadmill_half_width; p.tm_mu = (T)c.treadmill_friction;
-  p.resid_thr = c.solver_residual_threshold > 0 ? (T)sqrt(c.solver_residual_threshold) : T(-1);
-  p.cerp = (T)c.contact_erp; p.cmargin = (T)c.collision_margin;
-  p.set_mode(true, c.use_urdf_inertia != 0, c.friction_model == SOLORL_FRICTION_CONE, c.use_treadmill != 0);
-  return p;
 }
 
 // The phase functions address the dynamic LDS from the constant SOLO_LDS_BASE (dynamics.hpp): true exactly while a step kernel's
@@ -1531,6 +1445,15 @@ SOLO_DEFINE_PART(3, double, 1)
 #if SOLO_TU_PART == -1 || SOLO_TU_PART == 4        // ---- the C ABI and everything that is not a step kernel
 namespace {
 
+// The handle's instantiation as tag values: f(T{}) with T = float or double, f(T{}, robot) with decltype(robot)::value = 0 (Solo8) or 1
+// (Solo12) -- for everything but the step kernels, whose instantiations live in the other parts (dispatch_step, dispatch_rollout)
+template <typename F> auto with_type(const solorl_env* h, F&& f) { return h->f64 ? f(double{}) : f(float{}); }
+template <typename F> auto with_instantiation(const solorl_env* h, F&& f) {
+  return with_type(h, [&](auto t) {
+    return h->cfg.robot == SOLORL_ROBOT_SOLO12 ? f(t, std::integral_constant<int, 1>{}) : f(t, std::integral_constant<int, 0>{});
+  });
+}
+
 int dispatch_step(solorl_env* h, void* sf, int* si, int N, const float* actions, const Outputs& out, int mode, hipStream_t st) {
   const bool s12 = h->cfg.robot == SOLORL_ROBOT_SOLO12;
   if (!h->f64) return s12 ? solorl_launch_part1(h, sf, si, N, actions, &out, mode, st) : solorl_launch_part0(h, sf, si, N, actions, &out, mode, st);
@@ -1571,6 +1494,24 @@ int check_policy_tail(const solorl_env* h, const solorl_policy_params* p, const 
   for (const void* q : ptrs) if (!q) return fail(SOLORL_ERR_INVALID, w + ": null policy parameter pointer");
   const void* vec[] = {p->critic_w0, p->critic_w1, p->critic_w2, p->actor_w0, p->actor_w1, p->mean_w};
   for (const void* q : vec) if (reinterpret_cast<uintptr_t>(q) & 15u) return fail(SOLORL_ERR_INVALID, w + ": weight matrices must be 16-byte aligned (rows are read as float4)");
+  return 0;
+}
+
+PolicyTail make_policy_tail(const solorl_policy_params* p, const float* noise, float* value, float* action, float* logp) {
+  return PolicyTail{p->critic_w0, p->critic_b0, p->critic_w1, p->critic_b1, p->critic_w2, p->critic_b2, p->actor_w0, p->actor_b0, p->actor_w1, p->actor_b1,
+                    p->mean_w, p->mean_b, p->logstd, noise, value, action, logp};
+}
+
+// solorl_reset / solorl_reset_masked
+template <bool MASKED> int launch_reset(solorl_env* h, const uint8_t* mask, float* obs_out, void* stream) {
+  HIP_TRY(hipSetDevice(h->device));
+  const EnvParams P = make_env_params(h);
+  with_instantiation(h, [&](auto t, auto robot) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((reset_kernel<T, decltype(robot)::value, MASKED>), dim3((h->N + 255) / 256), dim3(256), 0, (hipStream_t)stream, (T*)h->sf, h->si,
+                       (const T*)h->snf, (const int*)h->sni, h->M, h->L, h->N, P, obs_out, mask);
+  });
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
@@ -1770,7 +1711,7 @@ int solorl_create(const solorl_config* cfg, int num_envs, int device_id, uint64_
   }
   {
     if (h->L.NF > ST_MAXNF) return cleanup(fail(SOLORL_ERR_INVALID, "state layout wider than the batched state kernels' staging block"));
-    std::vector<unsigned> tab;
+    std::vector<unsigned>& tab = h->stab_host;
     build_state_table(h->L, h->n, tab);
     if (hipMalloc(&h->stab, sizeof(unsigned) * tab.size()) != hipSuccess) return cleanup(fail(SOLORL_ERR_HIP, "hipMalloc state table"));
     if (hipMemcpy(h->stab, tab.data(), sizeof(unsigned) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) return cleanup(fail(SOLORL_ERR_HIP, "hipMemcpy state table"));
@@ -1786,10 +1727,11 @@ int solorl_create(const solorl_config* cfg, int num_envs, int device_id, uint64_
     if (hipMalloc(&h->si2, sizeof(int) * NI * Np) != hipSuccess) return cleanup(fail(SOLORL_ERR_HIP, "hipMalloc istate2"));
     if (hipMalloc(&h->perm, sizeof(int) * (size_t)num_envs) != hipSuccess) return cleanup(fail(SOLORL_ERR_HIP, "hipMalloc perm"));
   }
-  dim3 g((num_envs + 255) / 256), b(256);
-  if (h->f64) hipLaunchKernelGGL(init_pose_kernel<double>, g, b, 0, 0, (double*)h->sf, h->si, h->L, num_envs, 0.0);
-  else hipLaunchKernelGGL(init_pose_kernel<float>, g, b, 0, 0, (float*)h->sf, h->si, h->L, num_envs, 0.0f);
-  rc = h->f64 ? build_snapshots_t<double>(h) : build_snapshots_t<float>(h);
+  rc = with_type(h, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(init_pose_kernel<T>, dim3((num_envs + 255) / 256), dim3(256), 0, 0, (T*)h->sf, h->si, h->L, num_envs, T(0));
+    return build_snapshots_t<T>(h);
+  });
   if (rc) return cleanup(rc);
   if (hipDeviceSynchronize() != hipSuccess) return cleanup(fail(SOLORL_ERR_HIP, "device sync after create"));
   *out = h;
@@ -1834,6 +1776,7 @@ int solorl_get_property(const solorl_env* h, const char* name, double* value) {
   } else if (n == "max_contacts") *value = MAX_CONTACTS;
   else if (n == "max_limit_rows") *value = MAX_LIMITS;
   else if (n == "f64") *value = h->f64 ? 1 : 0;
+  else if (n == "sort") *value = h->sort ? 1 : 0;
   else if (n == "step_n_one_launch") *value = step_n_one_launch(h) ? 1 : 0;
   else if (n == "helper_wave") *value = helper_wave_rule(h) ? 1 : 0;
   else return fail(SOLORL_ERR_INVALID, "unknown property: " + n);
@@ -1842,19 +1785,7 @@ int solorl_get_property(const solorl_env* h, const char* name, double* value) {
 
 int solorl_reset(solorl_env* h, float* obs_out, void* stream) {
   if (!h) return fail(SOLORL_ERR_INVALID, "null handle");
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  EnvParams P = make_env_params(h);
-  dim3 g((h->N + 255) / 256), b(256);
-  const bool s12 = h->cfg.robot == SOLORL_ROBOT_SOLO12;
-  if (h->f64) {
-    if (s12) hipLaunchKernelGGL((reset_kernel<double, 1>), g, b, 0, st, (double*)h->sf, h->si, (const double*)h->snf, (const int*)h->sni, h->M, h->L, h->N, P, obs_out);
-    else hipLaunchKernelGGL((reset_kernel<double, 0>), g, b, 0, st, (double*)h->sf, h->si, (const double*)h->snf, (const int*)h->sni, h->M, h->L, h->N, P, obs_out);
-  } else {
-    if (s12) hipLaunchKernelGGL((reset_kernel<float, 1>), g, b, 0, st, (float*)h->sf, h->si, (const float*)h->snf, (const int*)h->sni, h->M, h->L, h->N, P, obs_out);
-    else hipLaunchKernelGGL((reset_kernel<float, 0>), g, b, 0, st, (float*)h->sf, h->si, (const float*)h->snf, (const int*)h->sni, h->M, h->L, h->N, P, obs_out);
-  }
-  HIP_TRY(hipGetLastError());
+  if (int rc = launch_reset<false>(h, nullptr, obs_out, stream)) return rc;
   h->reset_called = true;
   return 0;
 }
@@ -1869,9 +1800,11 @@ int solorl_step(solorl_env* h, const float* actions, float* obs_out, float* rewa
   if (h->sort) {   // re-sort the state by last contact count (stable), into the spare buffer
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(sort_perm_kernel, dim3(1), dim3(256), 0, st, (const int*)h->si, h->N, h->perm);
-    dim3 g((h->N + 255) / 256, h->L.NF + NI), b(256);
-    if (h->f64) hipLaunchKernelGGL(gather_state_kernel<double>, g, b, 0, st, (const double*)h->sf, (const int*)h->si, (const int*)h->perm, h->N, h->L.NF, (double*)h->sf2, h->si2);
-    else hipLaunchKernelGGL(gather_state_kernel<float>, g, b, 0, st, (const float*)h->sf, (const int*)h->si, (const int*)h->perm, h->N, h->L.NF, (float*)h->sf2, h->si2);
+    with_type(h, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(gather_state_kernel<T>, dim3((h->N + 255) / 256, h->L.NF + NI), dim3(256), 0, st, (const T*)h->sf, (const int*)h->si,
+                         (const int*)h->perm, h->N, h->L.NF, (T*)h->sf2, h->si2);
+    });
     HIP_TRY(hipGetLastError());
     std::swap(h->sf, h->sf2); std::swap(h->si, h->si2);
   }
@@ -1887,8 +1820,7 @@ int solorl_step_act(solorl_env* h, const float* actions, float* obs_out, float* 
   if (!actions || !obs_out || !reward_out || !done_out) return fail(SOLORL_ERR_INVALID, "null array argument");
   HIP_TRY(hipSetDevice(h->device));
   Outputs o = make_outputs(obs_out, reward_out, done_out, info);
-  o.pol = PolicyTail{p->critic_w0, p->critic_b0, p->critic_w1, p->critic_b1, p->critic_w2, p->critic_b2, p->actor_w0, p->actor_b0, p->actor_w1, p->actor_b1,
-                     p->mean_w, p->mean_b, p->logstd, noise, value_out, action_out, logp_out};
+  o.pol = make_policy_tail(p, noise, value_out, action_out, logp_out);
   return dispatch_step(h, h->sf, h->si, h->N, actions, o, MODE_STEP, (hipStream_t)stream);
 }
 
@@ -1936,8 +1868,7 @@ int solorl_rollout(solorl_env* h, int K, float* actions, float* obs_out, float* 
   if (!actions || !obs_out || !reward_out || !done_out) return fail(SOLORL_ERR_INVALID, "null array argument");
   HIP_TRY(hipSetDevice(h->device));
   Outputs o = make_outputs(obs_out, reward_out, done_out, info);
-  o.pol = PolicyTail{p->critic_w0, p->critic_b0, p->critic_w1, p->critic_b1, p->critic_w2, p->critic_b2, p->actor_w0, p->actor_b0, p->actor_w1, p->actor_b1,
-                     p->mean_w, p->mean_b, p->logstd, noise, value_out, actions, logp_out};
+  o.pol = make_policy_tail(p, noise, value_out, actions, logp_out);
   if (K == 1) {              // = solorl_step_act (policy after the step) or solorl_step, as in solorl_step_n
     if (policy_after_last) { o.pol.value = value_out + h->N; o.pol.logp = logp_out + h->N; o.pol.action = actions + (size_t)h->N * h->n; if (noise) o.pol.noise = noise + (size_t)h->N * h->n; }
     else o.pol = PolicyTail{};
@@ -1949,16 +1880,11 @@ int solorl_rollout(solorl_env* h, int K, float* actions, float* obs_out, float* 
 int solorl_get_observation(solorl_env* h, float* obs_out, void* stream) {
   if (!h || !obs_out) return fail(SOLORL_ERR_INVALID, "null argument");
   HIP_TRY(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  dim3 g((h->N + 255) / 256), b(256);
-  const bool s12 = h->cfg.robot == SOLORL_ROBOT_SOLO12;
-  if (h->f64) {
-    if (s12) hipLaunchKernelGGL((obs_kernel<double, 1>), g, b, 0, st, (const double*)h->sf, (const int*)h->si, h->L, h->N, h->cfg.task, obs_out);
-    else hipLaunchKernelGGL((obs_kernel<double, 0>), g, b, 0, st, (const double*)h->sf, (const int*)h->si, h->L, h->N, h->cfg.task, obs_out);
-  } else {
-    if (s12) hipLaunchKernelGGL((obs_kernel<float, 1>), g, b, 0, st, (const float*)h->sf, (const int*)h->si, h->L, h->N, h->cfg.task, obs_out);
-    else hipLaunchKernelGGL((obs_kernel<float, 0>), g, b, 0, st, (const float*)h->sf, (const int*)h->si, h->L, h->N, h->cfg.task, obs_out);
-  }
+  with_instantiation(h, [&](auto t, auto robot) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((obs_kernel<T, decltype(robot)::value>), dim3((h->N + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const T*)h->sf,
+                       (const int*)h->si, h->L, h->N, h->cfg.task, obs_out);
+  });
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -2003,18 +1929,11 @@ int solorl_get_state(solorl_env* h, int i, solorl_env_state* out) {
     for (int k = 0; k < h->L.NF; k++) f[k] = ff[k];
   }
   HIP_TRY(hipMemcpy2D(iv, sizeof(int), (const char*)h->si + sizeof(int) * slot0i, sizeof(int) * 4, sizeof(int), NI, hipMemcpyDeviceToHost));
-  const Layout& L = h->L;
-  memset(out, 0, sizeof *out);
-  for (int k = 0; k < 3; k++) { out->pos[k] = f[L.pos + k]; out->lin_vel[k] = f[L.v + k]; out->ang_vel[k] = f[L.w + k]; }
-  for (int k = 0; k < 4; k++) out->quat[k] = f[L.quat + k];
-  for (int j = 0; j < h->n; j++) { out->q[j] = f[L.q + j]; out->qd[j] = f[L.qd + j]; }
-  for (int p = 0; p < NPRIM; p++) out->lambda_prev[p] = f[L.lam + p];
-  for (int hh = 0; hh < SOLORL_STATE_MAX_HISTORY; hh++)
-    for (int d = 0; d < DMAX; d++) out->hist[hh][d] = hh < (L.H > 2 ? L.H : 2) ? f[L.hist + hh * HSTRIDE + d] : 0.0;
-  out->goal[0] = f[L.goal]; out->goal[1] = f[L.goal + 1]; out->potential = f[L.pot]; out->progress = f[L.prog];
-  out->goals_reached = f[L.goals]; out->env_goals_reached = f[L.egoals];
-  for (int k = 0; k < 5; k++) out->dr[k] = f[L.dr + k];
-  out->treadmill_y = f[L.tmy];
+  memset(out, 0, sizeof *out);            // (words no field maps to read 0: tau, joints / history levels the handle does not have)
+  for (int w = 0; w < ST_WORDS; w++) {    // the row's double members, by the table of the batched kernels
+    const unsigned code = h->stab_host[w] & 0xFFFFu;
+    if (code < ST_INT_B) memcpy(reinterpret_cast<char*>(out) + 8 * w, &f[code], 8);
+  }
   out->timestep = iv[I_TIMESTEP]; out->contact_mask = iv[I_MASK]; out->rng_counter = iv[I_RNG]; out->need_reset = iv[I_NEEDRESET];
   return 0;
 }
@@ -2027,16 +1946,12 @@ int solorl_set_state(solorl_env* h, int i, const solorl_env_state* in) {
   { int rc_ = find_slot(h, i, &i); if (rc_) return rc_; }
   const Layout& L = h->L;
   const size_t slot0f = (size_t)(i >> 2) * ((size_t)L.NF << 2) + (size_t)(i & 3), slot0i = (size_t)(i >> 2) * ((size_t)NI << 2) + (size_t)(i & 3);
-  std::vector<double> f(L.NF, 0.0);
-  for (int k = 0; k < 3; k++) { f[L.pos + k] = in->pos[k]; f[L.v + k] = in->lin_vel[k]; f[L.w + k] = in->ang_vel[k]; }
-  for (int k = 0; k < 4; k++) f[L.quat + k] = in->quat[k];
-  for (int j = 0; j < h->n; j++) { f[L.q + j] = in->q[j]; f[L.qd + j] = in->qd[j]; }
-  for (int p = 0; p < NPRIM; p++) f[L.lam + p] = in->lambda_prev[p];
-  for (int hh = 0; hh < (L.H > 2 ? L.H : 2); hh++) for (int d = 0; d < DMAX; d++) f[L.hist + hh * HSTRIDE + d] = in->hist[hh][d];
-  f[L.goal] = in->goal[0]; f[L.goal + 1] = in->goal[1]; f[L.pot] = in->potential; f[L.prog] = in->progress;
-  f[L.goals] = in->goals_reached; f[L.egoals] = in->env_goals_reached;
-  for (int k = 0; k < 5; k++) f[L.dr + k] = in->dr[k];
-  f[L.xyprev] = in->pos[0]; f[L.xyprev + 1] = in->pos[1]; f[L.tmy] = in->treadmill_y;
+  std::vector<double> f(L.NF, 0.0);       // (fields no row word maps to are written as 0: pads, joints / history levels the handle does not have)
+  for (int w = 0; w < ST_WORDS; w++) {    // the row's double members, by the table of the batched kernels
+    const unsigned code = h->stab_host[w] & 0xFFFFu;
+    if (code < ST_INT_B) memcpy(&f[code], reinterpret_cast<const char*>(in) + 8 * w, 8);
+  }
+  f[L.xyprev] = in->pos[0]; f[L.xyprev + 1] = in->pos[1];
   int iv[NI]; iv[I_TIMESTEP] = in->timestep; iv[I_MASK] = in->contact_mask; iv[I_RNG] = in->rng_counter; iv[I_NEEDRESET] = in->need_reset;
   iv[I_ENVID] = env_id;
   if (h->f64) {
@@ -2060,10 +1975,11 @@ int solorl_get_states(solorl_env* h, const uint8_t* mask, solorl_env_state* out,
   if (!out) return fail(SOLORL_ERR_INVALID, "solorl_get_states: null out array");
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
-  if (h->f64) hipLaunchKernelGGL(get_states_kernel<double>, state_grid(h), dim3(256), 0, st, (const double*)h->sf, (const int*)h->si, h->L.NF, h->N, h->sort ? 0 : 1,
-                                 (const unsigned*)h->stab, mask, (unsigned long long*)out);
-  else hipLaunchKernelGGL(get_states_kernel<float>, state_grid(h), dim3(256), 0, st, (const float*)h->sf, (const int*)h->si, h->L.NF, h->N, h->sort ? 0 : 1,
-                          (const unsigned*)h->stab, mask, (unsigned long long*)out);
+  with_type(h, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(get_states_kernel<T>, state_grid(h), dim3(256), 0, st, (const T*)h->sf, (const int*)h->si, h->L.NF, h->N, h->sort ? 0 : 1,
+                       (const unsigned*)h->stab, mask, (unsigned long long*)out);
+  });
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -2077,10 +1993,11 @@ int solorl_set_states(solorl_env* h, const uint8_t* mask, const solorl_env_state
     return fail(SOLORL_ERR_STATE, "solorl_set_states: a partial write (a mask, or fewer than all field groups) needs a handle that has been reset");
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
-  if (h->f64) hipLaunchKernelGGL(set_states_kernel<double>, state_grid(h), dim3(256), 0, st, (double*)h->sf, h->si, h->L.NF, h->N, h->sort ? 0 : 1,
-                                 (const unsigned*)h->stab, mask, (const unsigned long long*)in, (unsigned)fields, h->L.xyprev);
-  else hipLaunchKernelGGL(set_states_kernel<float>, state_grid(h), dim3(256), 0, st, (float*)h->sf, h->si, h->L.NF, h->N, h->sort ? 0 : 1,
-                          (const unsigned*)h->stab, mask, (const unsigned long long*)in, (unsigned)fields, h->L.xyprev);
+  with_type(h, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(set_states_kernel<T>, state_grid(h), dim3(256), 0, st, (T*)h->sf, h->si, h->L.NF, h->N, h->sort ? 0 : 1,
+                       (const unsigned*)h->stab, mask, (const unsigned long long*)in, (unsigned)fields, h->L.xyprev);
+  });
   HIP_TRY(hipGetLastError());
   if (whole) h->reset_called = true;      // every env now holds a caller-given state (the rows' own need_reset values are the caller's business)
   return 0;
@@ -2090,20 +2007,7 @@ int solorl_reset_masked(solorl_env* h, const uint8_t* mask, float* obs_out, void
   if (!h) return fail(SOLORL_ERR_INVALID, "solorl_reset_masked: null handle");
   if (!mask) return fail(SOLORL_ERR_INVALID, "solorl_reset_masked: null mask");
   if (!h->reset_called) return fail(SOLORL_ERR_STATE, "solorl_reset_masked: needs a handle that has been reset");
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  EnvParams P = make_env_params(h);
-  dim3 g((h->N + 255) / 256), b(256);
-  const bool s12 = h->cfg.robot == SOLORL_ROBOT_SOLO12;
-  if (h->f64) {
-    if (s12) hipLaunchKernelGGL((reset_masked_kernel<double, 1>), g, b, 0, st, (double*)h->sf, h->si, (const double*)h->snf, (const int*)h->sni, h->M, h->L, h->N, P, mask, obs_out);
-    else hipLaunchKernelGGL((reset_masked_kernel<double, 0>), g, b, 0, st, (double*)h->sf, h->si, (const double*)h->snf, (const int*)h->sni, h->M, h->L, h->N, P, mask, obs_out);
-  } else {
-    if (s12) hipLaunchKernelGGL((reset_masked_kernel<float, 1>), g, b, 0, st, (float*)h->sf, h->si, (const float*)h->snf, (const int*)h->sni, h->M, h->L, h->N, P, mask, obs_out);
-    else hipLaunchKernelGGL((reset_masked_kernel<float, 0>), g, b, 0, st, (float*)h->sf, h->si, (const float*)h->snf, (const int*)h->sni, h->M, h->L, h->N, P, mask, obs_out);
-  }
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return launch_reset<true>(h, mask, obs_out, stream);
 }
 
 }  // extern "C"

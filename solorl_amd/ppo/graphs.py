@@ -158,9 +158,9 @@ class GraphedRollout:
 
     def _capturable(self):
         # contact-count sorting (opt-in, SOLORL_SORT=1) ping-pongs two state buffers on the host side of
-        # solorl_step: a captured sequence is only self-consistent over an even number of steps
-        import os
-        sort = os.environ.get("SOLORL_SORT", "0") != "0"
+        # solorl_step: a captured sequence is only self-consistent over an even number of steps.  Asked of the handle (the engine
+        # latches the switch at solorl_create); an env without the engine's properties does not sort
+        sort = hasattr(self.envs, "get_property") and self.envs.get_property("sort") != 0
         return not sort or self.T % 2 == 0
 
     def __call__(self):

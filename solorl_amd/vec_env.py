@@ -191,11 +191,11 @@ class SoloVecEnv:
         return o, r, d, self._info
 
     def step_act_supported(self, params):
-        """solorl_step_act (include/solorl.h): the engine's defaults (fp32, team mode, no sorting) and an observation size that is a
+        """The policy tail's prerequisites (solorl_step_act, solorl_rollout; include/solorl.h), decided from the handle -- what the engine
+        latched at solorl_create, whatever the environment says now: fp32, team mode, no sorting, and an observation size that is a
         multiple of 4 floats and at most 88 (zero or one history level) with the reference's hidden-64 MLP on it."""
-        import os
-        return (self.cfg.precision == 0 and os.environ.get("SOLORL_TEAM", "1") != "0" and os.environ.get("SOLORL_SORT", "0") == "0"
-                and self.obs_dim % 4 == 0 and self.obs_dim <= 88 and params.obs_dim == self.obs_dim and params.act_dim == self.act_dim and params.hidden == 64)
+        return (self.get_property("step_n_one_launch") == 1 and self.get_property("f64") == 0 and self.obs_dim % 4 == 0 and self.obs_dim <= 88
+                and params.obs_dim == self.obs_dim and params.act_dim == self.act_dim and params.hidden == 64)
 
     def step_act_inplace(self, actions, params, noise, value_out, action_out, logp_out, obs_out=None, rew_out=None, done_out=None):
         """step_inplace + Policy.act on the new observations in ONE launch (solorl_step_act): value_out [N] or [N,1], action_out [N,A] =
@@ -276,10 +276,8 @@ class SoloVecEnv:
         return o, r, d, b["info"]
 
     def rollout_supported(self, params):
-        """solorl_rollout (include/solorl.h) on this handle: K steps in one launch (team mode, no sorting: as the handle was created,
-        whatever the environment says now), fp32, and solorl_step_act's policy shapes."""
-        return (self.get_property("step_n_one_launch") == 1 and self.get_property("f64") == 0 and self.obs_dim % 4 == 0 and self.obs_dim <= 88
-                and params.obs_dim == self.obs_dim and params.act_dim == self.act_dim and params.hidden == 64)
+        """solorl_rollout (K closed-loop steps in one launch) on this handle: the prerequisites of solorl_step_act."""
+        return self.step_act_supported(params)
 
     def rollout_inplace(self, actions, params, noise, value_out, logp_out, obs_out=None, rew_out=None, done_out=None, policy_after_last=False):
         """K closed-loop steps in one launch (solorl_rollout), in rollout-storage rows: actions [K (+1), N, A] -- row 0 drives the

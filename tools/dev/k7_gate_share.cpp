@@ -28,14 +28,7 @@ extern "C" void k7_substep(solorl_env_state* s, const solorl_config* c, int* nc,
   constexpr int NQ = RB::NQ;
   std::vector<unsigned char> mem(RowLds<T>::bytes(1) + 64);
   RowLds<T> lds; lds.lanes = 1; lds.lane = 0; lds.base = mem.data();
-  PhysParams<T> pp;
-  pp.dt = (T)c->sim_dt; pp.gravity = (T)c->gravity; pp.erp = (T)c->erp; pp.slop = (T)c->linear_slop; pp.warm = (T)c->warmstart;
-  pp.damping = (T)c->damping; pp.vmax = (T)c->max_velocity; pp.qlim = (T)c->joint_limit; pp.inv_dt = (T)(1.0 / c->sim_dt);
-  pp.iterations = c->solver_iterations;
-  pp.resid_thr = c->solver_residual_threshold > 0 ? (T)std::sqrt(c->solver_residual_threshold) : T(-1);
-  pp.cerp = (T)c->contact_erp; pp.cmargin = (T)c->collision_margin;
-  pp.set_mode(true, c->use_urdf_inertia != 0, c->friction_model == SOLORL_FRICTION_CONE, c->use_treadmill != 0);
-  pp.tm_hw = (T)c->treadmill_half_width; pp.tm_mu = (T)c->treadmill_friction;
+  const PhysParams<T> pp = make_phys<T>(*c);
   SubCtx<T, ROBOT> C;
   PhysState<T, NQ>& st = C.ps;
   C.tmy = (T)s->treadmill_y;
