@@ -2218,10 +2218,46 @@ template <typename T, int ROBOT, typename LDS> struct TeamCtx {
   static constexpr size_t bytes = TeamRows<T, LDS>::off_ctx + 4 * sizeof(SubCtx<T, ROBOT>);
 };
 
-// Helper wavefront of duo_kernel_team, one sub-step: the collision front between workgroup barriers A and B, nothing else.
-// Barrier A is behind the main wavefront's integrate of the previous sub-step (state, impulse cache, the row storage the sweep
-// read) and its C.R0 / sin / cos of this one; barrier B hands the front's results (selectors, support points, distances, the
-// base contacts' rows, the base link terms) to the main wavefront's leg rows.  Two barriers per sub-step, none under a predicate.
+// Helper wavefront of duo_kernel_team, the end of its B-to-C interval: the leg rates, then workgroup barrier C, which every lane's
+// wavefront passes whatever `valid` says.  (Not a phase_*: the barrier census of tests/test_helper_wave_static.py keeps the phases
+// and the kernel body as they are.  A leaf: a function that called phase_base_lead itself would save a register to scratch for its
+// return address.)
+template <typename T, int ROBOT, typename LDS, typename CH>
+SNI_SCALAR void duo_helper_rates(CH ch, const PhysParams<T> pp, const LDS lds, int t, bool valid) {
+  if (valid) phase_legrates_team<T, ROBOT, LDS, CH>(ch, pp, lds, t);
+  WG_SYNC();                              // barrier C
+}
+
+// Main wavefront of duo_kernel_team: barrier C, between its leg rows and the row finish (a function of its own for the same census;
+// nothing is live in registers across it that the phases on either side do not re-read from LDS).
+template <typename T, int ROBOT>
+SNI_SCALAR void duo_join_rows() {
+  WG_SYNC();                              // barrier C
+}
+
+// Helper wavefront of duo_kernel_team, one sub-step: the collision front between workgroup barriers A and B, then -- beside the main
+// wavefront's leg rows -- the leg sum, the base solve and the leg rates up to barrier C: the calls substep_team makes in the
+// classic kernel, in its order, on the same operands (phase_base_lead is the classic kernel's one instantiation; it reads neither
+// lam_prev nor nstride).  Three barriers per sub-step, none under a predicate.
+//   main   : R0, sin/cos | A | leg dynamics | B | leg rows                      | C | row finish, sweep, integrate
+//   helper :             | A | front        | B | leg sum, base solve, leg rates | C |
+// A is behind the main wavefront's integrate of the previous sub-step (state, impulse cache, the row storage the sweep read) and
+//   its C.R0 / sin / cos of this one.
+// B hands the front's results (selectors, support points, distances, the base contacts' rows, the base link terms) to the main
+//   wavefront's leg rows, and the main wavefront's C.Ileg / C.pleg / C.LR (stored by sub-lane 0 above its barrier B) to this one.
+// Between B and C (audit of every LDS word either side touches there):
+//   helper writes  C.Ibase, C.pbase (summed in place), C.ub, C.qds, bc[0..59], hdr[0], hdr[LN], and row 0 (the null row) of a
+//                  team WITHOUT rows (nlt + 3 nc == 0: the main wavefront parks nothing for such a team)
+//   helper reads   C.Ileg, C.pleg, C.LR (main, above B); C.Ibase, C.pbase, C.nc, C.nlim_total (its own front); the state
+//                  (C.ps.w, .v, .qd: next written by the main wavefront's integrate, behind C); bc[54..59] (its own)
+//   main writes    rows only (park_row: the row's core and its A_* words), of teams that HAVE rows
+//   main reads     C.lsel, C.mask, C.smask, C.nc, C.nlim_total, C.kneeP / footP / shP, C.dist, C.lamp -- none of them written
+//                  on this side of C
+// C hands bc, hdr, C.ub, C.qds and the null row to the main wavefront's row finish, sweep and integrate.  The helper writes
+//   them next behind the NEXT sub-step's B, which the main wavefront reaches only after its integrate; the front between the next
+//   A and B writes none of them (it does write C.Ibase / C.pbase, which the main wavefront never reads).  An idle team's
+//   hdr[0] = hdr[LN] = 0 is stored here, above C, where substep_team stores it in the classic kernel: phase_finish_team reads it.
+// The helper returns behind the last sub-step's C.
 template <typename T, int ROBOT, typename LDS>
 SD void substep_team_helper(const PhysParams<T> pp, const LDS& lds, int t, bool lead, bool valid) {
   using CH = typename TeamCtx<T, ROBOT, LDS>::type;
@@ -2230,6 +2266,20 @@ SD void substep_team_helper(const PhysParams<T> pp, const LDS& lds, int t, bool 
   if (pp.urdf_inertia()) phase_front_team<T, ROBOT, LDS, CH, true, true>(ch, pp, lds, t, valid, lead);
   else phase_front_team<T, ROBOT, LDS, CH, false, true>(ch, pp, lds, t, valid, lead);
   WG_SYNC();                              // barrier B (the main wavefront's is inside phase_leg_rt)
+#if defined(SOLO_WAVE_TIMING)
+  __builtin_amdgcn_s_waitcnt(0);
+  const long long wt_h0_ = clock64();
+#endif
+  if (valid) team_sum_base<T, ROBOT, CH>(ch, t);
+  if (lead) phase_base_lead<T, ROBOT, LDS, CH>(ch, pp, nullptr, 0u, lds);
+  else if (!valid && t == 0) {   // idle team: no rows
+    lds.hdr()[0] = T(0); lds.hdr()[LDS::LANES] = T(0);
+  }
+#if defined(SOLO_WAVE_TIMING)      // the helper's lane 0 adds to the slot the main wavefront leaves alone in the duo kernel (substep_team); the
+  __builtin_amdgcn_s_waitcnt(0);   // leg rates, 0.6 us per step, are not timed: their function ends in the barrier
+  if (threadIdx.x == 64) solo_pt_acc[4] += (unsigned long long)(clock64() - wt_h0_);
+#endif
+  duo_helper_rates<T, ROBOT, LDS, CH>(ch, pp, lds, t, valid);            // leg rates, barrier C (the main wavefront's: duo_join_rows)
 }
 
 // the leader's context C lives in LDS (see CtxLds); `C` is only dereferenced by leader lanes
@@ -2273,15 +2323,21 @@ SD int substep_team(const PhysParams<T> pp, T* lam_prev, unsigned nstride, const
   }
 #endif
   SOLO_PT(2);
-  if (valid) team_sum_base<T, ROBOT, CH>(ch, t);
-  SOLO_PT(3);
-  if (lead) phase_base_lead<T, ROBOT, LDS, CH>(ch, pp, lam_prev, nstride, lds);
-  else if (!valid && t == 0) {   // idle team: no rows
-    lds.hdr()[0] = T(0); lds.hdr()[LN] = T(0);
+  if constexpr (DUO) {
+    // leg sum, base solve and leg rates ran on the helper beside the leg rows (the audit is at substep_team_helper)
+    duo_join_rows<T, ROBOT>();             // barrier C
+    SOLO_PT(3);                            // (timing build: the wait at barrier C; slot 4 is the helper's, 5 stays zero)
+  } else {
+    if (valid) team_sum_base<T, ROBOT, CH>(ch, t);
+    SOLO_PT(3);
+    if (lead) phase_base_lead<T, ROBOT, LDS, CH>(ch, pp, lam_prev, nstride, lds);
+    else if (!valid && t == 0) {   // idle team: no rows
+      lds.hdr()[0] = T(0); lds.hdr()[LN] = T(0);
+    }
+    SOLO_PT(4);
+    if (valid) phase_legrates_team<T, ROBOT, LDS, CH>(ch, pp, lds, t);
+    SOLO_PT(5);
   }
-  SOLO_PT(4);
-  if (valid) phase_legrates_team<T, ROBOT, LDS, CH>(ch, pp, lds, t);
-  SOLO_PT(5);
   phase_finish_team<T, ROBOT, LDS>(pp, lds, t);
   SOLO_PT(6);
   phase_pgs_team<T, ROBOT, LDS>(pp.iterations, pp.warm != T(0), pp.resid_thr >= T(0), pp.pgs_pipe(), pp.cone(), lds, t);

@@ -628,9 +628,10 @@ SD void policy_tail_team(const PolicyTail& P, int O, int col, int t, idx_t env, 
   }
 }
 
-// DUO (duo_kernel_team): the workgroup has a second wavefront, the HELPER, which runs nothing but the collision front of every
-// sub-step (substep_team_helper) while this one, the main wavefront, computes the leg dynamics; both address the workgroup's one LDS
-// block with the lane index threadIdx.x & 63.  The helper loads nothing from HBM and stores nothing to it.
+// DUO (duo_kernel_team): the workgroup has a second wavefront, the HELPER, which runs the collision front of every sub-step while
+// this one, the main wavefront, computes the leg dynamics, and then the leg sum, the base solve and the leg rates while this one parks
+// the leg rows (substep_team_helper); both address the workgroup's one LDS block with the lane index threadIdx.x & 63.  The helper
+// loads nothing from HBM and stores nothing to it.
 template <typename T, int ROBOT, bool DUO = false>
 SD void step_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict__ snf, const int* __restrict__ sni, int M,
                   const Layout& L, int N, const EnvParams& P, const PhysParams<T>& pp, const float* __restrict__ actions,
@@ -672,9 +673,10 @@ SD void step_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict_
   SubCtx<T, ROBOT>& C = ch.get();
   T* const psv = reinterpret_cast<T*>(&C.ps);
   if constexpr (DUO) {
-    // Workgroup barriers of a step, per role: 2 x frame_skip (A and B of every sub-step; main: A in substep_team, B in phase_leg_rt;
-    // helper: both in substep_team_helper) -- plus the one behind the LDS poison fill above when that test hook is on, and, in a
-    // -DSOLO_WAVE_TIMING build, the one behind the counters' reset.  All of them sit on paths that depend on kernel arguments only.
+    // Workgroup barriers of a step, per role: 3 x frame_skip (A, B and C of every sub-step; main: A in substep_team, B in phase_leg_rt,
+    // C in duo_join_rows; helper: A and B in substep_team_helper, C in duo_helper_rates) -- plus the one behind the LDS poison fill
+    // above when that test hook is on, and, in a -DSOLO_WAVE_TIMING build, the one behind the counters' reset.  All of them sit on
+    // paths that depend on kernel arguments only; the helper returns behind the last sub-step's C.
     if (blk * 4u >= (unsigned)N) return;              // a workgroup of the padded grid without an env: both wavefronts leave here
     if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) {          // ---- the helper wavefront
 #pragma unroll 1
@@ -902,9 +904,10 @@ step_kernel_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict__
   step_team<T, ROBOT>(sf, si, snf, sni, M, L, N, P, pp, actions, out, mode);
 }
 
-// Helper wavefront: step_kernel_team with a second wavefront per workgroup that runs the collision front of
-// each sub-step beside the main wavefront's leg dynamics.  Same grid, same dynamic LDS (the two share the block), same register
-// bound; chosen by launch_step while every SIMD can hold both wavefronts of its workgroup.  fp32 only.
+// Helper wavefront: step_kernel_team with a second wavefront per workgroup that runs, in each sub-step, the
+// collision front beside the main wavefront's leg dynamics and then the leg sum, the base solve and the leg rates beside its leg
+// rows (three workgroup barriers per sub-step: substep_team_helper).  Same grid, same dynamic LDS (the two share the block), same
+// register bound; chosen by launch_step while every SIMD can hold both wavefronts of its workgroup.  fp32 only.
 template <typename T, int ROBOT>
 __global__ void __launch_bounds__(128, SOLO_WAVES_PER_SIMD)
 duo_kernel_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict__ snf, const int* __restrict__ sni, int M,

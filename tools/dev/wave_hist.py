@@ -63,13 +63,19 @@ if "SOLO_SWEEP_STATS" in os.environ.get("SOLORL_BUILD_DEFINES", "") and fr > 0:
 elif fr > 0: print("friction-slot visits with zero bound and zero impulse in every lane of the wavefront (a skip would be value-exact): %.1f %% of all, %.1f %% in the slowest 1 %% of the wavefronts" % (
     100.0 * R[:, :, 27].sum() / max(fr, 1), 100.0 * R[:, :, 27][slow_].sum() / max(frs, 1)))
 phases = ["sin/cos", "collision front", "legs (4 lanes)", "leg sum", "base solve (leader)", "leg rates", "row finish", "PGS sweep", "integrate"]
-if hw:      # duo_kernel_team: the stamps are the main wavefront's; the front runs on the helper between barriers A and B
+if hw:      # duo_kernel_team: the stamps are the main wavefront's; the helper runs the front between barriers A and B and the leg sum,
+    # the base solve and the leg rates between B and C, beside the main wavefront's leg rows: slot 4 is the HELPER's interval from B
+    # to the end of the base solve (its leg rates, ~0.6 us per step, end in barrier C and are not timed)
     phases[0], phases[1], phases[2] = "R0 + sin/cos", "barrier A", "front || legs (to barrier B) + leg rows"
+    phases[3], phases[4], phases[5] = "barrier C (wait for helper)", "HELPER: leg sum + base solve", "(leg rates: helper, untimed)"
 phases.append("  of the legs: dynamics above the lsel read (not drained)")
 print("helper wavefront: %s (SOLORL_HELPER_WAVE=0/1 pins it)" % ("on" if hw else "off"))
 print("phases of the sub-steps, summed over a step's %d sub-steps (us; mean over all wavefronts | over the slowest 1 %%; timing build drains the memory counters at every stamp):" % c.frame_skip)
 for i, n_ in enumerate(phases):
     print("  %-28s %7.2f | %7.2f" % (n_, us(R[:, :, 16 + i].mean()), us(R[:, :, 16 + i][slow_].mean())))
+if hw:
+    main_ = R[:, :, 16:25].sum(axis=2) - R[:, :, 20]          # the main wavefront's own chain: every slot but the helper's
+    print("  main wavefront's chain (all but the helper's slot) %7.2f | %7.2f" % (us(main_.mean()), us(main_[slow_].mean())))
 bw = 10.0
 edges = np.arange(0, us(tot.max()) + bw, bw)
 h, _ = np.histogram(us(tot), bins=edges)
