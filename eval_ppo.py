@@ -38,7 +38,12 @@ def main(argv=None):
         config["task"] = a.task
     ckpt = torch.load(os.path.join(a.checkpoint_dir, "solo.pt"), map_location="cpu", weights_only=False)
     dev = torch.device("cuda:0")
-    env = make_vec_envs(config, a.num_agents, None, device=dev, training=False, seed=a.seed)
+    # a checkpoint trained with --normalize-obs carries the observation statistics: the policy sees observations scaled by them,
+    # frozen (testing/test_ppo.py:89-90); rewards are reported raw
+    ob_rms = ckpt.get("ob_rms")
+    env = make_vec_envs(config, a.num_agents, None, device=dev, training=False, seed=a.seed, norm_obs=ob_rms is not None)
+    env.ob_rms = ob_rms
+    env.eval()
     policy = Policy(env.observation_space.shape, env.action_space, None, {"hidden_size": a.hidden_size}).to(dev)
     policy.load_state_dict(ckpt["state_dict"])
     policy.eval()
@@ -56,7 +61,7 @@ def main(argv=None):
         if push_gen is not None and steps > 0 and steps % a.push_interval == 0:
             dv[:, :2] = (torch.rand((a.num_agents, 2), device=dev, generator=push_gen) * 2 - 1) * a.push_max_vel
             env.push(dv)
-            obs = env.get_observation()          # the policy sees the kicked velocities
+            obs = env.normalize_obs(env.get_observation())          # the policy sees the kicked velocities
         steps += 1
         with torch.no_grad():
             _, action, _ = policy.act(obs, deterministic=a.deterministic)

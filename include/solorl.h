@@ -33,6 +33,9 @@
  *                             env), starts from a chosen state distribution, branching one env into many, resetting a chosen subset,
  *                             saving / restoring a batch and logging a batch reduce to.  Row i is env i of the handle; a byte mask
  *                             selects envs, SOLORL_SF_* bits select member groups on write.  No host synchronisation: capturable.
+ *   solorl_normalize_obs / solorl_normalize_rewards <- agents/running_mean_std.py:73-127 (VecNormalize: _obfilt :109-116, the reward half
+ *                             of step :98-105) with RunningMeanStd.update (:18-39), which agents/ppo/envs.py:25-26 wraps round the vec-env:
+ *                             running statistics in caller-owned device memory, fp64, a fixed number of launches for any number of rows
  *   solorl_destroy         <- agents/ppo/envs.py:129-135 (close)
  *
  * Plain pointers and sizes only; no torch types.  All array arguments are DEVICE pointers
@@ -265,6 +268,34 @@ int solorl_compute_returns(const float* rewards /* [T*N] */, float* value_preds 
                            const float* masks /* [(T+1)*N] */, const float* next_value /* [N] */,
                            float* returns /* [(T+1)*N] */, int T, int N, int use_gae, float gamma,
                            float gae_lambda, int device_id, void* stream);
+
+/* Running normalisation of observations and rewards (VecNormalize, agents/running_mean_std.py:73-127).  State is the caller's device
+ * memory: `stats` = mean[D], var[D], count as 2 D + 1 doubles (initially 0, 1, 1e-4: running_mean_std.py:13-16; D = the observation size,
+ * or 1 for the returns) and `ret` = the n discounted-return accumulators, doubles as the reference's.  Statistics and batch moments are
+ * fp64 sums in an order that depends on (n, D) only -- no atomics, the same bits on every run and graph replay, and one call over R rows
+ * gives the bits of R calls over one row; outputs are rounded to float once.  Everything is enqueued on `stream` as a linear chain of
+ * launches whose number does not depend on `rows` (update != 0: 4 for observations, 5 for rewards; update == 0: one), without host
+ * synchronisation or allocation: capturable.  Limits: D <= 1024, rows <= 65535, n D < 2^31, a scratch count below 2^31.
+ * Null array, `rows`, `n` or `D` < 1, a shape beyond the limits or a null `scratch`: SOLORL_ERR_INVALID, the message names the function
+ * (checked before any HIP call). */
+
+/* doubles of scratch the two calls below need with these (rows, n, D) -- D = 1 for the rewards (0 for bad arguments) */
+int solorl_norm_scratch_count(int rows, int n, int D);
+
+/* VecNormalize._obfilt (running_mean_std.py:109-116) for rows x [n][D] observations, row after row:
+ *   update != 0: stats <- update_mean_var_count_from_moments of (stats, mean_n x, var_n x, n)   (:18-39; population variance)
+ *   out = clip((x - mean) / sqrt(var + epsilon), -clip, clip)   with the stats AFTER that row's update
+ * obs_out may be obs_in (in place). */
+int solorl_normalize_obs(double* stats, int rows, int n, int D, const float* obs_in, float* obs_out,
+                         int update, double clip, double epsilon, double* scratch, int device_id, void* stream);
+
+/* VecNormalize.step's reward half (:98-105) for rows x [n] rewards, row after row:
+ *   ret = ret * gamma + r;  update != 0: stats (D = 1) <- moments of ret over the n envs;
+ *   r_out = clip(r / sqrt(var + epsilon), -clip, clip);  ret[done != 0] = 0          (in this order)
+ * rewards are rewritten in place; done is [rows][n] bytes. */
+int solorl_normalize_rewards(double* stats, double* ret, int rows, int n, float* rewards, const uint8_t* done,
+                             int update, double gamma, double clip, double epsilon, double* scratch,
+                             int device_id, void* stream);
 
 /* Fused PPO mini-batch loss, forward + gradients w.r.t. the policy heads (device arrays, m samples, A action dims):
  *   logp_i = sum_j -0.5 z_ij^2 - logstd_j - log sqrt(2 pi),  z = (action - mean) exp(-logstd);  ratio = exp(logp - old_logp)

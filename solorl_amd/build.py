@@ -12,6 +12,7 @@ INC = [os.path.join(ROOT, "include", f) for f in ("solorl.h", "solorl_model_data
 UNITS = {
     "solorl_hip.hip": [os.path.join(HERE, "csrc", f) for f in ("solorl_hip.hip", "dynamics.hpp", "spatial.hpp")] + INC,
     "solorl_ppo.hip": [os.path.join(HERE, "csrc", "solorl_ppo.hip"), INC[0]],
+    "solorl_norm.hip": [os.path.join(HERE, "csrc", "solorl_norm.hip"), INC[0]],
 }
 SRC = UNITS["solorl_hip.hip"][:3]
 LIB = os.path.join(HERE, "_lib", "libsolorl_hip.so")

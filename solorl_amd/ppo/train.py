@@ -8,6 +8,8 @@ Differences that come with the GPU engine (documented, not behavioural):
   * episode statistics are accumulated by the step kernel on the device at EVERY step (no sampling) instead of
     iterating N Python dicts per step (train.py:90-100) -- same quantities: episode_reward (last-step reward,
     baseEnv.py:65), episode_length, success, dr/* sums, as means over the episodes finished per log interval;
+  * args.normalize_obs / args.normalize_returns switch on the reference's VecNormalize (agents/running_mean_std.py:73-127; its launcher
+    hard-codes both off) on the device, single process only; the checkpoint's `ob_rms` then carries the statistics, as the reference's;
   * multi-GPU: one process per GPU (`python -m torch.distributed.run --nproc-per-node W ...`), envs
     sharded by rank (global env id = rank*N + i), flat-bucket RCCL gradient all-reduce (ppo.py).
 """
@@ -71,7 +73,13 @@ def train(args, config, env_constructor=None, writer=None):
         torch.cuda.manual_seed_all(args.seed)
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0"))) if args.cuda else torch.device("cpu")
     N = args.num_agents
-    envs = make_vec_envs(config, N, env_constructor, args.gamma, device, seed=args.seed, env_id_offset=rank * N)
+    norm_obs, norm_ret = bool(getattr(args, "normalize_obs", False)), bool(getattr(args, "normalize_returns", False))
+    if world > 1 and (norm_obs or norm_ret):
+        # every rank would keep statistics of its own shard and the policies would drift apart; merging moments across ranks is not built
+        raise NotImplementedError("--normalize-obs / --normalize-returns need a single process (world size %d): the running statistics "
+                                  "are not merged across ranks" % world)
+    envs = make_vec_envs(config, N, env_constructor, args.gamma, device, seed=args.seed, env_id_offset=rank * N,
+                         norm_obs=norm_obs, norm_ret=norm_ret)
     action_dim = envs.action_space.shape[0]
     base = torch.load(args.base_checkpoint) if getattr(args, "base_checkpoint", None) else None
     actor_critic = Policy(envs.observation_space.shape, envs.action_space, base, {"hidden_size": args.hidden_size}).to(device)
@@ -108,7 +116,10 @@ def train(args, config, env_constructor=None, writer=None):
         total = (j + 1) * N * world * args.num_steps
         if rank == 0 and args.logdir is not None and (j % args.save_interval == 0 or j == num_updates - 1):
             os.makedirs(args.logdir, exist_ok=True)
+            # ob_rms / ret_rms: host RunningMeanStd copies of the device statistics (one small device -> host copy each)
             ckpt = {"update": j, "state_dict": actor_critic.state_dict(), "ob_rms": getattr(envs.envs, "ob_rms", None)}
+            if getattr(envs.envs, "ret_rms", None) is not None:
+                ckpt["ret_rms"] = envs.envs.ret_rms
             torch.save(ckpt, os.path.join(args.logdir, "solo_{}.pt".format(total)))
             torch.save(ckpt, os.path.join(args.logdir, "solo.pt"))
         if j % args.log_interval == 0:

@@ -6,6 +6,8 @@
   step(actions Tensor[N, A]) -> (obs[N,O], reward[N,1], done[N] f32, infos)   (envs.py:189-196)
   step_n(actions Tensor[K, N, A]) -> (obs[K,N,O], reward[K,N,1], done[K,N] f32, infos)  (K steps, one launch: no reference counterpart)
   get_observation(), increment_curriculum(), close(), observation_space, action_space, nenvs
+  ob_rms, ret_rms, training, train(), eval(): the reference's VecNormalize (agents/running_mean_std.py:73-127) when make_vec_envs is given
+      norm_obs / norm_ret -- running statistics on the device (normalize.py, include/solorl.h solorl_normalize_obs / solorl_normalize_rewards)
   get_states(mask) -> StateBatch, set_states(states, mask, fields), reset_masked(mask) -> obs, push(dv, mask)   (the whole batch's state as
       one device array, include/solorl.h solorl_get_states ...: no reference counterpart)
 
@@ -19,6 +21,7 @@ import torch
 
 from . import _native
 from .config import SoloConfig, EnvState, InfoSoA, config_from_dict, EPSTAT_FIELDS, EPSTAT_NAMES
+from .normalize import RunningMeanStd, VecNormalizer
 from .state import StateBatch, field_bits, SF_VEL
 
 
@@ -90,7 +93,8 @@ class SoloVecEnv:
     """Batched SoloBaseEnv on one MI355X.  ``config`` is a reference-style dict (configs/*.yaml)
     or a ``SoloConfig``."""
 
-    def __init__(self, config, num_envs, device=None, seed=1, env_id_offset=0, applied_torque=False, **overrides):
+    def __init__(self, config, num_envs, device=None, seed=1, env_id_offset=0, applied_torque=False, norm_obs=False, norm_ret=False,
+                 clipob=10.0, cliprew=10.0, gamma=0.99, epsilon=1e-8, **overrides):
         self.cfg = config.copy() if isinstance(config, SoloConfig) else config_from_dict(config, **overrides)
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
@@ -130,7 +134,11 @@ class SoloVecEnv:
         self._kbuf = {}             # engine-owned [K, ...] rows of step_n_inplace / rollout_inplace, per K
         self._info_c = InfoSoA(ep_stats=self._ep_stats.data_ptr(), applied_torque=None if self._tau is None else self._tau.data_ptr(),
                                **{k: self._info[k].data_ptr() for k in _INFO_KEYS})
-        self.ob_rms = None          # VecNormalize(ob=False): agents/ppo/envs.py:26, read at train.py:126
+        # VecNormalize (agents/running_mean_std.py:73-127; the reference's launcher passes ob=False, ret=False: agents/ppo/envs.py:26):
+        # nothing is allocated or launched unless a switch is on
+        self._norm = VecNormalizer(N, self.obs_dim, device, norm_obs, norm_ret, clipob, cliprew, gamma, epsilon) if (norm_obs or norm_ret) else None
+        self._norm_obs, self._norm_ret = bool(norm_obs), bool(norm_ret)
+        self.training = True        # running_mean_std.py:94
         self.closed = False
 
     # reference call path: PyTorchEnvWrapper.envs (VecNormalize) .venv ...
@@ -145,12 +153,69 @@ class SoloVecEnv:
     def __len__(self):
         return self.nenvs
 
+    # ---- VecNormalize: the statistics live on the device; ob_rms / ret_rms are host copies (one device -> host copy per read), and
+    # assigning one (`env.envs.ob_rms = ckpt['ob_rms']`, testing/test_ppo.py:89-90) uploads it
+    @property
+    def ob_rms(self):
+        return RunningMeanStd(shape=(self.obs_dim,)).from_device(self._norm.ob_stats) if self._norm_obs else None
+
+    @ob_rms.setter
+    def ob_rms(self, rms):
+        if rms is None and not self._norm_obs:
+            return
+        if rms is None or not self._norm_obs:
+            raise _native.SoloRLError("ob_rms can only be assigned statistics on an env made with norm_obs=True (and never None on one)")
+        rms.to_device(self.device, out=self._norm.ob_stats)
+
+    @property
+    def ret_rms(self):
+        return RunningMeanStd(shape=()).from_device(self._norm.ret_stats) if self._norm_ret else None
+
+    @ret_rms.setter
+    def ret_rms(self, rms):
+        if rms is None and not self._norm_ret:
+            return
+        if rms is None or not self._norm_ret:
+            raise _native.SoloRLError("ret_rms can only be assigned statistics on an env made with norm_ret=True (and never None on one)")
+        rms.to_device(self.device, out=self._norm.ret_stats)
+
+    def eval(self):
+        """running_mean_std.py:123-124: the statistics stop updating (the scaling goes on)"""
+        self.training = False
+
+    def train(self):
+        self.training = True
+
+    def normalize_obs(self, obs, update=False):
+        """What the policy sees for raw observations [N, O] (get_observation() stays raw, as the reference's wrapper leaves it): a
+        normalised copy, the statistics untouched unless ``update``.  Identity without norm_obs."""
+        if not self._norm_obs:
+            return obs
+        x = obs.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        return self._norm.obs(x, 1, update, out=torch.empty_like(x))
+
+    def _normalize(self, o, r, d, rows):
+        """The wrapper's half of a step (running_mean_std.py:96-107) on the `rows` rows the engine has just written, in place."""
+        if self._norm_obs:
+            self._norm.obs(o, rows, self.training)
+        if self._norm_ret:
+            self._norm.rewards(r, d, rows, self.training)
+
+    def _no_policy_tail(self, name):
+        if self._norm_obs:
+            raise _native.SoloRLError("%s on an env with norm_obs: the policy inside the step kernel would read raw observations "
+                                      "(step_act_supported() / rollout_supported() are False)" % name)
+
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def reset(self):
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_reset(self._h, C.c_void_p(self._obs.data_ptr()), self._stream()))
+        if self._norm is not None:                      # running_mean_std.py:118-121
+            self._norm.ret.zero_()
+            if self._norm_obs:
+                self._norm.obs(self._obs, 1, self.training)
         return self._obs.clone()
 
     def step(self, actions):
@@ -162,6 +227,8 @@ class SoloVecEnv:
             _native.check(self.L.solorl_step(self._h, C.c_void_p(a.data_ptr()), C.c_void_p(self._obs.data_ptr()),
                                              C.c_void_p(self._rew.data_ptr()), C.c_void_p(self._done.data_ptr()),
                                              C.byref(self._info_c), self._stream()))
+        if self._norm is not None:
+            self._normalize(self._obs, self._rew, self._done, 1)
         t = {k: v.clone() for k, v in self._info.items()}
         t["done"] = self._done.clone()
         return self._obs.clone(), self._rew.clone().unsqueeze(-1), t["done"].float(), LazyInfos(t, t["done"])
@@ -188,18 +255,22 @@ class SoloVecEnv:
         self._steps_issued += 1
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_step(self._h, a, po, pr, C.c_void_p(d.data_ptr()), C.byref(self._info_c), self._stream()))
+        if self._norm is not None:
+            self._normalize(o, r, d, 1)
         return o, r, d, self._info
 
     def step_act_supported(self, params):
         """The policy tail's prerequisites (solorl_step_act, solorl_rollout; include/solorl.h), decided from the handle -- what the engine
         latched at solorl_create, whatever the environment says now: fp32, team mode, no sorting, and an observation size that is a
         multiple of 4 floats and at most 88 (zero or one history level) with the reference's hidden-64 MLP on it."""
-        return (self.get_property("step_n_one_launch") == 1 and self.get_property("f64") == 0 and self.obs_dim % 4 == 0 and self.obs_dim <= 88
+        return (not self._norm_obs                 # (the policy inside the step kernel would read the raw observations)
+                and self.get_property("step_n_one_launch") == 1 and self.get_property("f64") == 0 and self.obs_dim % 4 == 0 and self.obs_dim <= 88
                 and params.obs_dim == self.obs_dim and params.act_dim == self.act_dim and params.hidden == 64)
 
     def step_act_inplace(self, actions, params, noise, value_out, action_out, logp_out, obs_out=None, rew_out=None, done_out=None):
         """step_inplace + Policy.act on the new observations in ONE launch (solorl_step_act): value_out [N] or [N,1], action_out [N,A] =
         mean + exp(logstd) * noise (noise [N,A] or None), logp_out [N] or [N,1] -- e.g. the NEXT step's rollout-storage rows."""
+        self._no_policy_tail("step_act_inplace")
         a = self._raw("actions", actions, (self.nenvs, self.act_dim))
         o = self._obs if obs_out is None else obs_out
         r = self._rew if rew_out is None else rew_out
@@ -216,6 +287,8 @@ class SoloVecEnv:
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_step_act(self._h, a, po, pr, C.c_void_p(d.data_ptr()), C.byref(self._info_c), C.byref(params), pn, pv, pa, pl,
                                                  self._stream()))
+        if self._norm_ret:
+            self._normalize(o, r, d, 1)
         return o, r, d, self._info
 
     def _k_rows(self, K):
@@ -273,6 +346,8 @@ class SoloVecEnv:
         self._steps_issued += K
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_step_n(self._h, K, pa, po, pr, pd, C.byref(b["c"]), self._stream()))
+        if self._norm is not None:                      # one call for the window's K rows
+            self._normalize(o, r, d, K)
         return o, r, d, b["info"]
 
     def rollout_supported(self, params):
@@ -284,6 +359,7 @@ class SoloVecEnv:
         first step, rows 1.. are written by the policy on the observations the steps produce (row K too with policy_after_last: the
         first action of the next window); noise [K (+1), N, A] or None (actions = the mean); value_out / logp_out [K (+1), N] or
         [K (+1), N, 1], rows from 1 written; obs_out [K, N, O], rew_out [K, N] or [K, N, 1], done_out uint8 [K, N] as step_n_inplace."""
+        self._no_policy_tail("rollout_inplace")
         pal = 1 if policy_after_last else 0
         R = int(actions.shape[0]) if actions.dim() == 3 else 0
         K = R - pal
@@ -298,6 +374,8 @@ class SoloVecEnv:
         self._steps_issued += K
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_rollout(self._h, K, pa, po, pr, pd, C.byref(b["c"]), C.byref(params), pn, pv, pl, pal, self._stream()))
+        if self._norm_ret:                              # one call for the window's K rows, after the window
+            self._normalize(o, r, d, K)
         return o, r, d, b["info"]
 
     def get_observation(self):
@@ -406,6 +484,11 @@ class SoloVecEnv:
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_get_observation(self._h, C.c_void_p(self._obs.data_ptr()), self._stream()))
             _native.check(self.L.solorl_reset_masked(self._h, pm, C.c_void_p(self._obs.data_ptr()), self._stream()))
+        if self._norm is not None:
+            sel = m.bool()
+            self._norm.ret.masked_fill_(sel, 0.0)       # a reset env starts a new return (running_mean_std.py:105)
+            if self._norm_obs:                           # the selected rows as a reset() gives them, without an update; the others stay raw
+                return torch.where(sel.unsqueeze(-1), self._norm.obs(self._obs, 1, False, out=torch.empty_like(self._obs)), self._obs)
         return self._obs.clone()
 
     def push(self, dv, mask=None):
@@ -437,8 +520,14 @@ class SoloVecEnv:
 
 
 def make_vec_envs(config, num_envs, env_constructor=None, gamma=0.99, device=None, training=True, seed=1,
-                  env_id_offset=0):
+                  env_id_offset=0, norm_obs=False, norm_ret=False, clipob=10., cliprew=10., epsilon=1e-8):
     """Signature of agents/ppo/envs.py:14.  ``env_constructor`` (the per-process gym env class of the
-    reference) and ``gamma`` (VecNormalize's unused return accumulator, ob=False, ret=False) are
-    accepted for call-site compatibility and ignored."""
-    return SoloVecEnv(config, num_envs, device=device, seed=seed, env_id_offset=env_id_offset)
+    reference) is accepted for call-site compatibility and ignored.  ``norm_obs`` / ``norm_ret`` are VecNormalize's ``ob`` /
+    ``ret`` (agents/running_mean_std.py:79; the reference's launcher passes False, False, and so do the defaults here) with its
+    ``clipob``, ``cliprew``, ``epsilon``; ``gamma`` is the discount of its return accumulator and means something with ``norm_ret``.
+    ``training=False`` is its eval() (agents/ppo/envs.py:27-28)."""
+    envs = SoloVecEnv(config, num_envs, device=device, seed=seed, env_id_offset=env_id_offset, norm_obs=norm_obs, norm_ret=norm_ret,
+                      clipob=clipob, cliprew=cliprew, gamma=gamma, epsilon=epsilon)
+    if not training:
+        envs.eval()
+    return envs

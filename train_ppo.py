@@ -42,6 +42,8 @@ def get_ppo_args(argv=None):
     p.add_argument("--save-interval", type=int, default=20)
     p.add_argument("--config-file", type=str, default="configs/basic.yaml")
     p.add_argument("--task", type=str, default=None)
+    p.add_argument("--normalize-obs", action="store_true", default=False, help="running observation normalisation (VecNormalize ob=True)")
+    p.add_argument("--normalize-returns", action="store_true", default=False, help="running return normalisation of the rewards (VecNormalize ret=True, discount --gamma)")
     p.add_argument("--num-steps", type=int, default=None, help="rollout length (default: episode_length, train_ppo.py:62-63)")
     return p.parse_args(argv)
 
