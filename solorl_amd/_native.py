@@ -112,6 +112,11 @@ def lib():
     return _LIB
 
 
+def stream(device):
+    """The caller's current HIP stream on `device`, as the C ABI takes it"""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
 def check(rc):
     if rc != 0:
         raise SoloRLError("solorl error %d: %s" % (rc, lib().solorl_last_error().decode()))

@@ -44,11 +44,14 @@ def _same_flags():
 def needs_build():
     """Stale sources OR a library built with other flags (an instrumented SOLORL_BUILD_DEFINES / SOLORL_BUILD_FLAGS build must
     never be reused by a plain run: the bench and the tests would measure the wrong binary).  A missing flag record with a
-    library present (e.g. a prebuilt .so shipped to a box without its objects) counts as matching only for the plain flags."""
+    library present counts as matching only for the plain flags, and only without objects (a prebuilt .so shipped to a box
+    without them): objects without a record are what a failed or interrupted build leaves, under whatever flags it had."""
     if any(_stale(LIB, deps) for deps in UNITS.values()):
         return True
     if os.path.exists(TAG):
         return not _same_flags()
+    if any(os.path.exists(o) for o, _, _ in _jobs(_flags())):
+        return True
     return bool(os.environ.get("SOLORL_BUILD_DEFINES", "").split() or os.environ.get("SOLORL_BUILD_FLAGS", "").split())
 
 
@@ -74,6 +77,9 @@ def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = _flags()
     same = _same_flags()
+    # no flag record while objects are being rewritten: a failed or interrupted build leaves none, and the next build compiles every part
+    if os.path.exists(TAG):
+        os.remove(TAG)
     objs, running = [], []
     for o, deps, extra in _jobs(flags):
         objs.append(o)

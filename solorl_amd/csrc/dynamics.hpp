@@ -155,8 +155,8 @@ extern __shared__ __attribute__((aligned(16))) unsigned char solo_smem_sym[];
 // it from that constant.  (Through the `extern __shared__` symbol a NON-kernel function finds the start of the dynamic LDS with a
 // scalar load from a per-kernel table -- an exposed scalar-cache round trip at the top of every phase call, and, since scalar loads
 // return out of order, an s_waitcnt lgkmcnt(0) that drains every LDS read in flight wherever the compiler re-loads it.)
-// Checked on the HOST: solorl_step compares the loaded kernel's static LDS size (hipFuncGetAttributes) with the constant before its
-// first launch (check_lds_base, solorl_hip.hip: SOLORL_ERR_HIP instead of wrong physics), and tests/test_abi.py reads the same
+// Checked on the HOST: solorl_create compares the static LDS size of every step kernel the handle can launch (hipFuncGetAttributes)
+// with the constant (check_lds_base, solorl_hip.hip: SOLORL_ERR_HIP instead of wrong physics), and tests/test_abi.py reads the same
 // number from the built code object.  Nothing is checked on the device.
 #if defined(SOLO_WAVE_TIMING)
 constexpr unsigned SOLO_LDS_BASE = 80;                   // behind solo_pt_acc[10] -- which only the TEAM kernel references: the timing build

@@ -516,6 +516,8 @@ SD void team_current_state(const SubCtx<T, ROBOT>& C, int task, int D, int t, T 
 // (one history level).
 constexpr float POL_HALF_LOG_2PI = 0.91893853320467274178f;
 constexpr unsigned POL_ENV_BYTES = 2496;     // per-env slice of the row storage (26 rows x 24 values x 4 B): obs <= 96, h1 128, h2 128 floats
+static_assert(POL_ENV_BYTES == MAX_ROWS * (ROW_CORE + 4) * sizeof(float), "the policy tail's per-env slice is one env's fp32 row storage (RowLds)");
+static_assert((224 + 128) * sizeof(float) <= POL_ENV_BYTES, "the last activation block (h2: 128 floats at float offset 224) must end inside the slice");
 SD float pol_tanh(float x) { const float e = __expf(2.0f * x); return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + e); }   // as solorl_ppo.hip tanh_fast
 typedef float nfloat4 __attribute__((ext_vector_type(4)));          // (native vector: HIP's float4 class cannot be read through an address-space pointer)
 typedef __attribute__((address_space(1))) const nfloat4 gfloat4;
@@ -1279,7 +1281,6 @@ struct solorl_env {
   double* dyn = nullptr;   // device copy of the mutable parameters (EnvParams::dyn)
   std::vector<unsigned> stab_host;   // row-word / field-group table of a solorl_env_state row (build_state_table): solorl_get_state / solorl_set_state
   unsigned* stab = nullptr;          // its device copy: get_states_kernel / set_states_kernel
-  int epw = 64;   // envs per wavefront (lanes per workgroup)
   bool spread = true;
   bool team = false;   // 16 lanes per env (set at create: default true)
   int lds_poison_on = 0; unsigned lds_poison = 0;   // SOLORL_POISON_LDS test hook
@@ -1305,95 +1306,95 @@ EnvParams make_env_params(const solorl_env* h) {
 }
 
 // The phase functions address the dynamic LDS from the constant SOLO_LDS_BASE (dynamics.hpp): true exactly while a step kernel's
-// static LDS has that size.  Checked against the loaded code object, once per kernel and process.
-static int check_lds_base(const void* kernel, bool& checked) {
-  if (checked) return 0;
+// static LDS has that size.  Checked against the loaded code object for every kernel a handle can launch, at create (prepare_kernels).
+inline int check_lds_base(const void* kernel) {
   hipFuncAttributes a;
   HIP_TRY(hipFuncGetAttributes(&a, kernel));
   if (a.sharedSizeBytes != (size_t)SOLO_LDS_BASE)
     return fail(SOLORL_ERR_HIP, "step kernel's static LDS size differs from SOLO_LDS_BASE: the phase functions' dynamic-LDS base constant does not hold "
                                 "(a -DSOLO_WAVE_TIMING build runs team mode only)");
-  checked = true;
   return 0;
 }
 
+// ---- the launch rules, one function each: launches, solorl_create's checks and solorl_get_property all ask these
+// team mode's grid: a workgroup per four envs, a multiple of 8 (XCD-contiguous env ranges, step_team)
+inline int team_grid(int N) { return (((N + 3) / 4) + 7) & ~7; }
+// Pipelined sweep while every wavefront has a SIMD to itself, plain sweep above that (pgs_team_variant: 8192 envs 0.226 ->
+// 0.210 ms per step).  The two are re-associations of the same sums, so an env's last bits depend on which side of h->simds
+// workgroups its batch is; SOLORL_PGS_PIPE=1 (or 0) pins one variant for every batch size.  A function of the LAUNCH's N: the
+// snapshots are simulated with N = 1 (build_snapshots_t) whatever the handle's batch.
+inline bool team_pipe(const solorl_env* h, int N) { return h->pipe_override >= 0 ? h->pipe_override != 0 : team_grid(N) <= h->simds; }
 // Helper wavefront (duo_kernel_team): fp32 team mode on a fixed state buffer, while the batch's grid gives every SIMD at most one
 // workgroup -- its two wavefronts then have the SIMD's two slots to themselves; SOLORL_HELPER_WAVE=0 pins it off (=1 is checked
-// against the same rule at create and refused beyond it)
-inline bool helper_wave_allowed(const solorl_env* h) {
-  return h->team && !h->f64 && !h->sort && ((((h->N + 3) / 4) + 7) & ~7) <= h->simds;
-}
+// against the same rule at create and refused beyond it).  A function of h->N, not of a launch's N: what solorl_get_property
+// "helper_wave" reports is what every launch of the handle takes.
+inline bool helper_wave_allowed(const solorl_env* h) { return h->team && !h->f64 && !h->sort && team_grid(h->N) <= h->simds; }
 inline bool helper_wave_rule(const solorl_env* h) { return h->helper_override != 0 && helper_wave_allowed(h); }
+// solorl_step_n / solorl_rollout take one launch exactly where solorl_step is one team-mode launch on a fixed state buffer
+inline bool step_n_one_launch(const solorl_env* h) { return h->team && !h->sort; }
 
-// team mode: grid (a multiple of 8: XCD-contiguous env ranges, step_team), LDS bytes, and the physics parameters with the sweep
-// variant of this batch size
+// team mode: grid, LDS bytes, and the physics parameters with the sweep variant of this batch size
 template <typename T, int ROBOT>
 PhysParams<T> team_launch_shape(const solorl_env* h, int N, dim3& grid, size_t& smem) {
-  grid = dim3((((N + 3) / 4) + 7) & ~7);
+  grid = dim3(team_grid(N));
   using TeamLds = RowLds<T, 4>;
   smem = TeamCtx<T, ROBOT, TeamLds>::bytes;
   static_assert(sizeof(T) == 8 || TeamCtx<T, ROBOT, TeamLds>::bytes <= 20480, "team-mode LDS must allow 8 workgroups per CU (two wavefronts per SIMD)");
   PhysParams<T> pp = make_phys<T>(h->cfg);
-  // Pipelined sweep while every wavefront has a SIMD to itself, plain sweep above that (pgs_team_variant: 8192 envs 0.226 ->
-  // 0.210 ms per step).  The two are re-associations of the same sums, so an env's last bits depend on which side of
-  // h->simds workgroups its batch is; SOLORL_PGS_PIPE=1 (or 0) pins one variant for every batch size.
-  bool pipe = (int)grid.x <= h->simds;
-  if (h->pipe_override >= 0) pipe = h->pipe_override != 0;
-  pp.mode = (pp.mode & ~PhysParams<T>::M_PIPE) | (pipe ? PhysParams<T>::M_PIPE : 0);
+  pp.mode = (pp.mode & ~PhysParams<T>::M_PIPE) | (team_pipe(h, N) ? PhysParams<T>::M_PIPE : 0);
   return pp;
+}
+
+// Once per handle, at create: the SOLO_LDS_BASE check of every step kernel the handle can launch, and lane mode's dynamic-LDS limit
+// (hipFuncSetAttribute is per device; the handle's device is current).  launch_step / launch_rollout only shape and launch.
+template <typename T, int ROBOT>
+int prepare_kernels(const solorl_env* h) {
+  if (int rc = check_lds_base(h->team ? reinterpret_cast<const void*>(step_kernel_team<T, ROBOT>) : reinterpret_cast<const void*>(step_kernel<T, ROBOT>))) return rc;
+  if constexpr (sizeof(T) == 4)
+    if (helper_wave_rule(h))
+      if (int rc = check_lds_base(reinterpret_cast<const void*>(duo_kernel_team<T, ROBOT>))) return rc;
+  if (step_n_one_launch(h))
+    if (int rc = check_lds_base(reinterpret_cast<const void*>(rollout_kernel_team<T, ROBOT>))) return rc;
+  if (!h->team)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(step_kernel<T, ROBOT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)RowLds<T>::bytes(sizeof(T) == 8 ? 32 : 64)));
+  return 0;
 }
 
 template <typename T, int ROBOT>
 int launch_step(solorl_env* h, T* sf, int* si, int N, const float* actions, const Outputs& out, int mode, hipStream_t st) {
-  static bool lds_checked[3] = {false, false, false};
-  if (int rc = check_lds_base(h->team ? reinterpret_cast<const void*>(step_kernel_team<T, ROBOT>) : reinterpret_cast<const void*>(step_kernel<T, ROBOT>),
-                              lds_checked[h->team ? 1 : 0])) return rc;
   if (h->team) {
-    auto kt = step_kernel_team<T, ROBOT>;
-    dim3 grid, block(64);
+    dim3 grid;
     size_t team_smem = 0;
     const PhysParams<T> pp = team_launch_shape<T, ROBOT>(h, N, grid, team_smem);
     if constexpr (sizeof(T) == 4) {
-      // two wavefronts per workgroup while every SIMD can hold both (the size rule of the pipelined sweep); h->N, not this launch's N:
-      // what solorl_get_property "helper_wave" reports is what every launch of the handle takes
-      if (helper_wave_rule(h)) {
-        if (int rc = check_lds_base(reinterpret_cast<const void*>(duo_kernel_team<T, ROBOT>), lds_checked[2])) return rc;
+      if (helper_wave_rule(h)) {      // two wavefronts per workgroup
         hipLaunchKernelGGL((duo_kernel_team<T, ROBOT>), grid, dim3(128), team_smem, st, sf, si, (const T*)h->snf, (const int*)h->sni, h->M, h->L, N,
                            make_env_params(h), pp, actions, out, mode);
         HIP_TRY(hipGetLastError());
         return 0;
       }
     }
-    hipLaunchKernelGGL(kt, grid, block, team_smem, st, sf, si, (const T*)h->snf, (const int*)h->sni, h->M, h->L, N,
+    hipLaunchKernelGGL((step_kernel_team<T, ROBOT>), grid, dim3(64), team_smem, st, sf, si, (const T*)h->snf, (const int*)h->sni, h->M, h->L, N,
                        make_env_params(h), pp, actions, out, mode);
     HIP_TRY(hipGetLastError());
     return 0;
   }
-  auto kern = step_kernel<T, ROBOT>;
   const int EPB = RowLds<T>::LANES;
   // small workgroups would be packed several to a CU (sharing its LDS pipe and issue slots) while other
   // CUs idle; asking for (almost) the whole LDS forces one workgroup per CU.
   size_t smem = RowLds<T>::bytes(EPB);
   if (h->spread && (N + EPB - 1) / EPB <= 256) smem = RowLds<T>::bytes(sizeof(T) == 8 ? 32 : 64);
-  static bool attr_set[8] = {false, false, false, false, false, false, false, false};
-  int dev = h->device & 7;
-  if (!attr_set[dev]) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)RowLds<T>::bytes(sizeof(T) == 8 ? 32 : 64)));
-    attr_set[dev] = true;
-  }
   dim3 grid((N + EPB - 1) / EPB), block(EPB);
-  hipLaunchKernelGGL(kern, grid, block, smem, st, sf, si, (const T*)h->snf, (const int*)h->sni, h->M, h->L, N,
+  hipLaunchKernelGGL((step_kernel<T, ROBOT>), grid, block, smem, st, sf, si, (const T*)h->snf, (const int*)h->sni, h->M, h->L, N,
                      make_env_params(h), make_phys<T>(h->cfg), actions, out, mode);
   HIP_TRY(hipGetLastError());
   return 0;
 }
 
-// K team-mode steps in one launch (rollout_kernel_team); the caller has checked h->team && !h->sort
+// K team-mode steps in one launch (rollout_kernel_team); the caller has checked step_n_one_launch(h)
 template <typename T, int ROBOT>
 int launch_rollout(solorl_env* h, T* sf, int* si, int N, const float* actions, const Outputs& out, int K, int pol_last, hipStream_t st) {
-  static bool lds_checked = false;
-  if (int rc = check_lds_base(reinterpret_cast<const void*>(rollout_kernel_team<T, ROBOT>), lds_checked)) return rc;
   dim3 grid, block(64);
   RolloutArgs<T> a;
   size_t smem = 0;
@@ -1409,25 +1410,19 @@ int launch_rollout(solorl_env* h, T* sf, int* si, int N, const float* actions, c
 
 // ---- translation-unit split (build time only; solorl_amd/build.py).  The step kernels' phase functions are what takes minutes to
 // compile, once per (arithmetic type, robot): this file is compiled five times in parallel -- SOLO_TU_PART = 0..3 emit ONE
-// launch_step instantiation each (part = 2 * f64 + solo12) behind a hidden C symbol, part 4 the C ABI and every other kernel --
-// or once with SOLO_TU_PART undefined (everything; the -DSOLO_WAVE_TIMING dev build, whose device-side counters must live in one
-// translation unit).  The types below the anonymous namespace are the same source in every part.
+// instantiation of launch_step, launch_rollout and prepare_kernels each (part = 2 * f64 + solo12, part_index) behind hidden C symbols,
+// part 4 the C ABI and every other kernel -- or once with SOLO_TU_PART undefined (everything; the -DSOLO_WAVE_TIMING dev build, whose
+// device-side counters must live in one translation unit).  The types below the anonymous namespace are the same source in every part.
 #define SOLO_LAUNCH_ARGS solorl_env* h, void* sf, int* si, int N, const float* actions, const void* out, int mode, void* st
-extern "C" {
-__attribute__((visibility("hidden"))) int solorl_launch_part0(SOLO_LAUNCH_ARGS);
-__attribute__((visibility("hidden"))) int solorl_launch_part1(SOLO_LAUNCH_ARGS);
-__attribute__((visibility("hidden"))) int solorl_launch_part2(SOLO_LAUNCH_ARGS);
-__attribute__((visibility("hidden"))) int solorl_launch_part3(SOLO_LAUNCH_ARGS);
-}
 // the K-step launch (solorl_step_n / solorl_rollout) of the same instantiation, in the same part
 #define SOLO_ROLLOUT_ARGS solorl_env* h, void* sf, int* si, int N, const float* actions, const void* out, int K, int pol_last, void* st
-extern "C" {
-__attribute__((visibility("hidden"))) int solorl_rollout_part0(SOLO_ROLLOUT_ARGS);
-__attribute__((visibility("hidden"))) int solorl_rollout_part1(SOLO_ROLLOUT_ARGS);
-__attribute__((visibility("hidden"))) int solorl_rollout_part2(SOLO_ROLLOUT_ARGS);
-__attribute__((visibility("hidden"))) int solorl_rollout_part3(SOLO_ROLLOUT_ARGS);
-}
+#define SOLO_DECLARE_PART(K_) \
+  extern "C" __attribute__((visibility("hidden"))) int solorl_prepare_part##K_(const solorl_env* h); \
+  extern "C" __attribute__((visibility("hidden"))) int solorl_launch_part##K_(SOLO_LAUNCH_ARGS); \
+  extern "C" __attribute__((visibility("hidden"))) int solorl_rollout_part##K_(SOLO_ROLLOUT_ARGS);
+SOLO_DECLARE_PART(0) SOLO_DECLARE_PART(1) SOLO_DECLARE_PART(2) SOLO_DECLARE_PART(3)
 #define SOLO_DEFINE_PART(K_, T_, R_) \
+  extern "C" int solorl_prepare_part##K_(const solorl_env* h) { return prepare_kernels<T_, R_>(h); } \
   extern "C" int solorl_launch_part##K_(SOLO_LAUNCH_ARGS) { \
     return launch_step<T_, R_>(h, (T_*)sf, si, N, actions, *(const Outputs*)out, mode, (hipStream_t)st); } \
   extern "C" int solorl_rollout_part##K_(SOLO_ROLLOUT_ARGS) { \
@@ -1449,7 +1444,7 @@ SOLO_DEFINE_PART(3, double, 1)
 namespace {
 
 // The handle's instantiation as tag values: f(T{}) with T = float or double, f(T{}, robot) with decltype(robot)::value = 0 (Solo8) or 1
-// (Solo12) -- for everything but the step kernels, whose instantiations live in the other parts (dispatch_step, dispatch_rollout)
+// (Solo12) -- for everything but the step kernels (part_index)
 template <typename F> auto with_type(const solorl_env* h, F&& f) { return h->f64 ? f(double{}) : f(float{}); }
 template <typename F> auto with_instantiation(const solorl_env* h, F&& f) {
   return with_type(h, [&](auto t) {
@@ -1457,20 +1452,18 @@ template <typename F> auto with_instantiation(const solorl_env* h, F&& f) {
   });
 }
 
+// the step kernels' instantiations live in the other parts: the handle's part, and the three hidden functions of each
+int part_index(const solorl_env* h) { return 2 * (h->f64 ? 1 : 0) + (h->cfg.robot == SOLORL_ROBOT_SOLO12 ? 1 : 0); }
+constexpr decltype(&solorl_launch_part0) PART_LAUNCH[4] = {solorl_launch_part0, solorl_launch_part1, solorl_launch_part2, solorl_launch_part3};
+constexpr decltype(&solorl_rollout_part0) PART_ROLLOUT[4] = {solorl_rollout_part0, solorl_rollout_part1, solorl_rollout_part2, solorl_rollout_part3};
+constexpr decltype(&solorl_prepare_part0) PART_PREPARE[4] = {solorl_prepare_part0, solorl_prepare_part1, solorl_prepare_part2, solorl_prepare_part3};
+
 int dispatch_step(solorl_env* h, void* sf, int* si, int N, const float* actions, const Outputs& out, int mode, hipStream_t st) {
-  const bool s12 = h->cfg.robot == SOLORL_ROBOT_SOLO12;
-  if (!h->f64) return s12 ? solorl_launch_part1(h, sf, si, N, actions, &out, mode, st) : solorl_launch_part0(h, sf, si, N, actions, &out, mode, st);
-  return s12 ? solorl_launch_part3(h, sf, si, N, actions, &out, mode, st) : solorl_launch_part2(h, sf, si, N, actions, &out, mode, st);
+  return PART_LAUNCH[part_index(h)](h, sf, si, N, actions, &out, mode, st);
 }
 
-// solorl_step_n / solorl_rollout take one launch exactly where solorl_step is one team-mode launch on a fixed state buffer
-bool step_n_one_launch(const solorl_env* h) { return h->team && !h->sort; }
-
 int dispatch_rollout(solorl_env* h, const float* actions, const Outputs& out, int K, int pol_last, hipStream_t st) {
-  const bool s12 = h->cfg.robot == SOLORL_ROBOT_SOLO12;
-  void* sf = h->sf; int* si = h->si; const int N = h->N;
-  if (!h->f64) return s12 ? solorl_rollout_part1(h, sf, si, N, actions, &out, K, pol_last, st) : solorl_rollout_part0(h, sf, si, N, actions, &out, K, pol_last, st);
-  return s12 ? solorl_rollout_part3(h, sf, si, N, actions, &out, K, pol_last, st) : solorl_rollout_part2(h, sf, si, N, actions, &out, K, pol_last, st);
+  return PART_ROLLOUT[part_index(h)](h, h->sf, h->si, h->N, actions, &out, K, pol_last, st);
 }
 
 Outputs make_outputs(float* obs_out, float* reward_out, uint8_t* done_out, const solorl_info_soa* info) {
@@ -1489,7 +1482,7 @@ Outputs make_outputs(float* obs_out, float* reward_out, uint8_t* done_out, const
 int check_policy_tail(const solorl_env* h, const solorl_policy_params* p, const char* who) {
   const std::string w(who);
   if (h->f64 || !h->team || h->sort) return fail(SOLORL_ERR_INVALID, w + " needs the fp32 team-mode engine without contact-count sorting (the defaults)");
-  if (p->hidden != 64 || p->obs_dim != h->O || p->act_dim != h->n || (h->O & 3) || h->O > 88)
+  if (p->hidden != 64 || p->obs_dim != h->O || p->act_dim != h->n || (h->O & 3) || h->O > 88 || h->L.H > 1)     // (step_team copies history levels 0 and 1 to LDS)
     return fail(SOLORL_ERR_INVALID, w + ": the policy must be the MLP of hidden size 64 on this env's observation / action sizes, obs_dim a multiple of 4 "
                                         "and at most 88 (zero or one history level)");
   const void* ptrs[] = {p->critic_w0, p->critic_b0, p->critic_w1, p->critic_b1, p->critic_w2, p->critic_b2, p->actor_w0, p->actor_b0, p->actor_w1, p->actor_b1,
@@ -1497,6 +1490,14 @@ int check_policy_tail(const solorl_env* h, const solorl_policy_params* p, const 
   for (const void* q : ptrs) if (!q) return fail(SOLORL_ERR_INVALID, w + ": null policy parameter pointer");
   const void* vec[] = {p->critic_w0, p->critic_w1, p->critic_w2, p->actor_w0, p->actor_w1, p->mean_w};
   for (const void* q : vec) if (reinterpret_cast<uintptr_t>(q) & 15u) return fail(SOLORL_ERR_INVALID, w + ": weight matrices must be 16-byte aligned (rows are read as float4)");
+  return 0;
+}
+
+// what every step entry point asks after its own checks, in this order (tests pin which message wins)
+int step_ready(const solorl_env* h, const float* actions, const float* obs_out, const float* reward_out, const uint8_t* done_out) {
+  if (!h->reset_called) return fail(SOLORL_ERR_STATE, "env.reset() must be called before step");   // baseEnv.py:43
+  if (!actions || !obs_out || !reward_out || !done_out) return fail(SOLORL_ERR_INVALID, "null array argument");
+  HIP_TRY(hipSetDevice(h->device));
   return 0;
 }
 
@@ -1683,12 +1684,9 @@ int solorl_create(const solorl_config* cfg, int num_envs, int device_id, uint64_
   h->M = (cfg->settle_max - cfg->settle_min + 1) * (cfg->use_treadmill ? 2 : 1);
   h->goal_radius = cfg->goal_radius;
   {
-    // envs per wavefront.  Measured on MI355X (profiles/r01_notes.md): narrower waves do NOT help -- the
-    // kernel's duration is the sequential PGS sweep of the heaviest env, which a narrower wave
-    // still has to run, while more waves contend for the LDS/TA pipes -- so waves are kept full.
-    int epw = 64;
-    if (const char* ev = getenv("SOLORL_ENVS_PER_WAVE")) { int v = atoi(ev); if (v >= 1 && v <= 64) epw = v; }
-    if (h->f64 && epw > 32) epw = 32;
+    // Lane mode's waves are kept full (RowLds<T>::LANES envs each).  Measured on MI355X (profiles/r01_notes.md): narrower waves do NOT
+    // help -- the kernel's duration is the sequential PGS sweep of the heaviest env, which a narrower wave still has to run, while
+    // more waves contend for the LDS/TA pipes.
     if (const char* ev = getenv("SOLORL_SPREAD")) h->spread = atoi(ev) != 0;
     h->team = true;   // measured (tools/dev/bench_n.py): team mode wins at every batch size, 1k .. 262k envs; lane mode: SOLORL_TEAM=0
     if (const char* ev = getenv("SOLORL_TEAM")) h->team = atoi(ev) != 0;
@@ -1696,7 +1694,6 @@ int solorl_create(const solorl_config* cfg, int num_envs, int device_id, uint64_
     if (const char* ev = getenv("SOLORL_HELPER_WAVE")) h->helper_override = atoi(ev) != 0;
     { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device_id) == hipSuccess && prop.multiProcessorCount > 0) h->simds = 4 * prop.multiProcessorCount; }
     if (const char* ev = getenv("SOLORL_POISON_LDS")) { h->lds_poison_on = 1; h->lds_poison = (unsigned)strtoul(ev, nullptr, 0); }
-    h->epw = epw;
   }
   auto cleanup = [&](int code) { solorl_destroy(h); return code; };
   const size_t Np = ((size_t)num_envs + 3) & ~(size_t)3, Mp = ((size_t)h->M + 3) & ~(size_t)3;      // slot groups of 4 (SX)
@@ -1730,6 +1727,7 @@ int solorl_create(const solorl_config* cfg, int num_envs, int device_id, uint64_
     if (hipMalloc(&h->si2, sizeof(int) * NI * Np) != hipSuccess) return cleanup(fail(SOLORL_ERR_HIP, "hipMalloc istate2"));
     if (hipMalloc(&h->perm, sizeof(int) * (size_t)num_envs) != hipSuccess) return cleanup(fail(SOLORL_ERR_HIP, "hipMalloc perm"));
   }
+  if ((rc = PART_PREPARE[part_index(h)](h))) return cleanup(rc);
   rc = with_type(h, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(init_pose_kernel<T>, dim3((num_envs + 255) / 256), dim3(256), 0, 0, (T*)h->sf, h->si, h->L, num_envs, T(0));
@@ -1772,10 +1770,7 @@ int solorl_get_property(const solorl_env* h, const char* name, double* value) {
   else if (n == "sweep_variant") {
     if (h->cfg.solver_residual_threshold > 0) *value = 2;
     else if (!h->team) *value = 1;          // (lane mode: one software-pipelined row loop)
-    else {
-      const int grid = (((h->N + 3) / 4) + 7) & ~7;
-      *value = h->pipe_override >= 0 ? h->pipe_override : (grid <= h->simds ? 1 : 0);
-    }
+    else *value = team_pipe(h, h->N) ? 1 : 0;
   } else if (n == "max_contacts") *value = MAX_CONTACTS;
   else if (n == "max_limit_rows") *value = MAX_LIMITS;
   else if (n == "f64") *value = h->f64 ? 1 : 0;
@@ -1796,9 +1791,7 @@ int solorl_reset(solorl_env* h, float* obs_out, void* stream) {
 int solorl_step(solorl_env* h, const float* actions, float* obs_out, float* reward_out, uint8_t* done_out,
                 const solorl_info_soa* info, void* stream) {
   if (!h) return fail(SOLORL_ERR_INVALID, "null handle");
-  if (!h->reset_called) return fail(SOLORL_ERR_STATE, "env.reset() must be called before step");   // baseEnv.py:43
-  if (!actions || !obs_out || !reward_out || !done_out) return fail(SOLORL_ERR_INVALID, "null array argument");
-  HIP_TRY(hipSetDevice(h->device));
+  if (int rc = step_ready(h, actions, obs_out, reward_out, done_out)) return rc;
   Outputs o = make_outputs(obs_out, reward_out, done_out, info);
   if (h->sort) {   // re-sort the state by last contact count (stable), into the spare buffer
     hipStream_t st = (hipStream_t)stream;
@@ -1819,9 +1812,7 @@ int solorl_step_act(solorl_env* h, const float* actions, float* obs_out, float* 
   if (!h) return fail(SOLORL_ERR_INVALID, "null handle");
   if (!p || !value_out || !action_out || !logp_out) return fail(SOLORL_ERR_INVALID, "solorl_step_act: null policy argument");
   if (int rc = check_policy_tail(h, p, "solorl_step_act")) return rc;
-  if (!h->reset_called) return fail(SOLORL_ERR_STATE, "env.reset() must be called before step");
-  if (!actions || !obs_out || !reward_out || !done_out) return fail(SOLORL_ERR_INVALID, "null array argument");
-  HIP_TRY(hipSetDevice(h->device));
+  if (int rc = step_ready(h, actions, obs_out, reward_out, done_out)) return rc;
   Outputs o = make_outputs(obs_out, reward_out, done_out, info);
   o.pol = make_policy_tail(p, noise, value_out, action_out, logp_out);
   return dispatch_step(h, h->sf, h->si, h->N, actions, o, MODE_STEP, (hipStream_t)stream);
@@ -1842,8 +1833,7 @@ int solorl_step_n(solorl_env* h, int K, const float* actions, float* obs_out, fl
                   void* stream) {
   if (K < 1) return fail(SOLORL_ERR_INVALID, "solorl_step_n: K must be >= 1");
   if (!h) return fail(SOLORL_ERR_INVALID, "null handle");
-  if (!h->reset_called) return fail(SOLORL_ERR_STATE, "env.reset() must be called before step");
-  if (!actions || !obs_out || !reward_out || !done_out) return fail(SOLORL_ERR_INVALID, "null array argument");
+  if (int rc = step_ready(h, actions, obs_out, reward_out, done_out)) return rc;
   if (!step_n_one_launch(h)) {
     // lane mode and contact-count sorting have no K-step kernel: K ordinary steps, the same results by construction
     const size_t N = (size_t)h->N, O = (size_t)h->O, A = (size_t)h->n;
@@ -1855,7 +1845,6 @@ int solorl_step_n(solorl_env* h, int K, const float* actions, float* obs_out, fl
     }
     return 0;
   }
-  HIP_TRY(hipSetDevice(h->device));
   // (K = 1: the one-step kernel itself, so that a one-step call is solorl_step exactly)
   if (K == 1) return dispatch_step(h, h->sf, h->si, h->N, actions, make_outputs(obs_out, reward_out, done_out, info), MODE_STEP, (hipStream_t)stream);
   return dispatch_rollout(h, actions, make_outputs(obs_out, reward_out, done_out, info), K, 0, (hipStream_t)stream);
@@ -1867,9 +1856,7 @@ int solorl_rollout(solorl_env* h, int K, float* actions, float* obs_out, float* 
   if (!h) return fail(SOLORL_ERR_INVALID, "null handle");
   if (!p || !value_out || !logp_out) return fail(SOLORL_ERR_INVALID, "solorl_rollout: null policy argument");
   if (int rc = check_policy_tail(h, p, "solorl_rollout")) return rc;
-  if (!h->reset_called) return fail(SOLORL_ERR_STATE, "env.reset() must be called before step");
-  if (!actions || !obs_out || !reward_out || !done_out) return fail(SOLORL_ERR_INVALID, "null array argument");
-  HIP_TRY(hipSetDevice(h->device));
+  if (int rc = step_ready(h, actions, obs_out, reward_out, done_out)) return rc;
   Outputs o = make_outputs(obs_out, reward_out, done_out, info);
   o.pol = make_policy_tail(p, noise, value_out, actions, logp_out);
   if (K == 1) {              // = solorl_step_act (policy after the step) or solorl_step, as in solorl_step_n

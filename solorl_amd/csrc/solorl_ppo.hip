@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <mutex>
 #include <type_traits>
 #include <utility>
 
@@ -804,15 +805,26 @@ __global__ void __launch_bounds__(1024) ppo_clip_adam_kernel(const AdamArgs K) {
 }
 
 // observation widths of zero or one history level (14 + 2 n (+ 4 pointGoal), x 1 or x 2), action widths n = 8 / 12
-template <typename F> int dispatch_dims(int O, int A, F&& f) {
-#define SOLO_DIMS(O_, A_) if (O == O_ && A == A_) return f(std::integral_constant<int, O_>(), std::integral_constant<int, A_>());
-  SOLO_DIMS(76, 12) SOLO_DIMS(84, 12) SOLO_DIMS(38, 12) SOLO_DIMS(42, 12)
-  SOLO_DIMS(60, 8) SOLO_DIMS(68, 8) SOLO_DIMS(30, 8) SOLO_DIMS(34, 8)
+#define SOLO_DIMS_LIST(X) X(76, 12) X(84, 12) X(38, 12) X(42, 12) X(60, 8) X(68, 8) X(30, 8) X(34, 8)
+bool dims_supported(int O, int A) {
+#define SOLO_DIMS(O_, A_) if (O == O_ && A == A_) return true;
+  SOLO_DIMS_LIST(SOLO_DIMS)
 #undef SOLO_DIMS
+  return false;
+}
+int fail_dims() {
   return solorl_fail_(SOLORL_ERR_INVALID, "policy kernels are built for the observation / action sizes of zero or one history level "
                                           "(38, 42, 76 or 84 x 12; 30, 34, 60 or 68 x 8); use the PyTorch path for other shapes");
 }
+template <typename F> int dispatch_dims(int O, int A, F&& f) {
+#define SOLO_DIMS(O_, A_) if (O == O_ && A == A_) return f(std::integral_constant<int, O_>(), std::integral_constant<int, A_>());
+  SOLO_DIMS_LIST(SOLO_DIMS)
+#undef SOLO_DIMS
+  return fail_dims();
+}
 
+// every policy entry point: the parameters, the shape (stage 2's kernel is not reached through dispatch_dims and computes only the tile
+// counts it instantiates), then the device -- so an unsupported shape is refused on a machine without a GPU too
 int check_policy(const solorl_policy_params* p, int device_id) {
   if (!p) return solorl_fail_(SOLORL_ERR_INVALID, "null policy parameters");
   if (p->hidden != H) return solorl_fail_(SOLORL_ERR_INVALID, "policy kernels are built for hidden size 64");
@@ -823,10 +835,25 @@ int check_policy(const solorl_policy_params* p, int device_id) {
   // boundary (torch allocations do; an offset view passed by another C-ABI caller would fault on the GPU instead)
   const void* vec[] = {p->critic_w1, p->actor_w1, p->critic_w2, p->mean_w, p->obs_dim % 4 == 0 ? p->critic_w0 : nullptr, p->obs_dim % 4 == 0 ? p->actor_w0 : nullptr};
   for (const void* q : vec) if (reinterpret_cast<uintptr_t>(q) & 15u) return solorl_fail_(SOLORL_ERR_INVALID, "policy weight matrices must be 16-byte aligned (rows are read as float4)");
+  if (!dims_supported(p->obs_dim, p->act_dim)) return fail_dims();
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return solorl_fail_(SOLORL_ERR_NODEVICE, "no HIP device available (no CPU fallback)");
   if (device_id < 0 || device_id >= ndev) return solorl_fail_(SOLORL_ERR_NODEVICE, "device_id out of range");
   if (hipSetDevice(device_id) != hipSuccess) return solorl_fail_(SOLORL_ERR_HIP, "hipSetDevice");
+  return 0;
+}
+
+// Stage 1 takes more than the 64 KB of dynamic LDS a kernel gets by default: the limit is raised once per (instantiation, device)
+template <int O, int A> int stage1_raise_lds_limit(int device_id) {
+  static std::mutex mu;
+  static bool raised[64] = {};
+  if (device_id < 0 || device_id >= 64) return solorl_fail_(SOLORL_ERR_NODEVICE, "ppo_grad_stage1_mfma_kernel: device_id beyond the 64 the library tracks");
+  std::lock_guard<std::mutex> lock(mu);
+  if (raised[device_id]) return 0;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_grad_stage1_mfma_kernel<O, A>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          stage1_lds_bytes<O, A>()) != hipSuccess)
+    return solorl_fail_(SOLORL_ERR_HIP, "ppo_grad_stage1_mfma_kernel: cannot raise the dynamic LDS limit");
+  raised[device_id] = true;
   return 0;
 }
 
@@ -866,12 +893,7 @@ int solorl_ppo_grad_stage1(const solorl_policy_params* p, const solorl_ppo_batch
   return dispatch_dims(P.obs_dim, P.act_dim, [&](auto oc, auto ac) {
     constexpr int O = decltype(oc)::value, A = decltype(ac)::value;
     constexpr int LDS = stage1_lds_bytes<O, A>();
-    static bool lds_ok[64] = {};             // (more than the 64 KB a kernel gets by default: raised once per instantiation and device)
-    if (!lds_ok[device_id & 63]) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_grad_stage1_mfma_kernel<O, A>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-        return solorl_fail_(SOLORL_ERR_HIP, "ppo_grad_stage1_mfma_kernel: cannot raise the dynamic LDS limit");
-      lds_ok[device_id & 63] = true;
-    }
+    if (int rc = stage1_raise_lds_limit<O, A>(device_id)) return rc;
     hipLaunchKernelGGL((ppo_grad_stage1_mfma_kernel<O, A>), dim3((B.m + 127) / 128, 2), dim3(256), LDS, (hipStream_t)stream, CRITIC_PASS, ACTOR_PASS, B, W);
     return hipGetLastError() == hipSuccess ? 0 : solorl_fail_(SOLORL_ERR_HIP, "ppo_grad_stage1_mfma_kernel launch");
   });

@@ -75,16 +75,13 @@ class VecNormalizer:
             s = self._scratch[(rows, D)] = torch.empty(k, dtype=torch.float64, device=self.device)
         return s
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def obs(self, x, rows, update, out=None):
         """x: contiguous float32 [rows, n, D] (or [n, D] with rows = 1) on the device, normalised in place (or into ``out``)"""
         out = x if out is None else out
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_normalize_obs(C.c_void_p(self.ob_stats.data_ptr()), rows, self.n, self.D, C.c_void_p(x.data_ptr()),
                                                       C.c_void_p(out.data_ptr()), 1 if update else 0, self.clipob, self.epsilon,
-                                                      C.c_void_p(self.scratch(rows, self.D).data_ptr()), self.device.index or 0, self._stream()))
+                                                      C.c_void_p(self.scratch(rows, self.D).data_ptr()), self.device.index or 0, _native.stream(self.device)))
         return out
 
     def rewards(self, r, done, rows, update):
@@ -96,5 +93,5 @@ class VecNormalizer:
             _native.check(self.L.solorl_normalize_rewards(C.c_void_p(self.ret_stats.data_ptr()), C.c_void_p(self.ret.data_ptr()), rows, self.n,
                                                           C.c_void_p(r.data_ptr()), C.c_void_p(done.data_ptr()), 1 if update else 0, self.gamma,
                                                           self.cliprew, self.epsilon, C.c_void_p(self.scratch(rows, 1).data_ptr()),
-                                                          self.device.index or 0, self._stream()))
+                                                          self.device.index or 0, _native.stream(self.device)))
         return r

@@ -28,7 +28,7 @@ class _FusedPPOLoss(torch.autograd.Function):
         with torch.cuda.device(dev):
             _native.check(_native.lib().solorl_ppo_loss(p(mean_), p(logstd_), p(values_), p(action_), p(old_), p(adv_), p(vpred_), p(ret_),
                                                         m, A, float(clip), float(value_coef), int(bool(clipped_value)), p(g_mean), p(g_values),
-                                                        p(part), dev.index or 0, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                                        p(part), dev.index or 0, _native.stream(dev)))
         s = part.sum(0)
         value_loss, action_loss = s[0] / m, s[1] / m
         entropy = (0.5 + _HALF_LOG_2PI + logstd_).mean()
@@ -68,16 +68,22 @@ def policy_kernels_supported(actor_critic):
     return h == 64 and (o, a) in _SUPPORTED and p.is_cuda and p.dtype == torch.float32
 
 
+def _named_parameters(actor_critic):
+    """The MLP's 13 parameters under the member names of solorl_policy_params / solorl_ppo_grads"""
+    b, d = actor_critic.base, actor_critic.pi_dist
+    return {"critic_w0": b.critic[0].weight, "critic_b0": b.critic[0].bias, "critic_w1": b.critic[2].weight, "critic_b1": b.critic[2].bias,
+            "critic_w2": b.critic[4].weight, "critic_b2": b.critic[4].bias, "actor_w0": b.features[0].weight, "actor_b0": b.features[0].bias,
+            "actor_w1": b.features[2].weight, "actor_b1": b.features[2].bias, "mean_w": d.mean.weight, "mean_b": d.mean.bias,
+            "logstd": d.logstd}
+
+
 def policy_params(actor_critic):
     """solorl_policy_params over the module's own parameter storage (PyTorch layout is the kernels' layout: no copies).
     The pointers stay valid as long as the parameters are updated in place (optimizers do)."""
     b, d = actor_critic.base, actor_critic.pi_dist
     P = _native.PolicyParams()
     P.obs_dim, P.hidden, P.act_dim = b.features[0].in_features, b.features[0].out_features, d.mean.out_features
-    named = {"critic_w0": b.critic[0].weight, "critic_b0": b.critic[0].bias, "critic_w1": b.critic[2].weight, "critic_b1": b.critic[2].bias,
-             "critic_w2": b.critic[4].weight, "critic_b2": b.critic[4].bias, "actor_w0": b.features[0].weight, "actor_b0": b.features[0].bias,
-             "actor_w1": b.features[2].weight, "actor_b1": b.features[2].bias, "mean_w": d.mean.weight, "mean_b": d.mean.bias,
-             "logstd": d.logstd}
+    named = _named_parameters(actor_critic)
     for k, t in named.items():
         assert t.is_contiguous() and t.dtype == torch.float32 and t.is_cuda
         setattr(P, k, t.data_ptr())
@@ -94,10 +100,6 @@ def check_params(P):
             raise RuntimeError("policy parameter %s moved since solorl_policy_params was built; rebuild it (and any HIP graph)" % k)
 
 
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def policy_act(params, obs, noise, value_out, action_out, logp_out):
     """Policy.act (agents/ppo/policy.py:33-49) in one launch: value_out [N,1], action_out [N,A] = mean + exp(logstd) * noise
     (noise [N,A] standard normal, or None for the deterministic action), logp_out [N,1]."""
@@ -110,7 +112,7 @@ def policy_act(params, obs, noise, value_out, action_out, logp_out):
     with torch.cuda.device(dev):
         _native.check(_native.lib().solorl_policy_act(C.byref(params), C.c_void_p(obs.data_ptr()),
                                                       C.c_void_p(0 if noise is None else noise.data_ptr()), n, C.c_void_p(value_out.data_ptr()),
-                                                      C.c_void_p(action_out.data_ptr()), C.c_void_p(logp_out.data_ptr()), dev.index or 0, _stream(dev)))
+                                                      C.c_void_p(action_out.data_ptr()), C.c_void_p(logp_out.data_ptr()), dev.index or 0, _native.stream(dev)))
 
 
 class MiniBatchGrad:
@@ -146,17 +148,12 @@ class MiniBatchGrad:
         W = self.W = _native.PpoStage1()
         for k, t in self.buf.items():
             setattr(W, k, t.data_ptr())
-        b, d = actor_critic.base, actor_critic.pi_dist
         self.psum = torch.zeros(3 + A, device=dev)          # running sums of the partials over the steps of an update
         self.ent = torch.zeros(1, device=dev)               # running sum of sum_a logstd_a
         L = _native.lib()
         self.scratch = torch.zeros(L.solorl_ppo_scratch_count(O, A, m), device=dev)
         G = self.G = _native.PpoGrads()
-        grads = {"critic_w0": b.critic[0].weight, "critic_b0": b.critic[0].bias, "critic_w1": b.critic[2].weight, "critic_b1": b.critic[2].bias,
-                 "critic_w2": b.critic[4].weight, "critic_b2": b.critic[4].bias, "actor_w0": b.features[0].weight, "actor_b0": b.features[0].bias,
-                 "actor_w1": b.features[2].weight, "actor_b1": b.features[2].bias, "mean_w": d.mean.weight, "mean_b": d.mean.bias,
-                 "logstd": d.logstd}
-        for k, prm in grads.items():
+        for k, prm in _named_parameters(actor_critic).items():
             g = prm.grad
             assert g is not None and g.is_contiguous() and g.shape == prm.shape, "parameters need dense .grad tensors (FlatGradBucket)"
             setattr(G, k, g.data_ptr())
@@ -167,7 +164,7 @@ class MiniBatchGrad:
         dev = self.psum.device
         L = _native.lib()
         with torch.cuda.device(dev):
-            st = _stream(dev)
+            st = _native.stream(dev)
             _native.check(L.solorl_ppo_grad_stage1(C.byref(self.P), C.byref(self.B), C.byref(self.W), dev.index or 0, st))
             _native.check(L.solorl_ppo_grad_stage2(C.byref(self.P), C.byref(self.W), self.m, C.byref(self.G), dev.index or 0, st))
 
@@ -206,7 +203,7 @@ class ClipAdam:
 
     def __call__(self):
         with torch.cuda.device(self.dev):
-            _native.check(_native.lib().solorl_ppo_clip_adam(C.byref(self.P), C.byref(self.G), C.byref(self.S), self.dev.index or 0, _stream(self.dev)))
+            _native.check(_native.lib().solorl_ppo_clip_adam(C.byref(self.P), C.byref(self.G), C.byref(self.S), self.dev.index or 0, _native.stream(self.dev)))
 
     def zero_state(self):
         self.exp_avg.zero_(); self.exp_avg_sq.zero_(); self.step.zero_()

@@ -16,6 +16,8 @@ gradient all-reduce between them when world > 1).
 
 Both fall back to nothing: they are only constructed for CUDA devices; train() uses them unless
 --no-hip-graphs is given."""
+import os
+
 import torch
 import torch.nn as nn
 
@@ -26,7 +28,6 @@ from .ppo import PPO
 
 def _kernels_enabled():
     """SOLORL_PPO_KERNELS=0 keeps the rollout's act and the mini-batch step on their PyTorch paths (A/B runs)."""
-    import os
     return os.environ.get("SOLORL_PPO_KERNELS", "1") != "0"
 
 
@@ -102,7 +103,6 @@ class GraphedRollout:
         self.envs, self.ac, self.storage, self.T = envs, actor_critic, storage, num_steps
         # chunk = K > 0: the rollout as ceil(T / K) windows of K closed-loop steps, ONE launch each (solorl_rollout: no wavefront waits
         # for another between the steps of a window), where the handle supports it.  Default SOLORL_ROLLOUT_CHUNK, 0 = one launch per step.
-        import os
         self.chunk = int(os.environ.get("SOLORL_ROLLOUT_CHUNK", "0")) if chunk is None else int(chunk)
         self.windows = None          # the window lengths the captured body used (None: not chunked)
         self.graph = None
@@ -122,7 +122,6 @@ class GraphedRollout:
         # ONE launch per rollout step where the engine supports it (solorl_step_act: each wavefront of the step kernel evaluates the policy
         # on the observations it has just produced, in the time it would otherwise idle until the slowest wavefront ends); the first
         # step's action still needs its own policy launch.  SOLORL_STEP_ACT=0 keeps the two-launch form (A/B runs).
-        import os
         self.step_act = bool(fused and os.environ.get("SOLORL_STEP_ACT", "1") != "0" and hasattr(self.envs, "step_act_supported")
                              and self.envs.step_act_supported(self._pp))
         if fused and self.chunk > 0 and hasattr(self.envs, "rollout_supported") and self.envs.rollout_supported(self._pp):
@@ -315,7 +314,6 @@ class GraphedPPO(PPO):
         """Whether the bucket all-reduce goes INSIDE the captured mini-batch step.  Opt-in (SOLORL_CAPTURE_ALLREDUCE=1) until a real
         multi-GPU run has exercised it: no box of this project has had two GPUs, so the split form (graph -> eager all-reduce -> graph)
         stays the default and `allreduce_in_graph` is recorded with every result."""
-        import os
         want = D.backend() == "nccl" and os.environ.get("SOLORL_CAPTURE_ALLREDUCE", "0") == "1" and os.environ.get("SOLORL_SPLIT_ALLREDUCE", "0") == "0"
         if not want:
             return False

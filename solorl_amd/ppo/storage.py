@@ -51,7 +51,7 @@ class RolloutStorage:
                     C.c_void_p(self.rewards.data_ptr()), C.c_void_p(self.value_preds.data_ptr()),
                     C.c_void_p(self.masks.data_ptr()), C.c_void_p(nv.data_ptr()), C.c_void_p(self.returns.data_ptr()),
                     T, self.num_agents, int(bool(use_gae)), float(gamma), float(gae_lambda), dev.index or 0,
-                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                    _native.stream(dev)))
             return
         if use_gae:
             self.value_preds[-1].copy_(next_value)

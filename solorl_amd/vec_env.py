@@ -207,7 +207,7 @@ class SoloVecEnv:
                                       "(step_act_supported() / rollout_supported() are False)" % name)
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _native.stream(self.device)
 
     def reset(self):
         with torch.cuda.device(self.device):
@@ -233,28 +233,34 @@ class SoloVecEnv:
         t["done"] = self._done.clone()
         return self._obs.clone(), self._rew.clone().unsqueeze(-1), t["done"].float(), LazyInfos(t, t["done"])
 
-    def _raw(self, name, x, shape):
-        """The C ABI takes raw pointers: `x` must already be float32, contiguous, of `shape`, on this env's device."""
-        if not (x.is_cuda and x.device == self.device and x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape) == shape):
-            raise AssertionError("%s must be a contiguous float32 %s tensor on %s, got %s %s on %s" % (
-                name, list(shape), self.device, x.dtype, tuple(x.shape), x.device))
+    def _raw(self, name, x, *shapes, dtype=torch.float32):
+        """The C ABI takes raw pointers: `x` must already be `dtype`, contiguous, of one of `shapes`, on this env's device."""
+        if not (x.is_cuda and x.device == self.device and x.dtype == dtype and x.is_contiguous() and tuple(x.shape) in shapes):
+            raise AssertionError("%s must be a contiguous %s %s tensor on %s, got %s %s on %s" % (
+                name, str(dtype).replace("torch.", ""), " or ".join(str(list(sh)) for sh in shapes), self.device, x.dtype, tuple(x.shape), x.device))
         return C.c_void_p(x.data_ptr())
+
+    def _per_env(self, name, x, lead):
+        """one float per env and row (rewards, values, log-probs): [.., N] or [.., N, 1]"""
+        return self._raw(name, x, lead + (self.nenvs,), lead + (self.nenvs, 1))
+
+    def _outputs(self, lead, own, obs_out, rew_out, done_out):
+        """Output tensors of a step call with leading shape `lead` = () or (K,): the caller's, or the engine-owned defaults `own` =
+        (obs, rew, done) -> (o, r, d, and their checked pointers): observations lead + [N, O], rewards lead + [N] or [N, 1], done
+        flags uint8 lead + [N]."""
+        o, r, d = (own[i] if x is None else x for i, x in enumerate((obs_out, rew_out, done_out)))
+        return (o, r, d, self._raw("obs_out", o, lead + (self.nenvs, self.obs_dim)), self._per_env("rew_out", r, lead),
+                self._raw("done_out", d, lead + (self.nenvs,), dtype=torch.uint8))
 
     def step_inplace(self, actions, obs_out=None, rew_out=None, done_out=None):
         """Zero-copy variant for rollout loops: returns views of the engine-owned output buffers (overwritten by the next
         step) -- or writes observations [N, O] / rewards [N] or [N, 1] / done flags (uint8 [N]) straight into caller-owned tensors
         such as rollout-storage rows (the C ABI takes the caller's pointers anyway).  Host-side checks only, capturable in a HIP graph."""
         a = self._raw("actions", actions, (self.nenvs, self.act_dim))
-        o = self._obs if obs_out is None else obs_out
-        r = self._rew if rew_out is None else rew_out
-        po = self._raw("obs_out", o, (self.nenvs, self.obs_dim))
-        pr = self._raw("rew_out", r, tuple(r.shape) if tuple(r.shape) in ((self.nenvs,), (self.nenvs, 1)) else (self.nenvs,))
-        d = self._done if done_out is None else done_out
-        if not (d.is_cuda and d.device == self.device and d.dtype == torch.uint8 and d.is_contiguous() and tuple(d.shape) == (self.nenvs,)):
-            raise AssertionError("done_out must be a contiguous uint8 [%d] tensor on %s" % (self.nenvs, self.device))
+        o, r, d, po, pr, pd = self._outputs((), (self._obs, self._rew, self._done), obs_out, rew_out, done_out)
         self._steps_issued += 1
         with torch.cuda.device(self.device):
-            _native.check(self.L.solorl_step(self._h, a, po, pr, C.c_void_p(d.data_ptr()), C.byref(self._info_c), self._stream()))
+            _native.check(self.L.solorl_step(self._h, a, po, pr, pd, C.byref(self._info_c), self._stream()))
         if self._norm is not None:
             self._normalize(o, r, d, 1)
         return o, r, d, self._info
@@ -272,21 +278,14 @@ class SoloVecEnv:
         mean + exp(logstd) * noise (noise [N,A] or None), logp_out [N] or [N,1] -- e.g. the NEXT step's rollout-storage rows."""
         self._no_policy_tail("step_act_inplace")
         a = self._raw("actions", actions, (self.nenvs, self.act_dim))
-        o = self._obs if obs_out is None else obs_out
-        r = self._rew if rew_out is None else rew_out
-        po = self._raw("obs_out", o, (self.nenvs, self.obs_dim))
-        pr = self._raw("rew_out", r, tuple(r.shape) if tuple(r.shape) in ((self.nenvs,), (self.nenvs, 1)) else (self.nenvs,))
-        d = self._done if done_out is None else done_out
-        if not (d.is_cuda and d.device == self.device and d.dtype == torch.uint8 and d.is_contiguous() and tuple(d.shape) == (self.nenvs,)):
-            raise AssertionError("done_out must be a contiguous uint8 [%d] tensor on %s" % (self.nenvs, self.device))
-        pv = self._raw("value_out", value_out, tuple(value_out.shape) if tuple(value_out.shape) in ((self.nenvs,), (self.nenvs, 1)) else (self.nenvs,))
+        o, r, d, po, pr, pd = self._outputs((), (self._obs, self._rew, self._done), obs_out, rew_out, done_out)
+        pv = self._per_env("value_out", value_out, ())
         pa = self._raw("action_out", action_out, (self.nenvs, self.act_dim))
-        pl = self._raw("logp_out", logp_out, tuple(logp_out.shape) if tuple(logp_out.shape) in ((self.nenvs,), (self.nenvs, 1)) else (self.nenvs,))
+        pl = self._per_env("logp_out", logp_out, ())
         pn = C.c_void_p(0) if noise is None else self._raw("noise", noise, (self.nenvs, self.act_dim))
         self._steps_issued += 1
         with torch.cuda.device(self.device):
-            _native.check(self.L.solorl_step_act(self._h, a, po, pr, C.c_void_p(d.data_ptr()), C.byref(self._info_c), C.byref(params), pn, pv, pa, pl,
-                                                 self._stream()))
+            _native.check(self.L.solorl_step_act(self._h, a, po, pr, pd, C.byref(self._info_c), C.byref(params), pn, pv, pa, pl, self._stream()))
         if self._norm_ret:
             self._normalize(o, r, d, 1)
         return o, r, d, self._info
@@ -313,14 +312,7 @@ class SoloVecEnv:
             kw = dict(device=self.device)
             b.update(obs=torch.empty((K, self.nenvs, self.obs_dim), dtype=torch.float32, **kw), rew=torch.empty((K, self.nenvs), dtype=torch.float32, **kw),
                      done=torch.empty((K, self.nenvs), dtype=torch.uint8, **kw))
-        o = b["obs"] if obs_out is None else obs_out
-        r = b["rew"] if rew_out is None else rew_out
-        d = b["done"] if done_out is None else done_out
-        po = self._raw("obs_out", o, (K, self.nenvs, self.obs_dim))
-        pr = self._raw("rew_out", r, tuple(r.shape) if tuple(r.shape) in ((K, self.nenvs), (K, self.nenvs, 1)) else (K, self.nenvs))
-        if not (d.is_cuda and d.device == self.device and d.dtype == torch.uint8 and d.is_contiguous() and tuple(d.shape) == (K, self.nenvs)):
-            raise AssertionError("done_out must be a contiguous uint8 [%d, %d] tensor on %s" % (K, self.nenvs, self.device))
-        return o, r, d, po, pr, C.c_void_p(d.data_ptr())
+        return self._outputs((K,), (b["obs"], b.get("rew"), b.get("done")), obs_out, rew_out, done_out)
 
     def step_n(self, actions):
         """K control steps (include/solorl.h solorl_step_n; one launch where get_property("step_n_one_launch") is 1): actions [K, N, A]
@@ -367,8 +359,7 @@ class SoloVecEnv:
             raise AssertionError("actions must be [K%s, %d, %d] with K >= 1" % (" + 1" if pal else "", self.nenvs, self.act_dim))
         pa = self._raw("actions", actions, (R, self.nenvs, self.act_dim))
         pn = C.c_void_p(0) if noise is None else self._raw("noise", noise, (R, self.nenvs, self.act_dim))
-        pv = self._raw("value_out", value_out, tuple(value_out.shape) if tuple(value_out.shape) in ((R, self.nenvs), (R, self.nenvs, 1)) else (R, self.nenvs))
-        pl = self._raw("logp_out", logp_out, tuple(logp_out.shape) if tuple(logp_out.shape) in ((R, self.nenvs), (R, self.nenvs, 1)) else (R, self.nenvs))
+        pv, pl = self._per_env("value_out", value_out, (R,)), self._per_env("logp_out", logp_out, (R,))
         b = self._k_rows(K)
         o, r, d, po, pr, pd = self._rows_out(b, K, obs_out, rew_out, done_out)
         self._steps_issued += K

@@ -88,6 +88,32 @@ def test_policy_kernel_entry_points_reject_bad_arguments(lib):
         assert b"no CPU fallback" in lib.solorl_last_error()
 
 
+@pytest.mark.parametrize("obs_dim,act_dim", [(114, 12), (76, 16)])
+def test_policy_kernel_entry_points_reject_unsupported_shapes(lib, obs_dim, act_dim):
+    """Every policy entry point refuses an observation / action size its kernels are not built for -- solorl_ppo_grad_stage2 too, whose
+    tile dispatch would otherwise compute the first 32 input columns only and return success -- and names the supported sizes.  The
+    shape check precedes the device lookup, so this holds without a GPU."""
+    P = _native.PolicyParams()
+    P.obs_dim, P.act_dim, P.hidden = obs_dim, act_dim, 64
+    for k, _t in P._fields_[4:]:
+        setattr(P, k, 4096)                           # non-null, 16-byte aligned (never dereferenced on the host)
+    dummy = C.c_void_p(4096)
+    B, W, G, S = _native.PpoBatch(), _native.PpoStage1(), _native.PpoGrads(), _native.AdamState()
+    for st in (B, W, G, S):
+        for k, t in st._fields_:
+            if t is C.c_void_p:
+                setattr(st, k, 4096)
+    B.m = 64
+    calls = {"solorl_policy_act": lambda: lib.solorl_policy_act(C.byref(P), dummy, None, 64, dummy, dummy, dummy, 0, None),
+             "solorl_ppo_grad_stage1": lambda: lib.solorl_ppo_grad_stage1(C.byref(P), C.byref(B), C.byref(W), 0, None),
+             "solorl_ppo_grad_stage2": lambda: lib.solorl_ppo_grad_stage2(C.byref(P), C.byref(W), 64, C.byref(G), 0, None),
+             "solorl_ppo_clip_adam": lambda: lib.solorl_ppo_clip_adam(C.byref(P), C.byref(G), C.byref(S), 0, None)}
+    for name, call in calls.items():
+        assert call() == -1, name                     # SOLORL_ERR_INVALID
+        msg = lib.solorl_last_error()
+        assert b"38, 42, 76 or 84 x 12; 30, 34, 60 or 68 x 8" in msg, (name, msg)
+
+
 def test_product_never_imports_oracle():
     for dp, _, fs in os.walk(os.path.join(ROOT, "solorl_amd")):
         for f in fs:
