@@ -4,12 +4,54 @@ loads `<checkpoint-dir>/solo.pt` (same dict keys as the reference's checkpoint, 
 rolls it out on the HIP engine until --num-runs episodes have ended and prints
 `mean length / mean reward / mean success` (test_ppo.py:147).  In place of the GUI, --dump writes env 0's
 trajectory (base pose, joint angles, action, reward, done) to an .npz.  --push-interval K --push-max-vel V kicks the base of every env
-every K control steps with an xy velocity drawn uniformly from +-V m/s (robustness evaluation; SoloVecEnv.push)."""
+every K control steps with an xy velocity drawn uniformly from +-V m/s (robustness evaluation; SoloVecEnv.push).
+--gait-metrics says what the gait looks like, from the batched kinematics of every env at every step (SoloVecEnv.get_kinematics,
+reduced on the device): per foot the duty factor, mean and peak normal force, slip distance and peak swing clearance, and the mean
+ratio of the summed normal forces to the robot's weight; --dump then also holds env 0's foot positions and forces."""
 import argparse
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+FEET = ("FL", "FR", "HL", "HR")
+
+
+class GaitMetrics:
+    """Per-foot sums over envs and steps, kept on the device; one transfer in report()."""
+
+    def __init__(self, env):
+        import torch
+        self.dt = env.cfg.frame_skip * env.cfg.sim_dt            # control step [s]
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=env.device)
+        self.steps, self.contact, self.force, self.slip = 0, z(4), z(4), z(env.nenvs, 4)
+        self.peak_force, self.clearance, self.support = z(4), z(4), z()
+
+    def add(self, env, states, kin):
+        """states: the StateBatch of SoloVecEnv.get_states(); kin: the KinBatch computed from it"""
+        import torch
+        from solorl_amd.kinematics import FOOT_PRIMS
+        bits = torch.tensor(FOOT_PRIMS, device=env.device, dtype=torch.int32)
+        touch = ((states.contact_mask.unsqueeze(1) >> bits) & 1).bool()          # [N, 4]
+        self.steps += 1
+        self.contact += touch.sum(0)
+        self.force += kin.foot_force.sum(0)
+        self.peak_force = torch.maximum(self.peak_force, kin.foot_force.max(0).values)
+        self.slip += torch.where(touch, kin.foot_vel[:, :, :2].norm(dim=2) * self.dt, 0.0)
+        self.clearance = torch.maximum(self.clearance, torch.where(touch, 0.0, kin.foot_pos[:, :, 2]).max(0).values)
+        self.support += (kin.prim_force.sum(1) / (kin.mass * env.cfg.gravity)).mean()
+
+    def report(self):
+        n = self.slip.shape[0] * max(self.steps, 1)
+        out = dict(steps=self.steps, support_ratio=float(self.support) / max(self.steps, 1),
+                   duty_factor=(self.contact / n).tolist(), mean_force=(self.force / n).tolist(), peak_force=self.peak_force.tolist(),
+                   slip_distance=self.slip.mean(0).tolist(), peak_clearance=self.clearance.tolist())
+        print("gait over {} steps: mean sum of normal forces / weight {:.3f}".format(self.steps, out["support_ratio"]))
+        for f, name in enumerate(FEET):
+            print("  {} duty factor {:.3f}  normal force mean {:.2f} N peak {:.2f} N  slip {:.4f} m  peak swing clearance {:.4f} m".format(
+                name, out["duty_factor"][f], out["mean_force"][f], out["peak_force"][f], out["slip_distance"][f], out["peak_clearance"][f]))
+        return out
 
 
 def main(argv=None):
@@ -23,6 +65,8 @@ def main(argv=None):
     p.add_argument("--deterministic", action="store_true")
     p.add_argument("--seed", type=int, default=7)
     p.add_argument("--dump", default=None, help="write env 0's trajectory to this .npz")
+    p.add_argument("--gait-metrics", action="store_true", help="per-foot duty factor, normal force, slip and swing clearance over all envs and steps")
+    p.add_argument("--max-steps", type=int, default=0, help="stop after K control steps even if fewer than --num-runs episodes have ended (0 = no limit)")
     p.add_argument("--push-interval", type=int, default=0, help="kick every env's base velocity every K control steps (0 = never)")
     p.add_argument("--push-max-vel", type=float, default=0.0, help="a kick's x and y velocity change is uniform in +-V m/s")
     a = p.parse_args(argv)
@@ -51,13 +95,15 @@ def main(argv=None):
 
     ep_len, ep_R, ep_succ = [], [], []
     ret = torch.zeros(a.num_agents, device=dev)
-    traj = dict(pos=[], quat=[], q=[], action=[], reward=[], done=[])
+    traj = dict(pos=[], quat=[], q=[], action=[], reward=[], done=[], foot_pos=[], foot_force=[])
+    gait = GaitMetrics(env) if a.gait_metrics else None
+    rows = kin = None
     obs = env.reset()
     push_gen, steps = None, 0
     if a.push_interval > 0:
         push_gen = torch.Generator(device=dev); push_gen.manual_seed(a.seed)
         dv = torch.zeros((a.num_agents, 3), device=dev)
-    while len(ep_len) < a.num_runs:
+    while len(ep_len) < a.num_runs and not (a.max_steps and steps >= a.max_steps):
         if push_gen is not None and steps > 0 and steps % a.push_interval == 0:
             dv[:, :2] = (torch.rand((a.num_agents, 2), device=dev, generator=push_gen) * 2 - 1) * a.push_max_vel
             env.push(dv)
@@ -65,7 +111,13 @@ def main(argv=None):
         steps += 1
         with torch.no_grad():
             _, action, _ = policy.act(obs, deterministic=a.deterministic)
+        if gait is not None or a.dump:
+            rows = env.get_states(out=rows)              # the state the policy has just seen, every env: two launches
+            kin = env.get_kinematics(states=rows, out=kin)
+            if gait is not None:
+                gait.add(env, rows, kin)
         if a.dump:
+            traj["foot_pos"].append(kin.foot_pos[0].cpu().numpy()); traj["foot_force"].append(kin.foot_force[0].cpu().numpy())
             s = env.get_state(0)
             traj["pos"].append(list(s.pos)); traj["quat"].append(list(s.quat)); traj["q"].append(list(s.q))
             traj["action"].append(action[0].cpu().numpy())
@@ -80,13 +132,16 @@ def main(argv=None):
                 ep_len.append(int(T["episode_length"][i])); ep_succ.append(float(T["success"][i])); ep_R.append(float(ret[i]))
             ret[done.bool()] = 0
     n = len(ep_len)
-    print("episodes {} mean length {:.1f} mean reward {:.3f} mean success {:.2f}".format(
-        n, sum(ep_len) / n, sum(ep_R) / n, sum(ep_succ) / n))
+    mean = lambda v: sum(v) / n if n else float("nan")      # (--max-steps can end the run before any episode has)
+    print("episodes {} mean length {:.1f} mean reward {:.3f} mean success {:.2f}".format(n, mean(ep_len), mean(ep_R), mean(ep_succ)))
+    result = dict(episodes=n, mean_length=mean(ep_len), mean_reward=mean(ep_R), mean_success=mean(ep_succ))
+    if gait is not None:
+        result["gait"] = gait.report()
     if a.dump:
         np.savez(a.dump, **{k: np.asarray(v) for k, v in traj.items()})
         print("trajectory of env 0 ({} steps) -> {}".format(len(traj["reward"]), a.dump))
     env.close()
-    return dict(episodes=n, mean_length=sum(ep_len) / n, mean_reward=sum(ep_R) / n, mean_success=sum(ep_succ) / n)
+    return result
 
 
 if __name__ == "__main__":

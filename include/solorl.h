@@ -36,6 +36,9 @@
  *   solorl_normalize_obs / solorl_normalize_rewards <- agents/running_mean_std.py:73-127 (VecNormalize: _obfilt :109-116, the reward half
  *                             of step :98-105) with RunningMeanStd.update (:18-39), which agents/ppo/envs.py:25-26 wraps round the vec-env:
  *                             running statistics in caller-owned device memory, fp64, a fixed number of launches for any number of rows
+ *   solorl_kinematics      <- what the reference asks PyBullet for per env (solo.py getLinkState / getContactPoints): link poses, support
+ *                             points of the collision primitives with their velocities and normal forces, centre of mass, energy and
+ *                             momentum of a whole batch of state rows, one launch
  *   solorl_destroy         <- agents/ppo/envs.py:129-135 (close)
  *
  * Plain pointers and sizes only; no torch types.  All array arguments are DEVICE pointers
@@ -259,6 +262,43 @@ int solorl_set_states(solorl_env* env, const uint8_t* mask, const solorl_env_sta
                       uint32_t fields, void* stream);
 int solorl_reset_masked(solorl_env* env, const uint8_t* mask /* [N] device, not NULL */,
                         float* obs_out /* [N*O] or NULL */, void* stream);
+
+/* Derived quantities of a batch of state rows: link poses and velocities, the collision primitives' support points with their
+ * velocities and normal forces, centre of mass, energy and momentum -- what the reference reads from PyBullet (getLinkState,
+ * getContactPoints, the BodyPart poses of pybullet_envs.robot_bases) and Isaac-style vec-envs expose as rigid_body_state /
+ * net_contact_force tensors.  One kernel launch on `stream`, one row out per row in.
+ *   Links in the order of the model table, solorl_model_data: link 0 = the base (a foot is a fixed child of its lower leg); primitives likewise
+ *   (0..11 base points, 12 + 2 leg knee, 13 + 2 leg foot, 20 + leg shoulder housing of a Solo12).  Links 13..16 and primitives
+ *   20..23 of a Solo8 read 0.
+ *   prim_point is the support point of the BARE shape -- the engine's own formulas (disc_point, ring_disc_point, the base points of the
+ *   model table), what the oracle's oracle_prim_points returns; the contact test of a sub-step compares its z - collision_margin with the
+ *   primitive's margin.  Arithmetic is fp64 whatever the precision of the engine that produced the rows: an fp32 engine's collision front
+ *   sees the same points up to float rounding.
+ *   prim_force: the normal force of the LAST sub-step of the last step, lambda_prev[p] / sim_dt where contact_mask bit p is set, else 0.
+ *   Energy and momentum as the oracle's oracle_energy_momentum: link inertia per use_urdf_inertia (0: Bullet's box rule, 1: the URDF
+ *   tensor), potential = sum m g c_z, angular momentum about the WORLD origin.
+ * A function of the rows and of cfg's robot, use_urdf_inertia, sim_dt and gravity only (no handle; rows from any source).  mask: [n] bytes on
+ * the device or NULL = every row; a row whose mask byte is 0 is neither read nor written.  `out` must not overlap `states`.  No host
+ * synchronisation, no allocation: capturable.  Non-finite members of a row give non-finite members of that row's output and nothing
+ * else (no index is computed from data).
+ * Null cfg, states or out, n < 1, a robot that is neither SOLORL_ROBOT_*, sim_dt <= 0 or a non-finite sim_dt / gravity: SOLORL_ERR_INVALID,
+ * the message names the function (checked before any HIP call). */
+#define SOLORL_KIN_MAX_LINKS 17
+typedef struct solorl_env_kin {
+  double link_pos[SOLORL_KIN_MAX_LINKS][3];      /* world position of each link frame's origin */
+  double link_quat[SOLORL_KIN_MAX_LINKS][4];     /* x y z w, link axes -> world, unit, w >= 0 */
+  double link_com[SOLORL_KIN_MAX_LINKS][3];      /* world position of the link's centre of mass */
+  double link_com_vel[SOLORL_KIN_MAX_LINKS][3];  /* world velocity of that point */
+  double link_ang_vel[SOLORL_KIN_MAX_LINKS][3];  /* world angular velocity of the link */
+  double prim_point[SOLORL_STATE_MAX_PRIMS][3];  /* support point of each collision primitive (bare shape, see above) */
+  double prim_vel[SOLORL_STATE_MAX_PRIMS][3];    /* velocity of the link's material point at prim_point */
+  double prim_force[SOLORL_STATE_MAX_PRIMS];     /* normal force [N] of the last sub-step */
+  double com[3], com_vel[3], mass;
+  double kinetic, potential, lin_mom[3], ang_mom[3];
+} solorl_env_kin;
+int solorl_kinematics(const solorl_config* cfg, const solorl_env_state* states /* [n] DEVICE rows */,
+                      const uint8_t* mask /* [n] device, or NULL = all */, int n,
+                      solorl_env_kin* out /* [n] DEVICE rows */, int device_id, void* stream);
 
 /* Fused return computation over a rollout of T steps x N envs (device arrays, time-major [t][n]).
  * use_gae != 0:  value_preds[T][:] = next_value;  delta_t = r_t + gamma V_{t+1} m_{t+1} - V_t;

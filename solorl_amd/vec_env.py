@@ -10,6 +10,8 @@
       norm_obs / norm_ret -- running statistics on the device (normalize.py, include/solorl.h solorl_normalize_obs / solorl_normalize_rewards)
   get_states(mask) -> StateBatch, set_states(states, mask, fields), reset_masked(mask) -> obs, push(dv, mask)   (the whole batch's state as
       one device array, include/solorl.h solorl_get_states ...: no reference counterpart)
+  get_kinematics(mask) -> KinBatch   (link poses, support points of the collision primitives with velocity and normal force, centre of
+      mass, energy, momentum of every env: include/solorl.h solorl_kinematics, kinematics.py)
 
 torch is plumbing only: it owns the device buffers and the stream; all arithmetic happens in
 ``libsolorl_hip.so`` on the caller's current HIP stream (no host synchronisation in step()).
@@ -131,6 +133,7 @@ class SoloVecEnv:
         self._tau = torch.zeros((N, self.act_dim), dtype=torch.float32, **kw) if applied_torque else None
         self._steps_issued = 0
         self._push_states = None    # engine-owned StateBatch of push(), allocated at its first call
+        self._kin_states = None     # engine-owned StateBatch of get_kinematics(), allocated at its first call
         self._kbuf = {}             # engine-owned [K, ...] rows of step_n_inplace / rollout_inplace, per K
         self._info_c = InfoSoA(ep_stats=self._ep_stats.data_ptr(), applied_torque=None if self._tau is None else self._tau.data_ptr(),
                                **{k: self._info[k].data_ptr() for k in _INFO_KEYS})
@@ -455,6 +458,21 @@ class SoloVecEnv:
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_get_states(self._h, pm, self._rows("out", out), self._stream()))
         return out
+
+    def get_kinematics(self, mask=None, states=None, out=None):
+        """Link poses, support points of the collision primitives with their velocities and normal forces, centre of mass, energy and
+        momentum of every env (solorl_amd/kinematics.py KinBatch; include/solorl.h solorl_kinematics), on the current stream.
+        ``states``: rows to use instead of the handle's current state; without it ``get_states(mask)`` fills an engine-owned StateBatch
+        (allocated at the first call, so a HIP graph captured after a warm-up call keeps using it)."""
+        from .kinematics import kinematics
+        if states is None:
+            if self._kin_states is None:
+                self._kin_states = StateBatch(self.nenvs, self.device)
+            states = self.get_states(mask, out=self._kin_states)
+        else:
+            self._rows("states", states)
+        m, _ = self._mask(mask)
+        return kinematics(self.cfg, states, m, out)
 
     def set_states(self, states, mask=None, fields="all"):
         """Writes the member groups ``fields`` (a name, an iterable of names -- pose, vel, joint_pos, joint_vel, contact, history, task,
