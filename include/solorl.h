@@ -39,6 +39,9 @@
  *   solorl_kinematics      <- what the reference asks PyBullet for per env (solo.py getLinkState / getContactPoints): link poses, support
  *                             points of the collision primitives with their velocities and normal forces, centre of mass, energy and
  *                             momentum of a whole batch of state rows, one launch
+ *   solorl_dynamics        <- what the reference's MPC / WBC envs ask Pinocchio for and Isaac-style vec-envs expose as
+ *                             jacobian / mass_matrix tensors: joint-space mass matrix, bias and gravity forces, foot Jacobians and their
+ *                             Jdot v of a whole batch of state rows, one launch
  *   solorl_destroy         <- agents/ppo/envs.py:129-135 (close)
  *
  * Plain pointers and sizes only; no torch types.  All array arguments are DEVICE pointers
@@ -299,6 +302,45 @@ typedef struct solorl_env_kin {
 int solorl_kinematics(const solorl_config* cfg, const solorl_env_state* states /* [n] DEVICE rows */,
                       const uint8_t* mask /* [n] device, or NULL = all */, int n,
                       solorl_env_kin* out /* [n] DEVICE rows */, int device_id, void* stream);
+
+/* Rigid-body dynamics tensors of a batch of state rows: the joint-space mass matrix, the bias and gravity forces, and per foot the
+ * Jacobian, its Jdot v and the point it belongs to -- the members of the rigid_body_state / net_contact_force family that
+ * solorl_kinematics leaves out (Isaac-style jacobian and mass_matrix tensors).  One kernel launch on `stream`, one row out per row in.
+ *   Generalised velocity v = [lin_vel(3), ang_vel(3), qd[0..11]]: the state row's own members in the row's own order; lin_vel is the
+ *   world velocity of the base frame's origin `pos`, ang_vel the world angular velocity.  Dual forces are [world force on the base, world
+ *   torque about pos, joint torques].  A Solo8 has 14 coordinates: rows and columns 14..17 of every member read exactly 0.  The oracle
+ *   (oracle_mass_matrix) orders [angular, linear, joints]: the same quantities under the permutation that swaps the first two triples.
+ *   mass_matrix: M(q), kinetic = 1/2 v^T M v.  Link inertia per use_urdf_inertia (0: Bullet's box rule, 1: the URDF tensor); a foot is
+ *   counted with its lower leg.  Symmetric to the bit.  A leg's joints couple with the base and with the same leg only: the blocks
+ *   between different legs read exactly +0.0.
+ *   bias: h(q, v) of  M udot + bias = tau + J^T f : gravity, Coriolis and centrifugal terms, the gyroscopic term w x I w and Bullet's
+ *   link damping K3 (F = -m v_c (k + k |v_c|), T = -I w (k + k |w|), k = cfg->damping) -- what oracle_mass_matrix returns as h and what
+ *   the engine's unconstrained sub-step integrates.  For the rigid-body terms alone pass a config copy with damping = 0.
+ *   gravity: bias at v = 0.  Entries 0..2 are (0, 0, total mass x g), 3..5 the moment of the weight about pos, the joint entries
+ *   dV/dq_j of solorl_env_kin.potential: tau = gravity[6..] is the gravity-compensation torque, the one that holds the joints against the
+ *   links' weight (udot = 0 at rest in the equation above; -gravity[6..] is the generalised force the weight exerts).
+ *   foot_pos[L]: the support point of the foot primitive 13 + 2 L of leg L (FL, FR, HL, HR), = solorl_env_kin.prim_point[13 + 2 L].
+ *   foot_jac[L]: the 3 x 18 Jacobian of the lower leg's MATERIAL point at foot_pos[L]: foot_jac[L] v = solorl_env_kin.prim_vel[13 + 2 L],
+ *   foot_jac[L]^T f = the generalised force of a world force f at the foot.  Columns of the other legs' joints read 0.
+ *   foot_acc_bias[L]: Jdot v, the acceleration of that material point when all generalised accelerations are zero.
+ * A function of the rows and of cfg's robot, use_urdf_inertia, gravity and damping only (no handle; rows from any source); fp64 whatever
+ * the precision of the engine that produced the rows.  mask: [n] bytes on the device or NULL = every row; a row whose mask byte is 0 is
+ * neither read nor written.  `out` must not overlap `states`.  No host synchronisation, no allocation: capturable.  Non-finite members
+ * of a row give non-finite members of that row's output and nothing else (no index is computed from data).
+ * Null cfg, states or out, n < 1, a robot that is neither SOLORL_ROBOT_*, a non-finite gravity, a non-finite or negative damping:
+ * SOLORL_ERR_INVALID, the message names the function (checked before any HIP call). */
+#define SOLORL_DYN_NV 18
+typedef struct solorl_env_dyn {
+  double mass_matrix[SOLORL_DYN_NV][SOLORL_DYN_NV];
+  double bias[SOLORL_DYN_NV];
+  double gravity[SOLORL_DYN_NV];
+  double foot_jac[4][3][SOLORL_DYN_NV];
+  double foot_acc_bias[4][3];
+  double foot_pos[4][3];
+} solorl_env_dyn;                     /* 600 doubles = 4800 B */
+int solorl_dynamics(const solorl_config* cfg, const solorl_env_state* states /* [n] DEVICE rows */,
+                    const uint8_t* mask /* [n] device, or NULL = all */, int n,
+                    solorl_env_dyn* out /* [n] DEVICE rows */, int device_id, void* stream);
 
 /* Fused return computation over a rollout of T steps x N envs (device arrays, time-major [t][n]).
  * use_gae != 0:  value_preds[T][:] = next_value;  delta_t = r_t + gamma V_{t+1} m_{t+1} - V_t;

@@ -18,7 +18,7 @@ SYMBOLS = ("solorl_default_config", "solorl_create", "solorl_destroy", "solorl_d
            "solorl_compute_returns", "solorl_ppo_loss", "solorl_policy_act", "solorl_ppo_grad_stage1", "solorl_ppo_grad_stage2", "solorl_ppo_grad_count", "solorl_ppo_clip_adam", "solorl_last_error", "solorl_version",
            "solorl_abi_version", "solorl_step_act", "solorl_ppo_scratch_count", "solorl_step_n", "solorl_rollout",
            "solorl_get_states", "solorl_set_states", "solorl_reset_masked",
-           "solorl_norm_scratch_count", "solorl_normalize_obs", "solorl_normalize_rewards", "solorl_kinematics")
+           "solorl_norm_scratch_count", "solorl_normalize_obs", "solorl_normalize_rewards", "solorl_kinematics", "solorl_dynamics")
 
 
 class PolicyParams(C.Structure):            # solorl_policy_params
@@ -105,6 +105,8 @@ def lib():
         # derived quantities of state rows: states, mask and out are device pointers
         L.solorl_kinematics.argtypes = [C.POINTER(SoloConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.solorl_kinematics.restype = C.c_int
+        L.solorl_dynamics.argtypes = [C.POINTER(SoloConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.solorl_dynamics.restype = C.c_int
         for s in SYMBOLS:
             getattr(L, s)
         # the ctypes mirrors in config.py / this file are written against one layout of include/solorl.h's structs

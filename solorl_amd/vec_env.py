@@ -12,6 +12,8 @@
       one device array, include/solorl.h solorl_get_states ...: no reference counterpart)
   get_kinematics(mask) -> KinBatch   (link poses, support points of the collision primitives with velocity and normal force, centre of
       mass, energy, momentum of every env: include/solorl.h solorl_kinematics, kinematics.py)
+  get_dynamics(mask) -> DynBatch   (joint-space mass matrix, bias and gravity forces, foot Jacobians with their Jdot v of every env:
+      include/solorl.h solorl_dynamics, dyn_tensors.py)
 
 torch is plumbing only: it owns the device buffers and the stream; all arithmetic happens in
 ``libsolorl_hip.so`` on the caller's current HIP stream (no host synchronisation in step()).
@@ -134,6 +136,7 @@ class SoloVecEnv:
         self._steps_issued = 0
         self._push_states = None    # engine-owned StateBatch of push(), allocated at its first call
         self._kin_states = None     # engine-owned StateBatch of get_kinematics(), allocated at its first call
+        self._dyn_states = None     # engine-owned StateBatch of get_dynamics(), allocated at its first call
         self._kbuf = {}             # engine-owned [K, ...] rows of step_n_inplace / rollout_inplace, per K
         self._info_c = InfoSoA(ep_stats=self._ep_stats.data_ptr(), applied_torque=None if self._tau is None else self._tau.data_ptr(),
                                **{k: self._info[k].data_ptr() for k in _INFO_KEYS})
@@ -473,6 +476,21 @@ class SoloVecEnv:
             self._rows("states", states)
         m, _ = self._mask(mask)
         return kinematics(self.cfg, states, m, out)
+
+    def get_dynamics(self, mask=None, states=None, out=None):
+        """Joint-space mass matrix, bias and gravity forces, foot Jacobians with their Jdot v and foot points of every env
+        (solorl_amd/dyn_tensors.py DynBatch; include/solorl.h solorl_dynamics), on the current stream.  ``states``: rows to use instead of
+        the handle's current state; without it ``get_states(mask)`` fills an engine-owned StateBatch (allocated at the first call, so a
+        HIP graph captured after a warm-up call keeps using it)."""
+        from .dyn_tensors import dynamics
+        if states is None:
+            if self._dyn_states is None:
+                self._dyn_states = StateBatch(self.nenvs, self.device)
+            states = self.get_states(mask, out=self._dyn_states)
+        else:
+            self._rows("states", states)
+        m, _ = self._mask(mask)
+        return dynamics(self.cfg, states, m, out)
 
     def set_states(self, states, mask=None, fields="all"):
         """Writes the member groups ``fields`` (a name, an iterable of names -- pose, vel, joint_pos, joint_vel, contact, history, task,
