@@ -52,11 +52,11 @@ constexpr double DISC_RIM = 0.1;                         // sine of the tilt at 
 // [1] the sub-steps, [2] last sub-step -> end, [3] whole kernel in s_memrealtime ticks (100 MHz), [4] sum over the sub-steps of
 // the slots the wave swept, [5] the maximum over the sub-steps of its largest contact count
 #if defined(SOLO_WAVE_TIMING) && !defined(SOLO_HOST_SHIM)
-constexpr int SOLO_WT_WAVES = 65536, SOLO_WT_FIELDS = 28;    // [6..15]: the ten intervals between the kernel's stamps; [16..25]: per-phase
+constexpr int SOLO_WT_WAVES = 65536, SOLO_WT_FIELDS = 30;    // [6..15]: the ten intervals between the kernel's stamps; [16..25], [28..29]: per-phase
 __device__ unsigned long long solo_wave_times[SOLO_WT_WAVES][SOLO_WT_FIELDS];                                // sums over the sub-steps (SOLO_PT)
 // phase stamps of substep_team: after a full drain of the wave's memory counters (timing build only), lane 0 adds the ticks since
 // the previous stamp to phase slot i of the workgroup's LDS accumulators; step_team writes them out with its own stamps
-__shared__ unsigned long long solo_pt_acc[10];
+__shared__ unsigned long long solo_pt_acc[12];     // [10]: the main wavefront's wait at barrier D, [11]: the helper's work behind D (duo kernel)
 #define SOLO_PT_DECL() long long pt_last_ = 0
 #define SOLO_PT_BEGIN() do { __builtin_amdgcn_s_waitcnt(0); pt_last_ = clock64(); } while (0)
 #define SOLO_PT(i) do { __builtin_amdgcn_s_waitcnt(0); if (threadIdx.x == 0) { const long long n_ = clock64(); solo_pt_acc[i] += (unsigned long long)(n_ - pt_last_); } pt_last_ = clock64(); } while (0)
@@ -159,7 +159,7 @@ extern __shared__ __attribute__((aligned(16))) unsigned char solo_smem_sym[];
 // with the constant (check_lds_base, solorl_hip.hip: SOLORL_ERR_HIP instead of wrong physics), and tests/test_abi.py reads the same
 // number from the built code object.  Nothing is checked on the device.
 #if defined(SOLO_WAVE_TIMING)
-constexpr unsigned SOLO_LDS_BASE = 80;                   // behind solo_pt_acc[10] -- which only the TEAM kernel references: the timing build
+constexpr unsigned SOLO_LDS_BASE = 96;                   // behind solo_pt_acc[12] -- which only the TEAM kernel references: the timing build
                                                          // is team-mode only (check_lds_base rejects the lane-mode kernel there, by design)
 #else
 constexpr unsigned SOLO_LDS_BASE = 0;
@@ -2156,6 +2156,8 @@ SD void phase_pgs_team(int iterations_, bool warm_on, bool early_exit, bool pipe
 
 // apply + integrate, team mode: impulse cache and joints one per lane, base pose on the leader.
 // Reads the sweep's results straight from the team arrays (accumulators in hdr / y, impulses in lam).
+// The duo kernel runs this phase as two halves on its two wavefronts, duo_integrate_joints and duo_integrate_base (below): copies of
+// this text, bit for bit -- a change here is a change there.
 template <typename T, int ROBOT, typename LDS, typename CH>
 SNI_SCALAR void phase_integrate_team(CH ch, const PhysParams<T> pp, T* lam_prev, unsigned nstride, const LDS lds, int t, bool valid,
                               bool lead) {
@@ -2229,20 +2231,96 @@ SNI_SCALAR void duo_helper_rates(CH ch, const PhysParams<T> pp, const LDS lds, i
 }
 
 // Main wavefront of duo_kernel_team: barrier C, between its leg rows and the row finish (a function of its own for the same census;
-// nothing is live in registers across it that the phases on either side do not re-read from LDS).
+// nothing is live in registers across it that the phases on either side do not re-read from LDS).  Barriers D (behind the sweep) and
+// Z (in front of the epilogue) are calls of the same function, by BOTH roles: a barrier, nothing else.
 template <typename T, int ROBOT>
 SNI_SCALAR void duo_join_rows() {
-  WG_SYNC();                              // barrier C
+  WG_SYNC();                              // barrier C, D or Z
+}
+
+// Main wavefront of duo_kernel_team behind barrier D: phase_integrate_team without its leader block -- the impulse cache and the joints,
+// one per lane, operands read before any store as there.  Reads the sweep's w from hdr, never C.ps.w: the helper is writing that word
+// meanwhile (duo_integrate_base).
+template <typename T, int ROBOT, typename LDS, typename CH>
+SNI_SCALAR void duo_integrate_joints(CH ch, const PhysParams<T> pp, const LDS lds, int t, bool valid) {
+  using RB = Robot<ROBOT>;
+  using TRW = TeamRows<T, LDS>;
+  constexpr int NJ = RB::NJ, LN = LDS::LANES;
+  if (!valid) return;
+  SubCtx<T, ROBOT>& C = ch.get();
+  const T dt = pp.dt;
+  const int mask = C.mask;
+  const int nlt = C.nlim_total;
+  const T* hdr = lds.hdr();
+  const SV<T> w{{hdr[2 * LN], hdr[3 * LN], hdr[4 * LN]}, {hdr[5 * LN], hdr[6 * LN], hdr[7 * LN]}};
+  const int tj = t < RB::NQ ? t : 0;                 // (every lane reads a valid joint's operands; lanes >= NQ discard them)
+  const int L = tj / NJ, k = tj - L * NJ;
+  const T qds = C.qds[tj], yk = lds.y()[(L * 3 + k) * LN], qj = C.ps.q[tj];
+  const SV<T> Gk = C.LR[L].G[k];
+  const T* lam = TRW::lam(lds.lane);
+  const int npos0 = TRW::NPOS0 + extra_limits(nlt);
+  T lv[(NPRIM + 15) / 16];
+#pragma unroll
+  for (int i = 0; i < (NPRIM + 15) / 16; i++) {      // warm-start cache: normal impulse of primitive p (its rank among the contacts)
+    const int p = t + 16 * i;
+    const int pp_ = p < NPRIM ? p : 0;
+    lv[i] = lam[(npos0 + __builtin_popcount(mask & ((1 << pp_) - 1))) * 4];
+    lv[i] = (p < NPRIM && ((mask >> pp_) & 1)) ? lv[i] : T(0);
+  }
+  // ---- compute
+  const T nvj = clampv(qds + yk - dot(Gk, w), pp.vmax);
+  // ---- store
+#pragma unroll
+  for (int i = 0; i < (NPRIM + 15) / 16; i++) { const int p = t + 16 * i; if (p < NPRIM) C.lamp[p] = lv[i]; }
+  if (t < RB::NQ) { C.ps.qd[t] = nvj; C.ps.q[t] = qj + dt * nvj; }
+}
+
+// Helper wavefront of duo_kernel_team behind barrier D: the leader block of phase_integrate_team (the base's velocity and pose), its
+// operands loaded before any store, and then -- `r0`: for every sub-step but the last -- the NEXT sub-step's C.R0 from the quaternion it
+// has just written (substep_team computes it for the first sub-step only).
+template <typename T, int ROBOT, typename LDS, typename CH>
+SNI_SCALAR void duo_integrate_base(CH ch, const PhysParams<T> pp, const LDS lds, bool lead, bool r0) {
+  constexpr int LN = LDS::LANES;
+  if (!lead) return;
+  SubCtx<T, ROBOT>& C = ch.get();
+  const T dt = pp.dt;
+  const T* hdr = lds.hdr();
+  const SV<T> w{{hdr[2 * LN], hdr[3 * LN], hdr[4 * LN]}, {hdr[5 * LN], hdr[6 * LN], hdr[7 * LN]}};
+  const SV<T> ub = C.ub;
+  const V3<T> pos = C.ps.pos;
+  const T x = C.ps.qx, yq = C.ps.qy, z = C.ps.qz, ww = C.ps.qw;
+  // ---- compute
+  const V3<T> nw = mk(clampv(ub.a.x + w.a.x, pp.vmax), clampv(ub.a.y + w.a.y, pp.vmax), clampv(ub.a.z + w.a.z, pp.vmax));
+  const V3<T> nv = mk(clampv(ub.l.x + w.l.x, pp.vmax), clampv(ub.l.y + w.l.y, pp.vmax), clampv(ub.l.z + w.l.z, pp.vmax));
+  // ---- store
+  C.ps.w = nw; C.ps.v = nv;
+  C.ps.pos = fma3(nv, dt, pos);
+  T wn2 = dot(nw, nw), wn = sqrt_fast(wn2), sc, s_, cw;
+  sincos_t(T(0.5) * wn * dt, s_, cw);
+  if (wn < T(1e-3)) sc = T(0.5) * dt - dt * dt * dt * T(1.0 / 48.0) * wn2; else sc = s_ * rcp_fast(wn);
+  T ax = nw.x * sc, ay = nw.y * sc, az = nw.z * sc;
+  T nx = cw * x + ax * ww + ay * z - az * yq;
+  T ny = cw * yq - ax * z + ay * ww + az * x;
+  T nz = cw * z + ax * yq - ay * x + az * ww;
+  T nq = cw * ww - ax * x - ay * yq - az * z;
+  T inv = rsqrt_fast(nx * nx + ny * ny + nz * nz + nq * nq);
+  C.ps.qx = nx * inv; C.ps.qy = ny * inv; C.ps.qz = nz * inv; C.ps.qw = nq * inv;
+  if (r0) C.R0 = quat_to_mat(C.ps.qx, C.ps.qy, C.ps.qz, C.ps.qw);
 }
 
 // Helper wavefront of duo_kernel_team, one sub-step: the collision front between workgroup barriers A and B, then -- beside the main
 // wavefront's leg rows -- the leg sum, the base solve and the leg rates up to barrier C: the calls substep_team makes in the
 // classic kernel, in its order, on the same operands (phase_base_lead is the classic kernel's one instantiation; it reads neither
-// lam_prev nor nstride).  Three barriers per sub-step, none under a predicate.
-//   main   : R0, sin/cos | A | leg dynamics | B | leg rows                      | C | row finish, sweep, integrate
-//   helper :             | A | front        | B | leg sum, base solve, leg rates | C |
-// A is behind the main wavefront's integrate of the previous sub-step (state, impulse cache, the row storage the sweep read) and
-//   its C.R0 / sin / cos of this one.
+// lam_prev nor nstride), and behind barrier D the base's pose integration with the NEXT sub-step's R0 while the main wavefront
+// integrates the joints.  Four barriers per sub-step and one, Z, behind the last; none under a predicate.
+//   main   : sin/cos | A | leg dynamics | B | leg rows                      | C | row finish, sweep | D | joints, impulse cache |
+//   helper :         | A | front        | B | leg sum, base solve, leg rates | C |  (idle)           | D | base pose, next R0    |
+// Barriers per role, step of frame_skip = F sub-steps (every one on a path that depends on kernel arguments only):
+//             A                     B                    C                  D                          Z               total
+//   main      F (substep_team)      F (phase_leg_rt)     F (duo_join_rows)  F (duo_join_rows)          1 (step_team)   4 F + 1
+//   helper    F (here)              F (here)             F (duo_helper_rates)  F (duo_join_rows, here)  1 (step_team)   4 F + 1
+// A is behind the main wavefront's joint integrate of the previous sub-step (joints, impulse cache, the row storage the sweep read)
+//   and its sin / cos of this one, and behind the helper's base pose and C.R0 (the first sub-step's R0: step_team, main).
 // B hands the front's results (selectors, support points, distances, the base contacts' rows, the base link terms) to the main
 //   wavefront's leg rows, and the main wavefront's C.Ileg / C.pleg / C.LR (stored by sub-lane 0 above its barrier B) to this one.
 // Between B and C (audit of every LDS word either side touches there):
@@ -2257,9 +2335,18 @@ SNI_SCALAR void duo_join_rows() {
 //   them next behind the NEXT sub-step's B, which the main wavefront reaches only after its integrate; the front between the next
 //   A and B writes none of them (it does write C.Ibase / C.pbase, which the main wavefront never reads).  An idle team's
 //   hdr[0] = hdr[LN] = 0 is stored here, above C, where substep_team stores it in the classic kernel: phase_finish_team reads it.
-// The helper returns behind the last sub-step's C.
+// Between D and the next A, or Z (audit of every LDS word either side touches there):
+//   helper reads   hdr[2 LN .. 7 LN] (the sweep's w, final at D), C.ub (its own, above C), C.ps.pos and the quaternion
+//   helper writes  C.ps.w, C.ps.v, C.ps.pos, the quaternion, C.R0 (not behind the last sub-step)
+//   main reads     C.mask, C.nlim_total, hdr[2 LN .. 7 LN] (w -- never C.ps.w), C.qds, y, C.ps.q, C.LR[].G, the impulses lam;
+//                  then C.tau_base and its own C.ps.q for the next sub-step's torques and sin / cos
+//   main writes    C.lamp, C.ps.qd, C.ps.q, C.irec[IR_MASK], C.tau, C.sn, C.cs
+//   No word is written on one side and touched on the other.  The first reader of everything either side wrote is behind A: the
+//   helper's front (the whole state, sn / cs) and the main wavefront's leg dynamics (C.R0, C.tau, the state) -- or, behind Z, the
+//   main wavefront's epilogue (state back to HBM, reward, observation).
+// The helper returns behind Z (step_team).
 template <typename T, int ROBOT, typename LDS>
-SD void substep_team_helper(const PhysParams<T> pp, const LDS& lds, int t, bool lead, bool valid) {
+SD void substep_team_helper(const PhysParams<T> pp, const LDS& lds, int t, bool lead, bool valid, bool r0_next) {
   using CH = typename TeamCtx<T, ROBOT, LDS>::type;
   const CH ch{lds.lane};
   WG_SYNC();                              // barrier A
@@ -2280,10 +2367,20 @@ SD void substep_team_helper(const PhysParams<T> pp, const LDS& lds, int t, bool 
   if (threadIdx.x == 64) solo_pt_acc[4] += (unsigned long long)(clock64() - wt_h0_);
 #endif
   duo_helper_rates<T, ROBOT, LDS, CH>(ch, pp, lds, t, valid);            // leg rates, barrier C (the main wavefront's: duo_join_rows)
+  duo_join_rows<T, ROBOT>();                                             // barrier D: the sweep's w is final
+#if defined(SOLO_WAVE_TIMING)
+  __builtin_amdgcn_s_waitcnt(0);
+  const long long wt_h1_ = clock64();
+#endif
+  duo_integrate_base<T, ROBOT, LDS, CH>(ch, pp, lds, lead, r0_next);     // base pose, then R0 of the next sub-step
+#if defined(SOLO_WAVE_TIMING)      // the helper's D-to-A work (the wait at A or Z behind it is not in it)
+  __builtin_amdgcn_s_waitcnt(0);
+  if (threadIdx.x == 64) solo_pt_acc[11] += (unsigned long long)(clock64() - wt_h1_);
+#endif
 }
 
 // the leader's context C lives in LDS (see CtxLds); `C` is only dereferenced by leader lanes
-// DUO (main wavefront of duo_kernel_team): the front is the helper's (substep_team_helper), see there; C.R0 comes from here
+// DUO (main wavefront of duo_kernel_team): the front, the base solve, the base's pose and C.R0 are the helper's (substep_team_helper)
 template <typename T, int ROBOT, typename LDS, bool DUO = false>
 SD int substep_team(const PhysParams<T> pp, T* lam_prev, unsigned nstride, const LDS& lds, int t, bool lead, bool valid) {
   constexpr int LN = LDS::LANES;
@@ -2292,9 +2389,7 @@ SD int substep_team(const PhysParams<T> pp, T* lam_prev, unsigned nstride, const
   const CH ch{lds.lane};
   SOLO_PT_DECL();
   SOLO_PT_BEGIN();
-  if constexpr (DUO) {
-    if (lead) { SubCtx<T, ROBOT>& C = ch.get(); C.R0 = quat_to_mat(C.ps.qx, C.ps.qy, C.ps.qz, C.ps.qw); }
-  }
+  // (DUO: C.R0 is already there -- the first sub-step's from step_team, every later one's from the helper behind the previous barrier D)
   if (valid && t < Robot<ROBOT>::NQ) {   // sin/cos of joint t on lane t
     SubCtx<T, ROBOT>& C = ch.get();
     T sn, cs;
@@ -2342,7 +2437,11 @@ SD int substep_team(const PhysParams<T> pp, T* lam_prev, unsigned nstride, const
   SOLO_PT(6);
   phase_pgs_team<T, ROBOT, LDS>(pp.iterations, pp.warm != T(0), pp.resid_thr >= T(0), pp.pgs_pipe(), pp.cone(), lds, t);
   SOLO_PT(7);
-  phase_integrate_team<T, ROBOT, LDS, CH>(ch, pp, lam_prev, nstride, lds, t, valid, lead);
+  if constexpr (DUO) {
+    duo_join_rows<T, ROBOT>();             // barrier D: the base pose (and the next R0) is the helper's from here, see substep_team_helper
+    SOLO_PT(10);                           // (timing build: the wait at barrier D)
+    duo_integrate_joints<T, ROBOT, LDS, CH>(ch, pp, lds, t, valid);
+  } else phase_integrate_team<T, ROBOT, LDS, CH>(ch, pp, lam_prev, nstride, lds, t, valid, lead);
   SOLO_PT(8);
   return lead ? (ch.get().mask | strip_feet_bits(ch.get().smask)) : 0;
 }

@@ -631,9 +631,10 @@ SD void policy_tail_team(const PolicyTail& P, int O, int col, int t, idx_t env, 
 }
 
 // DUO (duo_kernel_team): the workgroup has a second wavefront, the HELPER, which runs the collision front of every sub-step while
-// this one, the main wavefront, computes the leg dynamics, and then the leg sum, the base solve and the leg rates while this one parks
-// the leg rows (substep_team_helper); both address the workgroup's one LDS block with the lane index threadIdx.x & 63.  The helper
-// loads nothing from HBM and stores nothing to it.
+// this one, the main wavefront, computes the leg dynamics, then the leg sum, the base solve and the leg rates while this one parks
+// the leg rows, and the base's pose integration (with the next sub-step's R0) while this one integrates the joints
+// (substep_team_helper); both address the workgroup's one LDS block with the lane index threadIdx.x & 63.  The helper loads nothing
+// from HBM and stores nothing to it.
 template <typename T, int ROBOT, bool DUO = false>
 SD void step_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict__ snf, const int* __restrict__ sni, int M,
                   const Layout& L, int N, const EnvParams& P, const PhysParams<T>& pp, const float* __restrict__ actions,
@@ -647,7 +648,7 @@ SD void step_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict_
   long long wts_[11];
   for (int i_ = 0; i_ < 11; i_++) wts_[i_] = 0;
   const long long wr0_ = wall_clock64();
-  if (threadIdx.x < 10) solo::solo_pt_acc[threadIdx.x] = 0;
+  if (threadIdx.x < 12) solo::solo_pt_acc[threadIdx.x] = 0;
   __syncthreads();
   wts_[0] = clock64();
 #endif
@@ -675,14 +676,17 @@ SD void step_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict_
   SubCtx<T, ROBOT>& C = ch.get();
   T* const psv = reinterpret_cast<T*>(&C.ps);
   if constexpr (DUO) {
-    // Workgroup barriers of a step, per role: 3 x frame_skip (A, B and C of every sub-step; main: A in substep_team, B in phase_leg_rt,
-    // C in duo_join_rows; helper: A and B in substep_team_helper, C in duo_helper_rates) -- plus the one behind the LDS poison fill
-    // above when that test hook is on, and, in a -DSOLO_WAVE_TIMING build, the one behind the counters' reset.  All of them sit on
-    // paths that depend on kernel arguments only; the helper returns behind the last sub-step's C.
+    // Workgroup barriers of a step, per role: 4 x frame_skip + 1 (A, B, C and D of every sub-step, then Z; main: A in substep_team, B in
+    // phase_leg_rt, C and D in duo_join_rows, Z in duo_join_rows below the sub-step loop; helper: A and B in substep_team_helper, C in
+    // duo_helper_rates, D in duo_join_rows, Z in duo_join_rows below its loop) -- plus the one behind the LDS poison fill above when
+    // that test hook is on, and, in a -DSOLO_WAVE_TIMING build, the one behind the counters' reset.  All of them sit on paths that
+    // depend on kernel arguments only; the helper returns behind Z.
     if (blk * 4u >= (unsigned)N) return;              // a workgroup of the padded grid without an env: both wavefronts leave here
     if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) {          // ---- the helper wavefront
 #pragma unroll 1
-      for (int ss = 0; ss < P.frame_skip; ss++) substep_team_helper<T, ROBOT>(pp, lds, t, lead, valid);
+      for (int ss = 0; ss < P.frame_skip; ss++)
+        substep_team_helper<T, ROBOT>(pp, lds, t, lead, valid, ss + 1 < P.frame_skip);
+      duo_join_rows<T, ROBOT>();                      // barrier Z: the last sub-step's base pose is in LDS
       return;
     }
     // an idle team of a workgroup that has envs runs the leg phase with the others (barrier B is inside): it parks nothing
@@ -726,6 +730,8 @@ SD void step_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict_
   if (lead) {
     C.erec[ER_XYPREV] = C.ps.pos.x; C.erec[ER_XYPREV + 1] = C.ps.pos.y;
     C.tmy = C.erec[ER_TMY];
+    // DUO: the first sub-step's R0 is this wavefront's; every later one is the helper's, left behind the previous sub-step's barrier D
+    if constexpr (DUO) C.R0 = quat_to_mat(C.ps.qx, C.ps.qy, C.ps.qz, C.ps.qw);
   }
   if (valid && L.H > 0) {
 #pragma unroll
@@ -752,6 +758,9 @@ SD void step_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict_
     if (valid && t < NQ) C.tau[t] = C.tau_base[t] * sc;
     const int m = substep_team<T, ROBOT, LDS, DUO>(pp, sf + SX(L.lam, e, L.NF), 4u, lds, t, lead, valid);
     if (lead) C.irec[IR_MASK] = m;
+  }
+  if constexpr (DUO) {
+    duo_join_rows<T, ROBOT>();           // barrier Z: the helper's last base pose is in LDS (it returns behind this barrier)
   }
   WT_STAMP(4);
   if (valid) for (int p = t; p < NPRIM; p += 16) sf[SX(L.lam + p, e, L.NF)] = C.lamp[p];
@@ -878,6 +887,7 @@ SD void step_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict_
     w_[3] = (unsigned long long)(wall_clock64() - wr0_);
     for (int i_ = 0; i_ < 10; i_++) w_[6 + i_] = (unsigned long long)(wts_[i_ + 1] > wts_[i_] && wts_[i_] ? wts_[i_ + 1] - wts_[i_] : 0);
     for (int i_ = 0; i_ < 10; i_++) w_[16 + i_] = solo::solo_pt_acc[i_];       // per-phase sums over the sub-steps (SOLO_PT)
+    for (int i_ = 10; i_ < 12; i_++) w_[18 + i_] = solo::solo_pt_acc[i_];      // (26, 27: the sweep's counters)
   }
 #endif
 }
