@@ -12,9 +12,9 @@ INC = [os.path.join(ROOT, "include", f) for f in ("solorl.h", "solorl_model_data
 UNITS = {
     "solorl_hip.hip": [os.path.join(HERE, "csrc", f) for f in ("solorl_hip.hip", "dynamics.hpp", "spatial.hpp")] + INC,
     "solorl_ppo.hip": [os.path.join(HERE, "csrc", "solorl_ppo.hip"), INC[0]],
-    "solorl_norm.hip": [os.path.join(HERE, "csrc", "solorl_norm.hip"), INC[0]],
-    "solorl_kin.hip": [os.path.join(HERE, "csrc", f) for f in ("solorl_kin.hip", "kinematics.hpp", "dynamics.hpp", "spatial.hpp")] + INC,
-    "solorl_dyn.hip": [os.path.join(HERE, "csrc", f) for f in ("solorl_dyn.hip", "dyn_tensors.hpp", "kinematics.hpp", "dynamics.hpp", "spatial.hpp")] + INC,
+    "solorl_norm.hip": [os.path.join(HERE, "csrc", f) for f in ("solorl_norm.hip", "row_batch.hpp")] + INC[:1],
+    "solorl_kin.hip": [os.path.join(HERE, "csrc", f) for f in ("solorl_kin.hip", "row_batch.hpp", "kinematics.hpp", "state_row.hpp", "dynamics.hpp", "spatial.hpp")] + INC,
+    "solorl_dyn.hip": [os.path.join(HERE, "csrc", f) for f in ("solorl_dyn.hip", "row_batch.hpp", "dyn_tensors.hpp", "state_row.hpp", "dynamics.hpp", "spatial.hpp")] + INC,
 }
 SRC = UNITS["solorl_hip.hip"][:3]
 # units whose object goes into a directory of its own under OBJ.  tests/test_build_cpu.py pins what lies directly in OBJ -- the five

@@ -4,7 +4,7 @@
 //
 // One function, env_dynamics<T, ROBOT>, made of five independent parts (the base and the four legs: DynRow) and the sum of their shares
 // of the base's 6 x 6 block and of bias[0..5] (dyn_totals), the way kinematics.hpp is built.  solorl_dyn.hip runs a row's parts on four
-// wavefronts, one lane per env each; tests/host/dyn_main.cpp, compiled by g++ under SOLO_HOST_SHIM, calls the function as it is.  A row
+// wavefronts, one lane per env each; tests/host/rows_main.cpp, compiled by g++ under SOLO_HOST_SHIM, calls the function as it is.  A row
 // is read through `ld(word)` and written through `st(word, value)`; every word index is a compile-time constant after unrolling.
 //
 // Frames and support points are not restated: leg_frames and leg_prim_points of dynamics.hpp.  Everything is expressed as the step
@@ -22,7 +22,7 @@
 #pragma once
 #include <cstddef>
 
-#include "kinematics.hpp"
+#include "state_row.hpp"
 
 namespace solo {
 
@@ -38,19 +38,24 @@ static_assert(offsetof(solorl_env_state, q) < offsetof(solorl_env_state, qd) && 
 #define DYN_M(a, b) (DYN_DW(mass_matrix) + (a) * DYN_NV + (b))
 #define DYN_J(leg, r, c) (DYN_DW(foot_jac) + ((leg) * 3 + (r)) * DYN_NV + (c))
 
-// after every link and every row of M: no instruction is scheduled across (KIN_FENCE of kinematics.hpp, for the same reason: the
-// outputs are stores nothing waits for, and the scheduler would otherwise run far ahead of them with everything live)
-#define DYN_FENCE() KIN_FENCE()
-
 // a part's share of the whole robot's rigid-body inertia about pos (-> the base's 6 x 6 block, gravity[0..5]) and of the wrench
 // about pos that the bias accelerations, the damping and the weights ask for (-> bias[0..5])
 template <typename T> struct DynSums { RBI<T> I; SV<T> W; };
 constexpr int DYN_SUM_WORDS = 16;
 constexpr int DYN_PARTS = 5;          // the base, then one part per leg
+// a share as DYN_SUM_WORDS words and back (how the device's wavefronts hand their shares to the one that adds them)
+template <typename T> SD void dyn_sums_to_words(T* q, const DynSums<T>& A) {
+  q[0] = A.I.m; q[1] = A.I.h.x; q[2] = A.I.h.y; q[3] = A.I.h.z;
+  q[4] = A.I.I.xx; q[5] = A.I.I.xy; q[6] = A.I.I.xz; q[7] = A.I.I.yy; q[8] = A.I.I.yz; q[9] = A.I.I.zz;
+  q[10] = A.W.a.x; q[11] = A.W.a.y; q[12] = A.W.a.z; q[13] = A.W.l.x; q[14] = A.W.l.y; q[15] = A.W.l.z;
+}
+template <typename T> SD DynSums<T> dyn_sums_from_words(const T* q) {
+  return DynSums<T>{RBI<T>{q[0], mk(q[1], q[2], q[3]), Sym3<T>{q[4], q[5], q[6], q[7], q[8], q[9]}}, SV<T>{mk(q[10], q[11], q[12]), mk(q[13], q[14], q[15])}};
+}
 
 template <typename T> SD RBI<T> rbi_zero() { return RBI<T>{T(0), {T(0), T(0), T(0)}, {T(0), T(0), T(0), T(0), T(0), T(0)}}; }
 
-// ld(w): word w of the state row (a member's KIN_SW offset + index);  st(w, v): word w of the solorl_env_dyn row.
+// ld(w): word w of the state row (a member's STATE_SW offset + index);  st(w, v): word w of the solorl_env_dyn row.
 // urdf: solorl_config use_urdf_inertia != 0;  gravity, kd: solorl_config gravity, damping.
 template <typename T, int ROBOT, typename LD, typename ST> struct DynRow {
   using RB = Robot<ROBOT>;
@@ -61,10 +66,10 @@ template <typename T, int ROBOT, typename LD, typename ST> struct DynRow {
   DynSums<T> S;
 
   SD DynRow(LD ld_, ST st_, bool urdf_, T gravity_, T kd_) : ld(ld_), st(st_), urdf(urdf_), gravity(gravity_), kd(kd_) {
-    pos = mk(ld(KIN_SW(pos)), ld(KIN_SW(pos) + 1), ld(KIN_SW(pos) + 2));
-    v0 = mk(ld(KIN_SW(lin_vel)), ld(KIN_SW(lin_vel) + 1), ld(KIN_SW(lin_vel) + 2));
-    w0 = mk(ld(KIN_SW(ang_vel)), ld(KIN_SW(ang_vel) + 1), ld(KIN_SW(ang_vel) + 2));
-    R0 = quat_to_mat(ld(KIN_SW(quat)), ld(KIN_SW(quat) + 1), ld(KIN_SW(quat) + 2), ld(KIN_SW(quat) + 3));   // the quaternion as it is, as the step reads it
+    pos = mk(ld(STATE_SW(pos)), ld(STATE_SW(pos) + 1), ld(STATE_SW(pos) + 2));
+    v0 = mk(ld(STATE_SW(lin_vel)), ld(STATE_SW(lin_vel) + 1), ld(STATE_SW(lin_vel) + 2));
+    w0 = mk(ld(STATE_SW(ang_vel)), ld(STATE_SW(ang_vel) + 1), ld(STATE_SW(ang_vel) + 2));
+    R0 = quat_to_mat(ld(STATE_SW(quat)), ld(STATE_SW(quat) + 1), ld(STATE_SW(quat) + 2), ld(STATE_SW(quat) + 3));   // the quaternion as it is, as the step reads it
     S = DynSums<T>{rbi_zero<T>(), zero6<T>()};
   }
   SD void st3(int w, V3<T> v) { st(w, v.x); st(w + 1, v.y); st(w + 2, v.z); }
@@ -79,11 +84,8 @@ template <typename T, int ROBOT, typename LD, typename ST> struct DynRow {
 
   // K2 inertia of link l about its COM, world axes: R I_l R^T (Bullet's box rule, or the URDF tensor)
   template <int l> SD Sym3<T> world_inertia(const M3<T>& R) const {
-    constexpr solorl_link_data LK = RB::MD.links[l];
-    const T ixx = urdf ? T(LK.inertia_urdf[0]) : T(LK.inertia_box[0]), iyy = urdf ? T(LK.inertia_urdf[1]) : T(LK.inertia_box[1]),
-            izz = urdf ? T(LK.inertia_urdf[2]) : T(LK.inertia_box[2]);
-    const T ixy = urdf ? T(LK.inertia_urdf[3]) : T(0), ixz = urdf ? T(LK.inertia_urdf[4]) : T(0), iyz = urdf ? T(LK.inertia_urdf[5]) : T(0);
-    const V3<T> A0 = R.c0 * ixx + R.c1 * ixy + R.c2 * ixz, A1 = R.c0 * ixy + R.c1 * iyy + R.c2 * iyz, A2 = R.c0 * ixz + R.c1 * iyz + R.c2 * izz;
+    const LinkInertia<T> I = link_inertia<T, ROBOT, l>(urdf);
+    const V3<T> A0 = R.c0 * I.xx + R.c1 * I.xy + R.c2 * I.xz, A1 = R.c0 * I.xy + R.c1 * I.yy + R.c2 * I.yz, A2 = R.c0 * I.xz + R.c1 * I.yz + R.c2 * I.zz;
     return Sym3<T>{A0.x * R.c0.x + A1.x * R.c1.x + A2.x * R.c2.x, A0.x * R.c0.y + A1.x * R.c1.y + A2.x * R.c2.y,
                    A0.x * R.c0.z + A1.x * R.c1.z + A2.x * R.c2.z, A0.y * R.c0.y + A1.y * R.c1.y + A2.y * R.c2.y,
                    A0.y * R.c0.z + A1.y * R.c1.z + A2.y * R.c2.z, A0.z * R.c0.z + A1.z * R.c1.z + A2.z * R.c2.z};
@@ -126,7 +128,7 @@ template <typename T, int ROBOT, typename LD, typename ST> struct DynRow {
     const V3<T> c = addc(zero, R0, LK.com[0], LK.com[1], LK.com[2]);
     add_wrench<0>(R0, zero, c, w0, v0, zero, zero, S.W);
     add_inertia<0>(R0, c, S.I);
-    DYN_FENCE();
+    ROW_FENCE();
     static_for<DYN_NV - NV>([&](auto ic) {
       constexpr int a = NV + decltype(ic)::value;
       static_for<DYN_NV>([&](auto bc) {
@@ -146,8 +148,8 @@ template <typename T, int ROBOT, typename LD, typename ST> struct DynRow {
     T qd[NQ], sn[NQ], cs[NQ];
     static_for<NJ>([&](auto kc) {
       constexpr int j = RB::MD.links[L0 + decltype(kc)::value].dof;
-      qd[j] = ld(KIN_SW(qd) + j);
-      const SinCos<T> full = sincos_call(ld(KIN_SW(q) + j));
+      qd[j] = ld(STATE_SW(qd) + j);
+      const SinCos<T> full = sincos_call(ld(STATE_SW(q) + j));
       sn[j] = full.s; cs[j] = full.c;
     });
     V3<T> kneeP, P, shP = zero;
@@ -165,7 +167,7 @@ template <typename T, int ROBOT, typename LD, typename ST> struct DynRow {
     st(DYN_J(L, 0, 3), T(0)); st(DYN_J(L, 0, 4), P.z);  st(DYN_J(L, 0, 5), -P.y);
     st(DYN_J(L, 1, 3), -P.z); st(DYN_J(L, 1, 4), T(0)); st(DYN_J(L, 1, 5), P.x);
     st(DYN_J(L, 2, 3), P.y);  st(DYN_J(L, 2, 4), -P.x); st(DYN_J(L, 2, 5), T(0));
-    DYN_FENCE();
+    ROW_FENCE();
 
     // outwards: velocities, bias accelerations, each joint's motion vector and its column of the foot's Jacobian, each moving link's
     // inertia about pos and its wrench about pos -- the wrench projected at once on the motion vectors of the joints between the
@@ -207,7 +209,7 @@ template <typename T, int ROBOT, typename LD, typename ST> struct DynRow {
       });
       S.W = S.W + W;
       op = o; wp = w; vop = vo; albp = alb; aobp = aob;
-      DYN_FENCE();
+      ROW_FENCE();
     });
     static_for<NJ>([&](auto kc) { st(DYN_DW(bias) + 6 + RB::MD.links[L0 + decltype(kc)::value].dof, bj[decltype(kc)::value]); });
 
@@ -228,7 +230,7 @@ template <typename T, int ROBOT, typename LD, typename ST> struct DynRow {
         if constexpr (!own<L>(c)) st(DYN_M(row, c), T(0));
       });
       st(DYN_DW(gravity) + row, gravity * (Sj[k].a.x * S.I.h.y - Sj[k].a.y * S.I.h.x + Sj[k].l.z * S.I.m));
-      DYN_FENCE();
+      ROW_FENCE();
     });
   }
 

@@ -2,7 +2,7 @@
 // collision primitives' support points with their velocities and normal forces, centre of mass, energy and momentum.
 //
 // One function, env_kinematics<T, ROBOT>, made of five independent parts (the base, the four legs: KinRow) and the sum of their shares.
-// solorl_kin.hip runs a row's parts on four wavefronts (a leg each, the base before the first), one lane per env each; tests/host/kin_main.cpp, compiled by g++ under
+// solorl_kin.hip runs a row's parts on four wavefronts (a leg each, the base before the first), one lane per env each; tests/host/rows_main.cpp, compiled by g++ under
 // SOLO_HOST_SHIM, calls the function as it is.  A row is read through `ld(word)` and written through `st(word, value)`; every word index
 // is a compile-time constant after unrolling, so on the device both are LDS accesses at immediate offsets and nothing is indexed
 // by data.
@@ -15,41 +15,20 @@
 #pragma once
 #include <cstddef>
 
-#include "dynamics.hpp"
+#include "state_row.hpp"
 
 namespace solo {
 
-constexpr int KIN_STATE_WORDS = sizeof(solorl_env_state) / 8;     // 255
 constexpr int KIN_OUT_WORDS = sizeof(solorl_env_kin) / 8;         // 455
 // the part of a state row that is read: pos .. lambda_prev, one contiguous segment (tau lies inside it and is skipped), and the 8-byte
 // word that holds contact_mask
 constexpr int KIN_IN_HEAD_WORDS = (offsetof(solorl_env_state, lambda_prev) + sizeof(double) * SOLORL_STATE_MAX_PRIMS) / 8;   // 73
 constexpr int KIN_IN_MASK_WORD = offsetof(solorl_env_state, contact_mask) / 8;                                              // 254
 constexpr int KIN_IN_WORDS = KIN_IN_HEAD_WORDS + 1;               // staged words per row: the head, then the contact_mask word
-static_assert(sizeof(solorl_env_state) % 8 == 0 && sizeof(solorl_env_kin) % 8 == 0, "rows are whole 8-byte words");
-static_assert(offsetof(solorl_env_state, pos) == 0 && offsetof(solorl_env_state, contact_mask) % 8 == 0, "state row layout");
-static_assert(sizeof(solorl_env_kin) == 3640 && sizeof(solorl_env_state) == 2040, "row sizes of include/solorl.h");
+static_assert(sizeof(solorl_env_kin) == 3640 && offsetof(solorl_env_state, contact_mask) % 8 == 0, "row layouts of include/solorl.h");
 static_assert(SOLORL_KIN_MAX_LINKS == SOLORL_MAX_LINKS && SOLORL_STATE_MAX_PRIMS == NPRIM, "table sizes");
 
-#define KIN_SW(member) ((int)(offsetof(solorl_env_state, member) / 8))
 #define KIN_KW(member) ((int)(offsetof(solorl_env_kin, member) / 8))
-
-// After every link and primitive: no instruction is scheduled across.  A row's 455 outputs are stores nothing waits for and the links'
-// chains are independent, so left alone the scheduler computes far ahead of the stores: the kernel went to 512 registers and spilled.
-#ifdef SOLO_HOST_SHIM
-#define KIN_FENCE() do {} while (0)
-#else
-#define KIN_FENCE() __builtin_amdgcn_sched_barrier(0)
-#endif
-
-// sin and cos by a CALL: a row needs them for every joint angle and its half, and the fp64 routine with its argument reduction is
-// several hundred instructions -- inlined two dozen times it was most of the kernel
-template <typename T> struct SinCos { T s, c; };
-template <typename T> SNI SinCos<T> sincos_call(T x) {
-  SinCos<T> r;
-  sincos_t(x, r.s, r.c);
-  return r;
-}
 
 template <typename T> struct Quat { T x, y, z, w; };
 // p (x) rotation by the half-angle pair (ch, sh) about the link's x (AX = 0) or y axis: the quaternion beside rot_axis<AX>
@@ -61,12 +40,20 @@ template <int AX, typename T> SD Quat<T> quat_rot_axis(const Quat<T>& p, T ch, T
 // sums over links: kinetic and potential energy, mass, linear momentum, angular momentum about the world origin, mass x COM
 template <typename T> struct KinSums { T KE, PE, M; V3<T> P, Lm, MC; };
 constexpr int KIN_SUM_WORDS = 12;
+// a share as KIN_SUM_WORDS words and back (how the device's wavefronts hand their shares to the one that adds them)
+template <typename T> SD void kin_sums_to_words(T* q, const KinSums<T>& A) {
+  q[0] = A.KE; q[1] = A.PE; q[2] = A.M; q[3] = A.P.x; q[4] = A.P.y; q[5] = A.P.z;
+  q[6] = A.Lm.x; q[7] = A.Lm.y; q[8] = A.Lm.z; q[9] = A.MC.x; q[10] = A.MC.y; q[11] = A.MC.z;
+}
+template <typename T> SD KinSums<T> kin_sums_from_words(const T* q) {
+  return KinSums<T>{q[0], q[1], q[2], mk(q[3], q[4], q[5]), mk(q[6], q[7], q[8]), mk(q[9], q[10], q[11])};
+}
 constexpr int KIN_PARTS = 5;          // the base with its twelve points, then one part per leg: independent of each other up to the sums
 
 // One state row's work, in KIN_PARTS independent parts: base() or leg<L>() writes that part's members of the output row and leaves its
 // share of the link sums in S; kin_totals adds the five shares in a fixed order and writes the totals.  The device runs the parts of a
 // row on four wavefronts (the base on the first leg's), the host one after the other: same functions, same order of summation.
-// ld(w): word w of the state row (w a member's KIN_SW offset + index);  st(w, v): word w of the solorl_env_kin row.
+// ld(w): word w of the state row (w a member's STATE_SW offset + index);  st(w, v): word w of the solorl_env_kin row.
 // cmask: the row's contact_mask;  urdf: solorl_config use_urdf_inertia != 0.
 template <typename T, int ROBOT, typename LD, typename ST> struct KinRow {
   using RB = Robot<ROBOT>;
@@ -78,10 +65,10 @@ template <typename T, int ROBOT, typename LD, typename ST> struct KinRow {
   KinSums<T> S;
 
   SD KinRow(LD ld_, ST st_, int cmask_, bool urdf_, T sim_dt_, T gravity_) : ld(ld_), st(st_), cmask(cmask_), urdf(urdf_), sim_dt(sim_dt_), gravity(gravity_) {
-    pos = mk(ld(KIN_SW(pos)), ld(KIN_SW(pos) + 1), ld(KIN_SW(pos) + 2));
-    const T qx = ld(KIN_SW(quat)), qy = ld(KIN_SW(quat) + 1), qz = ld(KIN_SW(quat) + 2), qw = ld(KIN_SW(quat) + 3);
-    v0 = mk(ld(KIN_SW(lin_vel)), ld(KIN_SW(lin_vel) + 1), ld(KIN_SW(lin_vel) + 2));
-    w0 = mk(ld(KIN_SW(ang_vel)), ld(KIN_SW(ang_vel) + 1), ld(KIN_SW(ang_vel) + 2));
+    pos = mk(ld(STATE_SW(pos)), ld(STATE_SW(pos) + 1), ld(STATE_SW(pos) + 2));
+    const T qx = ld(STATE_SW(quat)), qy = ld(STATE_SW(quat) + 1), qz = ld(STATE_SW(quat) + 2), qw = ld(STATE_SW(quat) + 3);
+    v0 = mk(ld(STATE_SW(lin_vel)), ld(STATE_SW(lin_vel) + 1), ld(STATE_SW(lin_vel) + 2));
+    w0 = mk(ld(STATE_SW(ang_vel)), ld(STATE_SW(ang_vel) + 1), ld(STATE_SW(ang_vel) + 2));
     R0 = quat_to_mat(qx, qy, qz, qw);             // the state's quaternion as it is, as the step reads it
     const T qn = rsqrt_fast(qx * qx + qy * qy + qz * qz + qw * qw);
     Q0 = Quat<T>{qx * qn, qy * qn, qz * qn, qw * qn};
@@ -102,12 +89,9 @@ template <typename T, int ROBOT, typename LD, typename ST> struct KinRow {
     st3(KIN_KW(link_com) + 3 * l, c);
     st3(KIN_KW(link_com_vel) + 3 * l, vc);
     st3(KIN_KW(link_ang_vel) + 3 * l, w);
-    // K2 inertia about the COM in link axes: Bullet's box rule (diagonal) or the URDF tensor
-    const T ixx = urdf ? T(LK.inertia_urdf[0]) : T(LK.inertia_box[0]), iyy = urdf ? T(LK.inertia_urdf[1]) : T(LK.inertia_box[1]),
-            izz = urdf ? T(LK.inertia_urdf[2]) : T(LK.inertia_box[2]);
-    const T ixy = urdf ? T(LK.inertia_urdf[3]) : T(0), ixz = urdf ? T(LK.inertia_urdf[4]) : T(0), iyz = urdf ? T(LK.inertia_urdf[5]) : T(0);
+    const LinkInertia<T> I = link_inertia<T, ROBOT, l>(urdf);
     const V3<T> wl = mk(dot(R.c0, w), dot(R.c1, w), dot(R.c2, w));
-    const V3<T> Iw = mul(R, mk(ixx * wl.x + ixy * wl.y + ixz * wl.z, ixy * wl.x + iyy * wl.y + iyz * wl.z, ixz * wl.x + iyz * wl.y + izz * wl.z));
+    const V3<T> Iw = mul(R, mk(I.xx * wl.x + I.xy * wl.y + I.xz * wl.z, I.xy * wl.x + I.yy * wl.y + I.yz * wl.z, I.xz * wl.x + I.yz * wl.y + I.zz * wl.z));
     const T m = T(LK.mass);
     S.KE += T(0.5) * m * dot(vc, vc) + T(0.5) * dot(w, Iw);
     S.PE += m * gravity * c.z;
@@ -115,7 +99,7 @@ template <typename T, int ROBOT, typename LD, typename ST> struct KinRow {
     S.Lm = fma3(cross(c, vc), m, S.Lm) + Iw;
     S.MC = fma3(c, m, S.MC);
     S.M += m;
-    KIN_FENCE();
+    ROW_FENCE();
   }
   // one primitive: support point Pp relative to the base origin, on a link with origin o, angular velocity w, origin velocity vo
   SD void prim(int p, V3<T> Pp, V3<T> o, V3<T> w, V3<T> vo) {
@@ -123,9 +107,9 @@ template <typename T, int ROBOT, typename LD, typename ST> struct KinRow {
     st3(KIN_KW(prim_vel) + 3 * p, vo + cross(w, Pp - o));
     // (divided whether in contact or not, then selected: a branch here would split the row's arithmetic into blocks, and the compiler
     // then sinks every link's energy and momentum terms into the last one, with all links' frames live until there)
-    const T force = ld(KIN_SW(lambda_prev) + p) / sim_dt;
+    const T force = ld(STATE_SW(lambda_prev) + p) / sim_dt;
     st(KIN_KW(prim_force) + p, ((cmask >> p) & 1) ? force : T(0));
-    KIN_FENCE();
+    ROW_FENCE();
   }
 
   // the base link, its twelve points, and the rows a Solo8 does not have (they read 0)
@@ -158,8 +142,8 @@ template <typename T, int ROBOT, typename LD, typename ST> struct KinRow {
     T qd[NQ], sn[NQ], cs[NQ], sh[NQ], ch[NQ];
     static_for<NJ>([&](auto kc) {
       constexpr int j = RB::MD.links[L0 + decltype(kc)::value].dof;
-      const T q = ld(KIN_SW(q) + j);
-      qd[j] = ld(KIN_SW(qd) + j);
+      const T q = ld(STATE_SW(q) + j);
+      qd[j] = ld(STATE_SW(qd) + j);
       const SinCos<T> full = sincos_call(q), half = sincos_call(q * T(0.5));
       sn[j] = full.s; cs[j] = full.c; sh[j] = half.s; ch[j] = half.c;
     });

@@ -36,11 +36,11 @@
 #include <climits>
 #include <cstdint>
 
-#include "../../include/solorl.h"
-
-extern "C" int solorl_fail_(int code, const char* msg);
+#include "row_batch.hpp"            // select_device (and include/solorl.h, solorl_fail_)
 
 namespace {
+
+using solo::select_device;
 
 constexpr int NT = 256;             // threads of every workgroup here
 constexpr int MAX_D = 1024;         // columns (LDS: 4 D + D doubles of partial sums beside the tile)
@@ -213,14 +213,6 @@ __global__ __launch_bounds__(NT) void norm_rew_apply_kernel(float* __restrict__ 
   if (e >= n) return;
   const size_t k = (size_t)r * n + e;
   rew[k] = (float)clipped((double)rew[k] / sqrt(snap[(size_t)r * 3 + 1] + eps), clip);
-}
-
-int select_device(int device_id) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return solorl_fail_(SOLORL_ERR_NODEVICE, "no HIP device available (no CPU fallback)");
-  if (device_id < 0 || device_id >= ndev) return solorl_fail_(SOLORL_ERR_NODEVICE, "device_id out of range");
-  if (hipSetDevice(device_id) != hipSuccess) return solorl_fail_(SOLORL_ERR_HIP, "hipSetDevice");
-  return 0;
 }
 
 // moments of rows x [n][D] values -> the statistics and their per-row snapshots

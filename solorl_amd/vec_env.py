@@ -26,6 +26,7 @@ import torch
 from . import _native
 from .config import SoloConfig, EnvState, InfoSoA, config_from_dict, EPSTAT_FIELDS, EPSTAT_NAMES
 from .normalize import RunningMeanStd, VecNormalizer
+from .rows import mask_arg
 from .state import StateBatch, field_bits, SF_VEL
 
 
@@ -436,13 +437,7 @@ class SoloVecEnv:
     # one launch each on the current stream, no host synchronisation -- capturable in a HIP graph
     def _mask(self, mask):
         """None, or a [N] torch.bool / torch.uint8 tensor on this device -> (tensor kept alive for the call, pointer)"""
-        if mask is None:
-            return None, C.c_void_p(0)
-        if not (mask.is_cuda and mask.device == self.device and mask.dtype in (torch.bool, torch.uint8) and mask.is_contiguous()
-                and tuple(mask.shape) == (self.nenvs,)):
-            raise AssertionError("mask must be a contiguous torch.bool or torch.uint8 [%d] tensor on %s" % (self.nenvs, self.device))
-        m = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
-        return m, C.c_void_p(m.data_ptr())
+        return mask_arg(mask, self.nenvs, self.device)
 
     def _rows(self, name, states):
         if not isinstance(states, StateBatch):
@@ -468,14 +463,7 @@ class SoloVecEnv:
         ``states``: rows to use instead of the handle's current state; without it ``get_states(mask)`` fills an engine-owned StateBatch
         (allocated at the first call, so a HIP graph captured after a warm-up call keeps using it)."""
         from .kinematics import kinematics
-        if states is None:
-            if self._kin_states is None:
-                self._kin_states = StateBatch(self.nenvs, self.device)
-            states = self.get_states(mask, out=self._kin_states)
-        else:
-            self._rows("states", states)
-        m, _ = self._mask(mask)
-        return kinematics(self.cfg, states, m, out)
+        return self._row_query(kinematics, "_kin_states", mask, states, out)
 
     def get_dynamics(self, mask=None, states=None, out=None):
         """Joint-space mass matrix, bias and gravity forces, foot Jacobians with their Jdot v and foot points of every env
@@ -483,14 +471,19 @@ class SoloVecEnv:
         the handle's current state; without it ``get_states(mask)`` fills an engine-owned StateBatch (allocated at the first call, so a
         HIP graph captured after a warm-up call keeps using it)."""
         from .dyn_tensors import dynamics
+        return self._row_query(dynamics, "_dyn_states", mask, states, out)
+
+    def _row_query(self, call, own, mask, states, out):
+        """``call`` (kinematics or dynamics) on ``states``, or on the handle's current state read into the engine-owned StateBatch
+        kept in attribute ``own`` (one per query: a graph captured around one call does not depend on the other's rows)"""
         if states is None:
-            if self._dyn_states is None:
-                self._dyn_states = StateBatch(self.nenvs, self.device)
-            states = self.get_states(mask, out=self._dyn_states)
+            if getattr(self, own) is None:
+                setattr(self, own, StateBatch(self.nenvs, self.device))
+            states = self.get_states(mask, out=getattr(self, own))
         else:
             self._rows("states", states)
         m, _ = self._mask(mask)
-        return dynamics(self.cfg, states, m, out)
+        return call(self.cfg, states, m, out)
 
     def set_states(self, states, mask=None, fields="all"):
         """Writes the member groups ``fields`` (a name, an iterable of names -- pose, vel, joint_pos, joint_vel, contact, history, task,

@@ -1,12 +1,8 @@
-"""Shared by tests/test_dyn_host.py and tests/test_dyn_gpu.py: the stand-alone host program (tests/host/dyn_main.cpp) and the
+"""Shared by tests/test_dyn_host.py and tests/test_dyn_gpu.py: the stand-alone host program (tests/host/rows_main.cpp) and the
 comparisons the rows of solorl_dynamics are held to (check_rows) -- the oracle's dense mass matrix, bias and forward dynamics, the
 rows of solorl_kinematics for the same states, and a restatement of the foot Jacobians and their Jdot v written here in numpy from
 solorl_amd/models/*.json and tests/kin_util.fk (nothing of the engine's source).  Inputs: tests/kin_util.inputs."""
-import atexit
-import os
-import shutil
-import subprocess
-import tempfile
+import functools
 
 import numpy as np
 
@@ -24,54 +20,10 @@ TAU_SEED = 777
 FOOT_PRIMS = (13, 15, 17, 19)
 PERM = np.array([3, 4, 5, 0, 1, 2] + list(range(6, NV)))      # ours [lin, ang, joints] <- the oracle's [ang, lin, joints]
 
-# ---------------------------------------------------------------- the host program
-_EXE = {}
-
-
-def dyn_main(sanitize=False):
-    """Path of tests/host/dyn_main.cpp built by g++ (once per process, in a temporary directory), or None if sanitize is asked for
-    and the sanitizer runtimes do not link here."""
-    if sanitize not in _EXE:
-        d = tempfile.mkdtemp(prefix="dyn_main_")
-        atexit.register(shutil.rmtree, d, ignore_errors=True)
-        cxx = shutil.which("g++")
-        assert cxx, "g++ not found"
-        if sanitize:
-            probe = os.path.join(d, "probe.cpp")
-            open(probe, "w").write("int main() { return 0; }\n")
-            r = subprocess.run([cxx, *ku.SAN, "-o", os.path.join(d, "probe"), probe], capture_output=True)
-            if r.returncode != 0 or subprocess.run([os.path.join(d, "probe")], capture_output=True).returncode != 0:
-                _EXE[sanitize] = None
-                return None
-        exe = os.path.join(d, "dyn_main_san" if sanitize else "dyn_main")
-        cmd = [cxx, "-O1", "-g1", "-std=c++17", "-DSOLO_HOST_SHIM", "-I" + ku.HOST, *(ku.SAN if sanitize else []), "-o", exe,
-               os.path.join(ku.HOST, "dyn_main.cpp")]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-4000:]
-        _EXE[sanitize] = exe
-    return _EXE[sanitize]
-
-
-def run_dyn_main(cfg, states, sanitize=False):
-    """states: sequence of EnvState -> float64 [n, ROW_WORDS] of the host program's rows"""
-    exe = dyn_main(sanitize)
-    with tempfile.TemporaryDirectory() as d:
-        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(bytes(cfg)); f.write(np.array([len(states), 0], np.int32).tobytes())
-            for s in states:
-                f.write(bytes(s))
-        r = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
-        assert "runtime error" not in r.stderr and "ERROR: AddressSanitizer" not in r.stderr, r.stderr[-4000:]
-        return np.fromfile(fout, np.float64).reshape(len(states), ROW_WORDS)
-
-
-def member(rows, name):
-    """view of member `name` of solorl_env_dyn in rows [n, ROW_WORDS] (numpy)"""
-    off, shape = MEMBERS[name]
-    n = int(np.prod(shape))
-    return rows[:, off // 8: off // 8 + n].reshape((rows.shape[0],) + tuple(shape))
+# the host program (tests/kin_util.rows_main) asked for the rows of solorl_dynamics, and a member's view of them
+dyn_main = ku.rows_main
+run_dyn_main = functools.partial(ku.run_rows_main, "dyn", ROW_WORDS)
+member = functools.partial(ku.rows_member, MEMBERS)
 
 
 def no_damping(cfg):

@@ -1,8 +1,9 @@
 """Shared by tests/test_kin_host.py and tests/test_kin_gpu.py: the seeded inputs of the solorl_kinematics checks, the stand-alone host
-program (tests/host/kin_main.cpp) and the three references its rows are compared with -- the oracle's prim_points and
+program (tests/host/rows_main.cpp, which tests/dyn_util.py runs too) and the three references its rows are compared with -- the oracle's prim_points and
 energy_momentum, and a forward kinematics written here in numpy from solorl_amd/models/*.json (nothing of the engine's source)."""
 import atexit
 import ctypes as C
+import functools
 import json
 import os
 import shutil
@@ -35,11 +36,11 @@ def kin_cfg(robot, urdf):
 _EXE = {}
 
 
-def kin_main(sanitize=False):
-    """Path of tests/host/kin_main.cpp built by g++ (once per process, in a temporary directory), or None if sanitize is asked for
+def rows_main(sanitize=False):
+    """Path of tests/host/rows_main.cpp built by g++ (once per process, in a temporary directory), or None if sanitize is asked for
     and the sanitizer runtimes do not link here."""
     if sanitize not in _EXE:
-        d = tempfile.mkdtemp(prefix="kin_main_")
+        d = tempfile.mkdtemp(prefix="rows_main_")
         atexit.register(shutil.rmtree, d, ignore_errors=True)
         cxx = shutil.which("g++")
         assert cxx, "g++ not found"
@@ -50,35 +51,40 @@ def kin_main(sanitize=False):
             if r.returncode != 0 or subprocess.run([os.path.join(d, "probe")], capture_output=True).returncode != 0:
                 _EXE[sanitize] = None
                 return None
-        exe = os.path.join(d, "kin_main_san" if sanitize else "kin_main")
-        cmd = [cxx, "-O1", "-g1", "-std=c++17", "-DSOLO_HOST_SHIM", "-I" + HOST, *(SAN if sanitize else []), "-o", exe, os.path.join(HOST, "kin_main.cpp")]
+        exe = os.path.join(d, "rows_main_san" if sanitize else "rows_main")
+        cmd = [cxx, "-O1", "-g1", "-std=c++17", "-DSOLO_HOST_SHIM", "-I" + HOST, *(SAN if sanitize else []), "-o", exe, os.path.join(HOST, "rows_main.cpp")]
         r = subprocess.run(cmd, capture_output=True, text=True)
         assert r.returncode == 0, r.stderr[-4000:]
         _EXE[sanitize] = exe
     return _EXE[sanitize]
 
 
-def run_kin_main(cfg, states, sanitize=False):
-    """states: sequence of EnvState -> float64 [n, ROW_WORDS] of the host program's rows (and its stderr)"""
-    exe = kin_main(sanitize)
+def run_rows_main(query, row_words, cfg, states, sanitize=False):
+    """query: "kin" or "dyn"; states: sequence of EnvState -> float64 [n, row_words] of the host program's rows"""
+    exe = rows_main(sanitize)
     with tempfile.TemporaryDirectory() as d:
         fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
         with open(fin, "wb") as f:
             f.write(bytes(cfg)); f.write(np.array([len(states), 0], np.int32).tobytes())
             for s in states:
                 f.write(bytes(s))
-        r = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
+        r = subprocess.run([exe, query, fin, fout], capture_output=True, text=True, timeout=120)
         assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
         assert "runtime error" not in r.stderr and "ERROR: AddressSanitizer" not in r.stderr, r.stderr[-4000:]
-        return np.fromfile(fout, np.float64).reshape(len(states), ROW_WORDS)
+        return np.fromfile(fout, np.float64).reshape(len(states), row_words)
 
 
-def member(rows, name):
-    """view of member `name` of solorl_env_kin in rows [n, ROW_WORDS] (numpy)"""
-    off, shape = MEMBERS[name]
+def rows_member(members, rows, name):
+    """view of member `name` (offset and shape from `members`) in rows [n, row words] (numpy)"""
+    off, shape = members[name]
     n = int(np.prod(shape)) if shape else 1
     v = rows[:, off // 8: off // 8 + n]
     return v.reshape((rows.shape[0],) + tuple(shape)) if shape else v[:, 0]
+
+
+kin_main = rows_main
+run_kin_main = functools.partial(run_rows_main, "kin", ROW_WORDS)
+member = functools.partial(rows_member, MEMBERS)      # of solorl_env_kin
 
 
 # ---------------------------------------------------------------- inputs

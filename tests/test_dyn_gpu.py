@@ -1,6 +1,6 @@
 """solorl_dynamics on the GPU (include/solorl.h; solorl_amd/dyn_tensors.py, SoloVecEnv.get_dynamics).
 
-The kernel's rows against the rows of the stand-alone host program (tests/host/dyn_main.cpp: the same per-env function compiled by
+The kernel's rows against the rows of the stand-alone host program (tests/host/rows_main.cpp: the same per-env function compiled by
 g++) to |err| <= 1e-10 max(1, |value|), the mass matrix to 1e-10 sqrt(M_aa M_bb), and through the five comparisons of
 tests/dyn_util.py check_rows on the device's own rows (the oracle's mass matrix, bias and forward dynamics, the device's own
 solorl_kinematics rows, the numpy restatement of the foot Jacobians) -- for both robots and both inertia rules, n = 1, 5, one more than

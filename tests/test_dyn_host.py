@@ -1,5 +1,5 @@
 """solorl_dynamics on the CPU: csrc/dyn_tensors.hpp -- the per-env function the HIP kernel runs, one lane per env -- compiled by g++
-into a stand-alone program (tests/host/dyn_main.cpp) and held, for both robots and both inertia rules, on the 32 random poses and 32
+into a stand-alone program (tests/host/rows_main.cpp) and held, for both robots and both inertia rules, on the 32 random poses and 32
 oracle rollout states of tests/kin_util.inputs, to the five comparisons of tests/dyn_util.py check_rows:
   1. mass_matrix against the oracle's dense M (|err| <= 1e-10 sqrt(M_aa M_bb)), symmetric to the bit, exact zeros, Cholesky;
   2. bias against the oracle's h at the default damping and at damping 0; gravity against h at rest, (0, 0, m g) and dV/dq;

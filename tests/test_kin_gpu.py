@@ -1,6 +1,6 @@
 """solorl_kinematics on the GPU (include/solorl.h; solorl_amd/kinematics.py, SoloVecEnv.get_kinematics).
 
-The kernel's rows against the rows of the stand-alone host program (tests/host/kin_main.cpp: the same per-env function compiled by
+The kernel's rows against the rows of the stand-alone host program (tests/host/rows_main.cpp: the same per-env function compiled by
 g++) to |err| <= 1e-10 max(1, |value|), and through the three comparisons of tests/test_kin_host.py on the device's own rows (oracle
 prim_points, oracle energy_momentum, numpy forward kinematics and its central differences) -- for both robots and both inertia rules,
 n = 1, 5, one more than the kernel's envs per workgroup, and 67 (four workgroups, the last one ragged).  Then the call's contract:

@@ -1,5 +1,5 @@
 """solorl_kinematics on the CPU: csrc/kinematics.hpp -- the per-env function the HIP kernel runs, one lane per env -- compiled by g++
-into a stand-alone program (tests/host/kin_main.cpp) and compared, for both robots and both inertia rules, on 32 random poses and 32
+into a stand-alone program (tests/host/rows_main.cpp) and compared, for both robots and both inertia rules, on 32 random poses and 32
 states of oracle rollouts with contacts, three ways (tests/kin_util.py check_rows):
   1. prim_point against the oracle's prim_points;
   2. kinetic, potential, lin_mom, ang_mom against the oracle's energy_momentum of the same state;
