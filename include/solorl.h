@@ -33,6 +33,8 @@
  *                             env), starts from a chosen state distribution, branching one env into many, resetting a chosen subset,
  *                             saving / restoring a batch and logging a batch reduce to.  Row i is env i of the handle; a byte mask
  *                             selects envs, SOLORL_SF_* bits select member groups on write.  No host synchronisation: capturable.
+ *   solorl_set_perturbation / solorl_perturb / solorl_get_perturbation : random base kicks at random intervals, drawn on the device from a
+ *                             Philox stream per env and applied in place by one launch between two steps (no reference counterpart)
  *   solorl_normalize_obs / solorl_normalize_rewards <- agents/running_mean_std.py:73-127 (VecNormalize: _obfilt :109-116, the reward half
  *                             of step :98-105) with RunningMeanStd.update (:18-39), which agents/ppo/envs.py:25-26 wraps round the vec-env:
  *                             running statistics in caller-owned device memory, fp64, a fixed number of launches for any number of rows
@@ -48,7 +50,7 @@
  * (HIP, the device the handle was created on); the engine never retains them past the stream
  * work of the call.  All work is enqueued on the `stream` argument (a hipStream_t passed as
  * void*; NULL = the null stream) and no entry point synchronises the host except
- * solorl_create/solorl_destroy/solorl_get_state/solorl_set_state.
+ * solorl_create/solorl_destroy/solorl_get_state/solorl_set_state/solorl_set_perturbation.
  *
  * Error convention: every function returns 0 on success or a negative code; the message is
  * available from solorl_last_error() (thread-local).  A per-env numeric failure (NaN/Inf state)
@@ -265,6 +267,44 @@ int solorl_set_states(solorl_env* env, const uint8_t* mask, const solorl_env_sta
                       uint32_t fields, void* stream);
 int solorl_reset_masked(solorl_env* env, const uint8_t* mask /* [N] device, not NULL */,
                         float* obs_out /* [N*O] or NULL */, void* stream);
+
+/* Random base kicks drawn and applied on the device (no reference counterpart; what domain-randomised training calls "pushes").  A kick
+ * is a change of the base's world-frame velocity, as SoloVecEnv.push() makes one through solorl_get_states / solorl_set_states; here
+ * every env receives kicks at random intervals from a Philox stream of its own, by ONE launch per control step that touches six state
+ * words of the kicked envs and nothing of the others.  The step kernels know nothing of it: a caller issues solorl_perturb between two
+ * steps (SoloVecEnv does, right before each step launch, once a perturbation is set).
+ * solorl_set_perturbation: allocates (first call) and initialises two per-env arrays owned by the handle and indexed by ENV id -- the
+ *   countdown to the env's next kick and the number of kicks it has drawn -- and latches *p; calling it again restarts the schedule
+ *   from block 0; p == NULL switches the perturbation off and frees the arrays (solorl_destroy frees them too).  Synchronises the host,
+ *   as solorl_create does: not capturable.  SOLORL_ERR_INVALID for an interval outside 1 <= min <= max or a negative or non-finite
+ *   amplitude (the handle's perturbation stays as it was).
+ * solorl_perturb: one launch on `stream`, no allocation, no host synchronisation (capturable).  Per env: countdown -= 1; at 0 the env draws
+ *   kick j (j = its kick count), applies it, counts it and draws its next countdown.  kick_out ([N][6]: lin x y z, ang x y z; or NULL)
+ *   receives the kick applied by THIS call, zeros for an env that was not kicked.  An env that is not kicked has no state word written;
+ *   of a kicked env only the components with a non-zero amplitude are (v + 0.0 would turn -0.0 into +0.0): a zero amplitude is an exact
+ *   no-op and its kick_out entry is +0.0.  SOLORL_ERR_STATE before solorl_set_perturbation or before the handle's first reset.
+ * solorl_get_perturbation: copies the two arrays out in one launch (either pointer may be NULL, not both).
+ * Draws (all of them a function of seed, global env id, the call count and *p -- never of the state or the actions):
+ *   key      the handle's seed (lo, hi), as for the env's own stream
+ *   counter  (gid_lo, gid_hi, block, 4) with gid = env_id_offset + i.  The env's own stream uses 1, 2 and 3 in the last word with
+ *            rng_counter in the third; a kick never reads or advances rng_counter.
+ *   block 0          word 0 -> the first countdown
+ *   block 1 + 2 j    words 0, 1, 2 -> kick j's lin x, y, z; word 3 -> the countdown to kick j + 1
+ *   block 2 + 2 j    words 0, 1, 2 -> kick j's ang x, y, z
+ *   uniform    u = (word >> 8) * 2^-24; component = (2 u - 1) * max, in double (2 u - 1 is exact: one rounding)
+ *   countdown  interval_min + word % (interval_max - interval_min + 1)
+ *   addition   v <- T(double(v) + kick), T the engine's arithmetic type: one rounding, bitwise what push() gives for the same kick as a
+ *              float64 tensor on fp32 and fp64 handles alike
+ *   schedule   counts solorl_perturb calls and ignores episode boundaries: auto-resets and solorl_reset_masked leave it alone
+ *   shards     keyed by global env id: W handles of N envs at offsets k N kick like one handle of W N envs */
+typedef struct solorl_perturbation {
+  int32_t interval_min, interval_max;   /* control steps between two kicks of an env, uniform in [min, max]; 1 <= min <= max */
+  double  max_lin_vel[3];               /* a kick adds U(-m, m) to lin_vel[i]; 0 = that component is never touched */
+  double  max_ang_vel[3];               /* the same for ang_vel[i] */
+} solorl_perturbation;
+int solorl_set_perturbation(solorl_env* env, const solorl_perturbation* p /* host; NULL = switch off */);
+int solorl_perturb(solorl_env* env, double* kick_out /* [N][6] device, or NULL */, void* stream);
+int solorl_get_perturbation(solorl_env* env, int32_t* countdown_out /* [N] device */, uint32_t* kicks_out /* [N] device */, void* stream);
 
 /* Derived quantities of a batch of state rows: link poses and velocities, the collision primitives' support points with their
  * velocities and normal forces, centre of mass, energy and momentum -- what the reference reads from PyBullet (getLinkState,

@@ -18,6 +18,7 @@ SYMBOLS = ("solorl_default_config", "solorl_create", "solorl_destroy", "solorl_d
            "solorl_compute_returns", "solorl_ppo_loss", "solorl_policy_act", "solorl_ppo_grad_stage1", "solorl_ppo_grad_stage2", "solorl_ppo_grad_count", "solorl_ppo_clip_adam", "solorl_last_error", "solorl_version",
            "solorl_abi_version", "solorl_step_act", "solorl_ppo_scratch_count", "solorl_step_n", "solorl_rollout",
            "solorl_get_states", "solorl_set_states", "solorl_reset_masked",
+           "solorl_set_perturbation", "solorl_perturb", "solorl_get_perturbation",
            "solorl_norm_scratch_count", "solorl_normalize_obs", "solorl_normalize_rewards", "solorl_kinematics", "solorl_dynamics")
 
 
@@ -46,6 +47,10 @@ class AdamState(C.Structure):               # solorl_adam_state
 
 class PpoStage1(C.Structure):               # solorl_ppo_stage1
     _fields_ = [(n, C.c_void_p) for n in ("xt0", "c_xt1", "c_xt2", "c_g1", "c_g2", "c_gh", "a_xt1", "a_xt2", "a_g1", "a_g2", "a_gh", "partials")]
+
+
+class Perturbation(C.Structure):            # solorl_perturbation
+    _fields_ = [("interval_min", C.c_int32), ("interval_max", C.c_int32), ("max_lin_vel", C.c_double * 3), ("max_ang_vel", C.c_double * 3)]
 
 
 class SoloRLError(RuntimeError):
@@ -81,6 +86,12 @@ def lib():
         L.solorl_set_states.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.solorl_reset_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         for f in (L.solorl_get_states, L.solorl_set_states, L.solorl_reset_masked):
+            f.restype = C.c_int
+        # device-side kicks: the struct is a host pointer (None = off), kick_out / countdown_out / kicks_out are device pointers
+        L.solorl_set_perturbation.argtypes = [C.c_void_p, C.POINTER(Perturbation)]
+        L.solorl_perturb.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.solorl_get_perturbation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        for f in (L.solorl_set_perturbation, L.solorl_perturb, L.solorl_get_perturbation):
             f.restype = C.c_int
         L.solorl_get_property.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]
         L.solorl_ppo_loss.argtypes = [C.c_void_p] * 8 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

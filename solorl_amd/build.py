@@ -10,7 +10,7 @@ ROOT = os.path.dirname(HERE)
 INC = [os.path.join(ROOT, "include", f) for f in ("solorl.h", "solorl_model_data.h")]
 # translation units -> what each depends on (the env engine takes ~2.5 min to compile, the PPO kernels seconds: separate objects)
 UNITS = {
-    "solorl_hip.hip": [os.path.join(HERE, "csrc", f) for f in ("solorl_hip.hip", "dynamics.hpp", "spatial.hpp")] + INC,
+    "solorl_hip.hip": [os.path.join(HERE, "csrc", f) for f in ("solorl_hip.hip", "dynamics.hpp", "spatial.hpp", "perturb.hpp")] + INC,
     "solorl_ppo.hip": [os.path.join(HERE, "csrc", "solorl_ppo.hip"), INC[0]],
     "solorl_norm.hip": [os.path.join(HERE, "csrc", f) for f in ("solorl_norm.hip", "row_batch.hpp")] + INC[:1],
     "solorl_kin.hip": [os.path.join(HERE, "csrc", f) for f in ("solorl_kin.hip", "row_batch.hpp", "kinematics.hpp", "state_row.hpp", "dynamics.hpp", "spatial.hpp")] + INC,

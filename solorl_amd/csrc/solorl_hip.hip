@@ -27,6 +27,7 @@
 
 #include "../../include/solorl.h"
 #include "dynamics.hpp"
+#include "perturb.hpp"
 
 using namespace solo;
 
@@ -1171,6 +1172,46 @@ __global__ void __launch_bounds__(256) set_states_kernel(T* __restrict__ sf, int
 }
 static_assert(offsetof(solorl_env_state, pos) == 0, "set_states_kernel derives xyprev from a row's words 0 and 1");
 
+// ---- device-side kicks (solorl_perturb; the draws are perturb.hpp's): one thread per storage slot.  The six velocity fields of a slot
+// group are [field][4] blocks (SX), so neighbouring threads read and write neighbouring words; countdown / kicks / kick_out are indexed
+// by ENV id (the slot's own number, or under contact-count sorting the id the slot carries, as the state kernels read it).  An env that
+// is not kicked has no state word loaded or stored; of a kicked one only the components with a non-zero amplitude are.
+template <typename T>
+__global__ void __launch_bounds__(256) perturb_kernel(T* __restrict__ sf, const int* __restrict__ si, int NF, int N, int linear_ids, int fv, int fw,
+                                                      PerturbParams pp, int* __restrict__ countdown, unsigned* __restrict__ kicks,
+                                                      double* __restrict__ kick_out) {
+  const unsigned slot = blockIdx.x * 256u + threadIdx.x;
+  if (slot >= (unsigned)N) return;
+  const unsigned env = linear_ids ? slot : (unsigned)si[SX(I_ENVID, slot, NI)];
+  if (env >= (unsigned)N) return;
+  double kick[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  int c = countdown[env] - 1;
+  if (c <= 0) {
+    const unsigned j = kicks[env];
+    c = perturb_kick(pp, pp.id0 + (long long)env, j, kick);
+    kicks[env] = j + 1u;
+#pragma unroll
+    for (int k = 0; k < 6; k++)
+      if (pp.max_vel[k] != 0.0) {
+        const idx_t at = SX((k < 3 ? fv : fw - 3) + k, slot, NF);
+        sf[at] = (T)((double)sf[at] + kick[k]);
+      }
+  }
+  countdown[env] = c;
+  if (kick_out) {
+#pragma unroll
+    for (int k = 0; k < 6; k++) kick_out[(size_t)env * 6 + k] = kick[k];
+  }
+}
+
+__global__ void __launch_bounds__(256) perturb_state_kernel(const int* __restrict__ countdown, const unsigned* __restrict__ kicks, int N,
+                                                            int* __restrict__ countdown_out, unsigned* __restrict__ kicks_out) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= (unsigned)N) return;
+  if (countdown_out) countdown_out[i] = countdown[i];
+  if (kicks_out) kicks_out[i] = kicks[i];
+}
+
 // ---- fused GAE / discounted returns (agents/ppo/storage.py:35-55): one thread per env walks the rollout
 // backwards; every access is coalesced across envs.  HBM-bound: 16 B per (t, env) sample.
 __global__ void returns_kernel(const float* __restrict__ rew, float* __restrict__ val, const float* __restrict__ msk,
@@ -1297,6 +1338,9 @@ struct solorl_env {
   int simds = 1024;          // SIMDs of the device (4 per CU): grids up to this size have a SIMD per wavefront
   int pipe_override = -1;    // SOLORL_PGS_PIPE=0/1 (dev A/B)
   int helper_override = -1;  // SOLORL_HELPER_WAVE=0/1: pin the helper wavefront (duo_kernel_team) off / on
+  // solorl_set_perturbation: the kick schedule, [N] each, indexed by env id (null: no perturbation set)
+  int* pert_countdown = nullptr; unsigned* pert_kicks = nullptr;
+  PerturbParams pert{};
 };
 
 namespace {
@@ -1761,6 +1805,8 @@ int solorl_destroy(solorl_env* h) {
   if (h->perm) hipFree(h->perm);
   if (h->dyn) hipFree(h->dyn);
   if (h->stab) hipFree(h->stab);
+  if (h->pert_countdown) hipFree(h->pert_countdown);
+  if (h->pert_kicks) hipFree(h->pert_kicks);
   delete h;
   return 0;
 }
@@ -2008,6 +2054,65 @@ int solorl_reset_masked(solorl_env* h, const uint8_t* mask, float* obs_out, void
   if (!mask) return fail(SOLORL_ERR_INVALID, "solorl_reset_masked: null mask");
   if (!h->reset_called) return fail(SOLORL_ERR_STATE, "solorl_reset_masked: needs a handle that has been reset");
   return launch_reset<true>(h, mask, obs_out, stream);
+}
+
+// ---- device-side kicks (perturb_kernel above; the draw rules are in include/solorl.h)
+int solorl_set_perturbation(solorl_env* h, const solorl_perturbation* p) {
+  if (!h) return fail(SOLORL_ERR_INVALID, "solorl_set_perturbation: null handle");
+  HIP_TRY(hipSetDevice(h->device));
+  if (!p) {                                    // switch off
+    if (h->pert_countdown) HIP_TRY(hipFree(h->pert_countdown));
+    h->pert_countdown = nullptr;
+    if (h->pert_kicks) HIP_TRY(hipFree(h->pert_kicks));
+    h->pert_kicks = nullptr;
+    return 0;
+  }
+  if (p->interval_min < 1 || p->interval_max < p->interval_min)
+    return fail(SOLORL_ERR_INVALID, "solorl_set_perturbation: the interval must satisfy 1 <= interval_min <= interval_max");
+  PerturbParams pp{};
+  for (int k = 0; k < 6; k++) {
+    const double m = k < 3 ? p->max_lin_vel[k] : p->max_ang_vel[k - 3];
+    if (!std::isfinite(m) || m < 0.0) return fail(SOLORL_ERR_INVALID, "solorl_set_perturbation: amplitudes must be finite and >= 0");
+    pp.max_vel[k] = m;
+  }
+  pp.seed_lo = (unsigned)h->seed; pp.seed_hi = (unsigned)(h->seed >> 32); pp.id0 = h->id0;
+  pp.interval_min = p->interval_min; pp.span = (unsigned)p->interval_max - (unsigned)p->interval_min + 1u;
+  const size_t N = (size_t)h->N;
+  if (!h->pert_countdown && hipMalloc(&h->pert_countdown, sizeof(int) * N) != hipSuccess) { h->pert_countdown = nullptr; return fail(SOLORL_ERR_HIP, "solorl_set_perturbation: hipMalloc countdown"); }
+  if (!h->pert_kicks && hipMalloc(&h->pert_kicks, sizeof(unsigned) * N) != hipSuccess) { h->pert_kicks = nullptr; return fail(SOLORL_ERR_HIP, "solorl_set_perturbation: hipMalloc kicks"); }
+  std::vector<int> first(N);
+  for (size_t i = 0; i < N; i++) first[i] = perturb_first_countdown(pp, pp.id0 + (long long)i);
+  HIP_TRY(hipDeviceSynchronize());             // (a restart must not overtake perturb launches still in flight on another stream)
+  HIP_TRY(hipMemcpy(h->pert_countdown, first.data(), sizeof(int) * N, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(h->pert_kicks, 0, sizeof(unsigned) * N));
+  HIP_TRY(hipDeviceSynchronize());
+  h->pert = pp;
+  return 0;
+}
+
+int solorl_perturb(solorl_env* h, double* kick_out, void* stream) {
+  if (!h) return fail(SOLORL_ERR_INVALID, "solorl_perturb: null handle");
+  if (!h->pert_countdown || !h->pert_kicks) return fail(SOLORL_ERR_STATE, "solorl_perturb: no perturbation set (solorl_set_perturbation)");
+  if (!h->reset_called) return fail(SOLORL_ERR_STATE, "solorl_perturb: needs a handle that has been reset");
+  HIP_TRY(hipSetDevice(h->device));
+  with_type(h, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(perturb_kernel<T>, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (T*)h->sf, (const int*)h->si, h->L.NF, h->N,
+                       h->sort ? 0 : 1, h->L.v, h->L.w, h->pert, h->pert_countdown, h->pert_kicks, kick_out);
+  });
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int solorl_get_perturbation(solorl_env* h, int32_t* countdown_out, uint32_t* kicks_out, void* stream) {
+  if (!h) return fail(SOLORL_ERR_INVALID, "solorl_get_perturbation: null handle");
+  if (!countdown_out && !kicks_out) return fail(SOLORL_ERR_INVALID, "solorl_get_perturbation: null out arrays");
+  if (!h->pert_countdown || !h->pert_kicks) return fail(SOLORL_ERR_STATE, "solorl_get_perturbation: no perturbation set (solorl_set_perturbation)");
+  HIP_TRY(hipSetDevice(h->device));
+  hipLaunchKernelGGL(perturb_state_kernel, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const int*)h->pert_countdown,
+                     (const unsigned*)h->pert_kicks, h->N, (int*)countdown_out, (unsigned*)kicks_out);
+  HIP_TRY(hipGetLastError());
+  return 0;
 }
 
 }  // extern "C"

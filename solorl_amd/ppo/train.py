@@ -10,6 +10,9 @@ Differences that come with the GPU engine (documented, not behavioural):
     baseEnv.py:65), episode_length, success, dr/* sums, as means over the episodes finished per log interval;
   * args.normalize_obs / args.normalize_returns switch on the reference's VecNormalize (agents/running_mean_std.py:73-127; its launcher
     hard-codes both off) on the device, single process only; the checkpoint's `ob_rms` then carries the statistics, as the reference's;
+  * args.push_interval / args.push_max_vel / args.push_max_yaw_rate (train_ppo.py --push-interval LO[:HI] ...; no reference counterpart)
+    kick every training env's base at random intervals, drawn and applied on the device in front of every step launch of the eager
+    and of the captured rollout alike (SoloVecEnv.set_perturbation); the schedule is keyed by global env id, so ranks kick like one batch;
   * multi-GPU: one process per GPU (`python -m torch.distributed.run --nproc-per-node W ...`), envs
     sharded by rank (global env id = rank*N + i), flat-bucket RCCL gradient all-reduce (ppo.py).
 """
@@ -79,7 +82,8 @@ def train(args, config, env_constructor=None, writer=None):
         raise NotImplementedError("--normalize-obs / --normalize-returns need a single process (world size %d): the running statistics "
                                   "are not merged across ranks" % world)
     envs = make_vec_envs(config, N, env_constructor, args.gamma, device, seed=args.seed, env_id_offset=rank * N,
-                         norm_obs=norm_obs, norm_ret=norm_ret)
+                         norm_obs=norm_obs, norm_ret=norm_ret, push_interval=getattr(args, "push_interval", None),
+                         push_max_vel=getattr(args, "push_max_vel", 0.0), push_max_yaw_rate=getattr(args, "push_max_yaw_rate", 0.0))
     action_dim = envs.action_space.shape[0]
     base = torch.load(args.base_checkpoint) if getattr(args, "base_checkpoint", None) else None
     actor_critic = Policy(envs.observation_space.shape, envs.action_space, base, {"hidden_size": args.hidden_size}).to(device)

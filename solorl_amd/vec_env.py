@@ -10,6 +10,8 @@
       norm_obs / norm_ret -- running statistics on the device (normalize.py, include/solorl.h solorl_normalize_obs / solorl_normalize_rewards)
   get_states(mask) -> StateBatch, set_states(states, mask, fields), reset_masked(mask) -> obs, push(dv, mask)   (the whole batch's state as
       one device array, include/solorl.h solorl_get_states ...: no reference counterpart)
+  set_perturbation(interval, max_lin_vel, max_ang_vel), perturb(), last_kick, perturbation_state()   (random base kicks drawn and applied on
+      the device, in front of every step launch while set: include/solorl.h solorl_set_perturbation / solorl_perturb)
   get_kinematics(mask) -> KinBatch   (link poses, support points of the collision primitives with velocity and normal force, centre of
       mass, energy, momentum of every env: include/solorl.h solorl_kinematics, kinematics.py)
   get_dynamics(mask) -> DynBatch   (joint-space mass matrix, bias and gravity forces, foot Jacobians with their Jdot v of every env:
@@ -139,6 +141,7 @@ class SoloVecEnv:
         self._kin_states = None     # engine-owned StateBatch of get_kinematics(), allocated at its first call
         self._dyn_states = None     # engine-owned StateBatch of get_dynamics(), allocated at its first call
         self._kbuf = {}             # engine-owned [K, ...] rows of step_n_inplace / rollout_inplace, per K
+        self.last_kick = None       # [N, 6] float64: the kick of the last perturb(), allocated by set_perturbation(); None = no perturbation set
         self._info_c = InfoSoA(ep_stats=self._ep_stats.data_ptr(), applied_torque=None if self._tau is None else self._tau.data_ptr(),
                                **{k: self._info[k].data_ptr() for k in _INFO_KEYS})
         # VecNormalize (agents/running_mean_std.py:73-127; the reference's launcher passes ob=False, ret=False: agents/ppo/envs.py:26):
@@ -216,6 +219,65 @@ class SoloVecEnv:
     def _stream(self):
         return _native.stream(self.device)
 
+    # ---- device-side kicks (include/solorl.h solorl_set_perturbation / solorl_perturb / solorl_get_perturbation)
+    def set_perturbation(self, interval, max_lin_vel=0.0, max_ang_vel=0.0):
+        """Random base kicks during stepping: every env is kicked every ``interval`` control steps (an int, or a (lo, hi) pair: uniform
+        in lo..hi, drawn per env and kick), the kick adding U(-m, m) per component to the base's world-frame linear / angular velocity
+        (``max_lin_vel`` / ``max_ang_vel``: a scalar or a 3-sequence; 0 = that component is never touched).  Drawn on the device from a
+        Philox stream per env (the draw table is in include/solorl.h); calling it again restarts the schedule, ``interval=None``
+        switches it off.  Synchronises the host; call it before capturing a HIP graph of steps.
+
+        While a perturbation is set, step(), step_inplace() and step_act_inplace() issue perturb() right before their step launch, so a
+        control step is  observation -> policy -> kick -> physics:  a kick is a disturbance of the transition, the policy sees it in the
+        next observation (also in step_act_inplace, whose tail computes the next action from the observation AFTER the kicked step).
+        step_n*, rollout_inplace run K steps in one launch and cannot take kicks in between: they raise, and rollout_supported() is False."""
+        if interval is None:
+            with torch.cuda.device(self.device):
+                _native.check(self.L.solorl_set_perturbation(self._h, None))
+            self.last_kick = None
+            return
+        lo, hi = (interval, interval) if np.isscalar(interval) else interval
+        if int(lo) != lo or int(hi) != hi:
+            raise AssertionError("interval must be an int or a pair of ints, got %r" % (interval,))
+
+        def amp(x):
+            v = np.broadcast_to(np.asarray(x, dtype=np.float64), (3,)) if np.ndim(x) == 0 else np.asarray(x, dtype=np.float64)
+            if v.shape != (3,):
+                raise AssertionError("an amplitude is a scalar or a 3-sequence, got %r" % (x,))
+            return (C.c_double * 3)(*v.tolist())
+        p = _native.Perturbation(int(lo), int(hi), amp(max_lin_vel), amp(max_ang_vel))
+        with torch.cuda.device(self.device):
+            _native.check(self.L.solorl_set_perturbation(self._h, C.byref(p)))
+        if self.last_kick is None:
+            self.last_kick = torch.zeros((self.nenvs, 6), dtype=torch.float64, device=self.device)
+        else:
+            self.last_kick.zero_()
+
+    def perturb(self):
+        """One solorl_perturb launch on the current stream: every env's countdown goes down by one, the envs that reach 0 are kicked.
+        -> last_kick [N, 6] (lin x y z, ang x y z; zeros for the envs not kicked by this call).  No host synchronisation: capturable."""
+        with torch.cuda.device(self.device):
+            _native.check(self.L.solorl_perturb(self._h, None if self.last_kick is None else C.c_void_p(self.last_kick.data_ptr()), self._stream()))
+        return self.last_kick
+
+    def perturbation_state(self):
+        """(countdown int32 [N], kicks drawn so far [N] as int64 -- the engine's uint32 widened) of the kick schedule, by env id"""
+        cd = torch.empty((self.nenvs,), dtype=torch.int32, device=self.device)
+        kc = torch.empty((self.nenvs,), dtype=torch.int32, device=self.device)     # (uint32 words: torch has no arithmetic on that type)
+        with torch.cuda.device(self.device):
+            _native.check(self.L.solorl_get_perturbation(self._h, C.c_void_p(cd.data_ptr()), C.c_void_p(kc.data_ptr()), self._stream()))
+        return cd, kc.to(torch.int64) & 0xFFFFFFFF
+
+    def _kick(self):
+        """the kick of a control step, in front of its step launch"""
+        if self.last_kick is not None:
+            self.perturb()
+
+    def _no_kicks(self, name):
+        if self.last_kick is not None:
+            raise _native.SoloRLError("%s with a perturbation set: K steps in one launch cannot take kicks between the steps "
+                                      "(rollout_supported() is False; step one at a time, or set_perturbation(None))" % name)
+
     def reset(self):
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_reset(self._h, C.c_void_p(self._obs.data_ptr()), self._stream()))
@@ -230,6 +292,7 @@ class SoloVecEnv:
             raise AssertionError("actions must be [%d, %d]" % (self.nenvs, self.act_dim))   # solo.py:226
         a = actions.detach().to(device=self.device, dtype=torch.float32).contiguous()
         self._steps_issued += 1
+        self._kick()
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_step(self._h, C.c_void_p(a.data_ptr()), C.c_void_p(self._obs.data_ptr()),
                                              C.c_void_p(self._rew.data_ptr()), C.c_void_p(self._done.data_ptr()),
@@ -266,6 +329,7 @@ class SoloVecEnv:
         a = self._raw("actions", actions, (self.nenvs, self.act_dim))
         o, r, d, po, pr, pd = self._outputs((), (self._obs, self._rew, self._done), obs_out, rew_out, done_out)
         self._steps_issued += 1
+        self._kick()
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_step(self._h, a, po, pr, pd, C.byref(self._info_c), self._stream()))
         if self._norm is not None:
@@ -291,6 +355,7 @@ class SoloVecEnv:
         pl = self._per_env("logp_out", logp_out, ())
         pn = C.c_void_p(0) if noise is None else self._raw("noise", noise, (self.nenvs, self.act_dim))
         self._steps_issued += 1
+        self._kick()
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_step_act(self._h, a, po, pr, pd, C.byref(self._info_c), C.byref(params), pn, pv, pa, pl, self._stream()))
         if self._norm_ret:
@@ -336,6 +401,7 @@ class SoloVecEnv:
         """step_inplace for K steps: actions [K, N, A] (float32, contiguous, on this device); returns views of engine-owned rows
         (overwritten by the next call with the same K) -- or writes observations [K, N, O] / rewards [K, N] or [K, N, 1] / done flags
         (uint8 [K, N]) straight into caller-owned tensors such as rollout-storage rows.  Host-side checks only, capturable."""
+        self._no_kicks("step_n")
         K = int(actions.shape[0]) if actions.dim() == 3 else 0
         if K < 1:
             raise AssertionError("actions must be [K, %d, %d] with K >= 1" % (self.nenvs, self.act_dim))
@@ -350,8 +416,9 @@ class SoloVecEnv:
         return o, r, d, b["info"]
 
     def rollout_supported(self, params):
-        """solorl_rollout (K closed-loop steps in one launch) on this handle: the prerequisites of solorl_step_act."""
-        return self.step_act_supported(params)
+        """solorl_rollout (K closed-loop steps in one launch) on this handle: the prerequisites of solorl_step_act, and no perturbation
+        set (kicks come between two step launches)."""
+        return self.last_kick is None and self.step_act_supported(params)
 
     def rollout_inplace(self, actions, params, noise, value_out, logp_out, obs_out=None, rew_out=None, done_out=None, policy_after_last=False):
         """K closed-loop steps in one launch (solorl_rollout), in rollout-storage rows: actions [K (+1), N, A] -- row 0 drives the
@@ -359,6 +426,7 @@ class SoloVecEnv:
         first action of the next window); noise [K (+1), N, A] or None (actions = the mean); value_out / logp_out [K (+1), N] or
         [K (+1), N, 1], rows from 1 written; obs_out [K, N, O], rew_out [K, N] or [K, N, 1], done_out uint8 [K, N] as step_n_inplace."""
         self._no_policy_tail("rollout_inplace")
+        self._no_kicks("rollout_inplace")
         pal = 1 if policy_after_last else 0
         R = int(actions.shape[0]) if actions.dim() == 3 else 0
         K = R - pal
@@ -540,14 +608,20 @@ class SoloVecEnv:
 
 
 def make_vec_envs(config, num_envs, env_constructor=None, gamma=0.99, device=None, training=True, seed=1,
-                  env_id_offset=0, norm_obs=False, norm_ret=False, clipob=10., cliprew=10., epsilon=1e-8):
+                  env_id_offset=0, norm_obs=False, norm_ret=False, clipob=10., cliprew=10., epsilon=1e-8,
+                  push_interval=None, push_max_vel=0.0, push_max_yaw_rate=0.0):
     """Signature of agents/ppo/envs.py:14.  ``env_constructor`` (the per-process gym env class of the
     reference) is accepted for call-site compatibility and ignored.  ``norm_obs`` / ``norm_ret`` are VecNormalize's ``ob`` /
     ``ret`` (agents/running_mean_std.py:79; the reference's launcher passes False, False, and so do the defaults here) with its
     ``clipob``, ``cliprew``, ``epsilon``; ``gamma`` is the discount of its return accumulator and means something with ``norm_ret``.
-    ``training=False`` is its eval() (agents/ppo/envs.py:27-28)."""
+    ``training=False`` is its eval() (agents/ppo/envs.py:27-28).
+    ``push_interval`` (an int or a (lo, hi) pair of control steps; None = no kicks, and nothing is allocated or launched): random kicks of
+    up to ``push_max_vel`` m/s on the base's world x and y velocity and ``push_max_yaw_rate`` rad/s on its yaw rate, in front of every
+    step (SoloVecEnv.set_perturbation)."""
     envs = SoloVecEnv(config, num_envs, device=device, seed=seed, env_id_offset=env_id_offset, norm_obs=norm_obs, norm_ret=norm_ret,
                       clipob=clipob, cliprew=cliprew, gamma=gamma, epsilon=epsilon)
+    if push_interval is not None:
+        envs.set_perturbation(push_interval, (push_max_vel, push_max_vel, 0.0), (0.0, 0.0, push_max_yaw_rate))
     if not training:
         envs.eval()
     return envs

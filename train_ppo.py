@@ -10,6 +10,17 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
+def push_interval(text):
+    """--push-interval LO[:HI] -> (lo, hi): control steps between two kicks of an env, 1 <= lo <= hi"""
+    try:
+        parts = [int(x) for x in text.split(":")]
+    except ValueError:
+        parts = []
+    if len(parts) not in (1, 2) or parts[0] < 1 or parts[-1] < parts[0]:
+        raise argparse.ArgumentTypeError("expected LO or LO:HI with 1 <= LO <= HI, got %r" % text)
+    return parts[0], parts[-1]
+
+
 def get_ppo_args(argv=None):
     p = argparse.ArgumentParser("PPO args")
     p.add_argument("--num-agents", type=int, default=32)          # envs PER GPU
@@ -44,6 +55,10 @@ def get_ppo_args(argv=None):
     p.add_argument("--task", type=str, default=None)
     p.add_argument("--normalize-obs", action="store_true", default=False, help="running observation normalisation (VecNormalize ob=True)")
     p.add_argument("--normalize-returns", action="store_true", default=False, help="running return normalisation of the rewards (VecNormalize ret=True, discount --gamma)")
+    p.add_argument("--push-interval", type=push_interval, default=None, metavar="LO[:HI]",
+                   help="kick every training env's base every LO..HI control steps (drawn on the device; default: no kicks)")
+    p.add_argument("--push-max-vel", type=float, default=0.0, help="a kick adds U(-V, V) m/s to the base's world x and y velocity")
+    p.add_argument("--push-max-yaw-rate", type=float, default=0.0, help="... and U(-W, W) rad/s to its yaw rate")
     p.add_argument("--num-steps", type=int, default=None, help="rollout length (default: episode_length, train_ppo.py:62-63)")
     return p.parse_args(argv)
 
