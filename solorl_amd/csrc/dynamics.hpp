@@ -52,11 +52,12 @@ constexpr double DISC_RIM = 0.1;                         // sine of the tilt at 
 // [1] the sub-steps, [2] last sub-step -> end, [3] whole kernel in s_memrealtime ticks (100 MHz), [4] sum over the sub-steps of
 // the slots the wave swept, [5] the maximum over the sub-steps of its largest contact count
 #if defined(SOLO_WAVE_TIMING) && !defined(SOLO_HOST_SHIM)
-constexpr int SOLO_WT_WAVES = 65536, SOLO_WT_FIELDS = 30;    // [6..15]: the ten intervals between the kernel's stamps; [16..25], [28..29]: per-phase
+constexpr int SOLO_WT_WAVES = 65536, SOLO_WT_FIELDS = 32;    // [6..15]: the ten intervals between the kernel's stamps; [16..25], [28..31]: per-phase
 __device__ unsigned long long solo_wave_times[SOLO_WT_WAVES][SOLO_WT_FIELDS];                                // sums over the sub-steps (SOLO_PT)
 // phase stamps of substep_team: after a full drain of the wave's memory counters (timing build only), lane 0 adds the ticks since
 // the previous stamp to phase slot i of the workgroup's LDS accumulators; step_team writes them out with its own stamps
-__shared__ unsigned long long solo_pt_acc[12];     // [10]: the main wavefront's wait at barrier D, [11]: the helper's work behind D (duo kernel)
+__shared__ unsigned long long solo_pt_acc[16];     // [10]: the main wavefront's wait at barrier D, [11]: the helper's work behind D (duo kernel),
+                                                   // [12]: its wait at barrier C2 (duo kernel), [13]: the sweep's set-up, a part of [7]; [14], [15] unused
 #define SOLO_PT_DECL() long long pt_last_ = 0
 #define SOLO_PT_BEGIN() do { __builtin_amdgcn_s_waitcnt(0); pt_last_ = clock64(); } while (0)
 #define SOLO_PT(i) do { __builtin_amdgcn_s_waitcnt(0); if (threadIdx.x == 0) { const long long n_ = clock64(); solo_pt_acc[i] += (unsigned long long)(n_ - pt_last_); } pt_last_ = clock64(); } while (0)
@@ -159,7 +160,7 @@ extern __shared__ __attribute__((aligned(16))) unsigned char solo_smem_sym[];
 // with the constant (check_lds_base, solorl_hip.hip: SOLORL_ERR_HIP instead of wrong physics), and tests/test_abi.py reads the same
 // number from the built code object.  Nothing is checked on the device.
 #if defined(SOLO_WAVE_TIMING)
-constexpr unsigned SOLO_LDS_BASE = 96;                   // behind solo_pt_acc[12] -- which only the TEAM kernel references: the timing build
+constexpr unsigned SOLO_LDS_BASE = 128;                  // behind solo_pt_acc[16] -- which only the TEAM kernel references: the timing build
                                                          // is team-mode only (check_lds_base rejects the lane-mode kernel there, by design)
 #else
 constexpr unsigned SOLO_LDS_BASE = 0;
@@ -1680,6 +1681,60 @@ SNI_SCALAR void phase_finish_team(const PhysParams<T> pp, const LDS lds, int t) 
   if (two) emit(r1, c1, meta1, mu1);
 }
 
+// duo_kernel_team: phase_finish_team as two halves, one per wavefront, behind barrier C -- the main wavefront calls SECOND = false
+// (lane t: row t and position t), the helper SECOND = true (row t + 16 and position t + 16), and both pass barrier C2 before the sweep
+// reads a row.  The expressions are phase_finish_team's, per row: a row's record, its A_LAM word and its impulse come out the same bits
+// whichever wavefront emits them.  Each call writes only ITS rows (core and A_LAM), zero at ITS positions of lam that the team leaves
+// empty, and its rows' impulses at their positions (never an empty one): every word has one writer.  Both read hdr and bc, which
+// nobody writes between C and C2 (the audit is at substep_team_helper).  No barrier in here, no scratch, no access outside LDS.
+template <typename T, int ROBOT, typename LDS, bool SECOND>
+SNI_SCALAR void duo_finish_rows(const PhysParams<T> pp, const LDS lds, int t) {
+  using TRW = TeamRows<T, LDS>;
+  const int col = lds.lane;
+  const T* hdr = lds.hdr();
+  const int nlt = (int)hdr[0], nc = (int)hdr[LDS::LANES];          // (team_counts without the wave-wide sweep extent)
+  const int nrows = nlt + 3 * nc, rfric = nlt + nc;
+  T* const lam = TRW::lam(col);
+  const T* bc = TRW::bc(col);
+  const int r = SECOND ? t + 16 : t;                               // this lane's row and, by the same number, its position
+  // impulses of the positions this team leaves empty (the wave may sweep them as null rows)
+  if (r < TRW::TR && TRW::row_of(r, nlt, nc) < 0) lam[r * 4] = T(0);
+  if (r >= nrows) return;
+  Sym6<T> Lam;
+#pragma unroll
+  for (int i = 0; i < 6; i++)
+#pragma unroll
+    for (int j = 0; j < 6; j++) Lam.m[i][j] = bc[i * 6 + j];
+  const SV<T> ub{{bc[36], bc[37], bc[38]}, {bc[39], bc[40], bc[41]}};
+  T c[ROW_CORE];
+  lds.load_core(r, c);
+  const int meta = (int)lds.A(r, LDS::A_META);
+  const T mu = lds.A(r, LDS::A_MU);
+  // (phase_finish_team's lambda, word for word: as a lambda it does not carry this function's target attribute, so the constexpr index
+  // functions E_J / E_B are inlined into it -- written straight into the body they are CALLED, eighteen times, with the record in scratch)
+  auto emit = [&](int r, const T (&c)[ROW_CORE], int meta, T mu) __attribute__((always_inline)) {
+    const int leg = (meta >> 5) & 3;
+    const T* ql = bc + 42 + leg * 3;
+    SV<T> W; T rhs, dinv;
+    finish_row(c, meta, Lam, ub, ql[0], ql[1], ql[2], pp, W, rhs, dinv);
+    const bool fr = r >= rfric;
+    const T sB = fr ? mu : T(1);
+    const T isB = rcp_fast(sB);
+    const T sJ = dinv * isB;
+    T o[ROW_CORE];
+#pragma unroll
+    for (int e = 0; e < 9; e++) o[E_J(e)] = c[e] * sJ;                       // J': base 0..5, leg 6..8
+    o[E_B(0)] = W.a.x * sB; o[E_B(1)] = W.a.y * sB; o[E_B(2)] = W.a.z * sB; o[E_B(3)] = W.l.x * sB; o[E_B(4)] = W.l.y * sB; o[E_B(5)] = W.l.z * sB;
+    o[E_B(6)] = c[15] * sB; o[E_B(7)] = c[16] * sB; o[E_B(8)] = c[17] * sB;
+    o[E_RHS] = rhs * isB;               // finish_row's rhs already carries 1/diag
+    o[E_LEG] = T(leg);
+    lds.store_core(r, o);
+    lds.A(r, LDS::A_LAM) = (fr && pp.cone()) ? rcp_fast(pp.resid_thr * sJ) : pp.resid_thr * sJ;       // K7 in the row's units: phase_finish_team
+    lam[TRW::pos_of(r, nlt, nc) * 4] = c[13];      // warm-start impulse (0 for friction / limit rows)
+  };
+  emit(r, c, meta, mu);
+}
+
 // exchange between the two 8-lane halves of a 16-lane team (values are uniform within a half)
 template <typename T> SD T half_swap(T x) {
   if constexpr (sizeof(T) == 4) return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0x140, 0xF, 0xF, true));   // row_mirror
@@ -1737,6 +1792,9 @@ template <typename T, typename LDS, int LIM, int NNS, int NFS, bool EXIT, bool P
 SNI void pgs_team_variant(int iterations_v, const LDS lds, int t) {
   // (the residual threshold of K7 reaches the sweep through the rows: phase_finish_team stores it per row, in the row's units)
   using TRW = TeamRows<T, LDS>;
+#if defined(SOLO_WAVE_TIMING)
+  const long long wt_su0_ = clock64();
+#endif
   const int itv = __builtin_amdgcn_readfirstlane(iterations_v);          // function arguments arrive in VGPRs: make the sweep loop scalar
   const int iterations = itv & 0xFFFF;
   const bool warm_on = (itv >> 30) & 1;                                  // (bit 30: the rows carry warm-start impulses, phase_pgs_team)
@@ -1907,6 +1965,10 @@ SNI void pgs_team_variant(int iterations_v, const LDS lds, int t) {
   // in the cold block, from the slots' changes kept in registers (2.5 instructions per cone slot and two per sweep less on the common
   // path; the block is entered in ~1/6 of the heavy wavefronts' sweeps: DESIGN section 4, "The K7 gate").
   constexpr bool GATE = EXIT && CONE && NFS >= SOLO_K7_GATE_MIN_NFS && sizeof(T) == 4;
+#if defined(SOLO_WAVE_TIMING)
+  __builtin_amdgcn_s_waitcnt(0);
+  if (threadIdx.x == 0) solo_pt_acc[13] += (unsigned long long)(clock64() - wt_su0_);
+#endif
 #pragma unroll 1                                                    // (unrolled by two: no change, measured)
   for (int it = iterations; it > 0; it--) {                         // (a uniform down-counter: no vector instruction; the early exit zeroes it)
 #if defined(SOLO_WAVE_TIMING) && defined(SOLO_SWEEP_STATS)
@@ -2312,13 +2374,13 @@ SNI_SCALAR void duo_integrate_base(CH ch, const PhysParams<T> pp, const LDS lds,
 // wavefront's leg rows -- the leg sum, the base solve and the leg rates up to barrier C: the calls substep_team makes in the
 // classic kernel, in its order, on the same operands (phase_base_lead is the classic kernel's one instantiation; it reads neither
 // lam_prev nor nstride), and behind barrier D the base's pose integration with the NEXT sub-step's R0 while the main wavefront
-// integrates the joints.  Four barriers per sub-step and one, Z, behind the last; none under a predicate.
-//   main   : sin/cos | A | leg dynamics | B | leg rows                      | C | row finish, sweep | D | joints, impulse cache |
-//   helper :         | A | front        | B | leg sum, base solve, leg rates | C |  (idle)           | D | base pose, next R0    |
+// integrates the joints.  Five barriers per sub-step and one, Z, behind the last; none under a predicate.
+//   main   : sin/cos | A | leg dynamics | B | leg rows                      | C | rows 0..15 finished | C2 | sweep  | D | joints, impulse cache |
+//   helper :         | A | front        | B | leg sum, base solve, leg rates | C | rows 16..  finished | C2 | (idle) | D | base pose, next R0    |
 // Barriers per role, step of frame_skip = F sub-steps (every one on a path that depends on kernel arguments only):
-//             A                     B                    C                  D                          Z               total
-//   main      F (substep_team)      F (phase_leg_rt)     F (duo_join_rows)  F (duo_join_rows)          1 (step_team)   4 F + 1
-//   helper    F (here)              F (here)             F (duo_helper_rates)  F (duo_join_rows, here)  1 (step_team)   4 F + 1
+//             A                  B                  C                     C2                 D                  Z               total
+//   main      F (substep_team)   F (phase_leg_rt)   F (duo_join_rows)     F (duo_join_rows)  F (duo_join_rows)  1 (step_team)   5 F + 1
+//   helper    F (here)           F (here)           F (duo_helper_rates)  F (duo_join_rows)  F (duo_join_rows)  1 (step_team)   5 F + 1
 // A is behind the main wavefront's joint integrate of the previous sub-step (joints, impulse cache, the row storage the sweep read)
 //   and its sin / cos of this one, and behind the helper's base pose and C.R0 (the first sub-step's R0: step_team, main).
 // B hands the front's results (selectors, support points, distances, the base contacts' rows, the base link terms) to the main
@@ -2335,6 +2397,14 @@ SNI_SCALAR void duo_integrate_base(CH ch, const PhysParams<T> pp, const LDS lds,
 //   them next behind the NEXT sub-step's B, which the main wavefront reaches only after its integrate; the front between the next
 //   A and B writes none of them (it does write C.Ibase / C.pbase, which the main wavefront never reads).  An idle team's
 //   hdr[0] = hdr[LN] = 0 is stored here, above C, where substep_team stores it in the classic kernel: phase_finish_team reads it.
+// Between C and C2 (audit of every LDS word either side touches there; both sides run duo_finish_rows, lane t of the main wavefront
+//   for row t and impulse position t, lane t of the helper for row t + 16 and position t + 16):
+//   both read      hdr[0], hdr[LN] (the team's counts), bc[0..53] (Lam, u*_base, the leg rates: the helper's, above C)
+//   main writes    rows 0..15 in place (core and A_LAM; read by the same lane first), lam[p] = 0 at the empty positions p < 16,
+//                  lam[pos_of(r)] for its rows r < 16 (a position that HAS a row, below or above 16)
+//   helper writes  rows 16.. in place, lam[p] = 0 at the empty positions p >= 16, lam[pos_of(r)] for its rows r >= 16
+//   A row has one lane; a position is either empty (zeroed by the lane with its number) or has one row (written by that row's
+//   lane): no word is written twice or written on one side and read on the other.  The sweep, behind C2, is the first reader.
 // Between D and the next A, or Z (audit of every LDS word either side touches there):
 //   helper reads   hdr[2 LN .. 7 LN] (the sweep's w, final at D), C.ub (its own, above C), C.ps.pos and the quaternion
 //   helper writes  C.ps.w, C.ps.v, C.ps.pos, the quaternion, C.R0 (not behind the last sub-step)
@@ -2367,6 +2437,8 @@ SD void substep_team_helper(const PhysParams<T> pp, const LDS& lds, int t, bool 
   if (threadIdx.x == 64) solo_pt_acc[4] += (unsigned long long)(clock64() - wt_h0_);
 #endif
   duo_helper_rates<T, ROBOT, LDS, CH>(ch, pp, lds, t, valid);            // leg rates, barrier C (the main wavefront's: duo_join_rows)
+  duo_finish_rows<T, ROBOT, LDS, true>(pp, lds, t);                      // rows 16.. beside the main wavefront's rows 0..15
+  duo_join_rows<T, ROBOT>();                                             // barrier C2: every row is finished
   duo_join_rows<T, ROBOT>();                                             // barrier D: the sweep's w is final
 #if defined(SOLO_WAVE_TIMING)
   __builtin_amdgcn_s_waitcnt(0);
@@ -2433,8 +2505,15 @@ SD int substep_team(const PhysParams<T> pp, T* lam_prev, unsigned nstride, const
     if (valid) phase_legrates_team<T, ROBOT, LDS, CH>(ch, pp, lds, t);
     SOLO_PT(5);
   }
-  phase_finish_team<T, ROBOT, LDS>(pp, lds, t);
-  SOLO_PT(6);
+  if constexpr (DUO) {
+    duo_finish_rows<T, ROBOT, LDS, false>(pp, lds, t);       // rows 0..15; the helper finishes rows 16.. meanwhile
+    SOLO_PT(6);
+    duo_join_rows<T, ROBOT>();             // barrier C2: every row is finished, every impulse position set
+    SOLO_PT(12);                           // (timing build: the wait at barrier C2)
+  } else {
+    phase_finish_team<T, ROBOT, LDS>(pp, lds, t);
+    SOLO_PT(6);
+  }
   phase_pgs_team<T, ROBOT, LDS>(pp.iterations, pp.warm != T(0), pp.resid_thr >= T(0), pp.pgs_pipe(), pp.cone(), lds, t);
   SOLO_PT(7);
   if constexpr (DUO) {

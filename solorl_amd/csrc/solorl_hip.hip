@@ -649,7 +649,7 @@ SD void step_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict_
   long long wts_[11];
   for (int i_ = 0; i_ < 11; i_++) wts_[i_] = 0;
   const long long wr0_ = wall_clock64();
-  if (threadIdx.x < 12) solo::solo_pt_acc[threadIdx.x] = 0;
+  if (threadIdx.x < 16) solo::solo_pt_acc[threadIdx.x] = 0;
   __syncthreads();
   wts_[0] = clock64();
 #endif
@@ -677,9 +677,9 @@ SD void step_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict_
   SubCtx<T, ROBOT>& C = ch.get();
   T* const psv = reinterpret_cast<T*>(&C.ps);
   if constexpr (DUO) {
-    // Workgroup barriers of a step, per role: 4 x frame_skip + 1 (A, B, C and D of every sub-step, then Z; main: A in substep_team, B in
-    // phase_leg_rt, C and D in duo_join_rows, Z in duo_join_rows below the sub-step loop; helper: A and B in substep_team_helper, C in
-    // duo_helper_rates, D in duo_join_rows, Z in duo_join_rows below its loop) -- plus the one behind the LDS poison fill above when
+    // Workgroup barriers of a step, per role: 5 x frame_skip + 1 (A, B, C, C2 and D of every sub-step, then Z; main: A in substep_team, B in
+    // phase_leg_rt, C, C2 and D in duo_join_rows, Z in duo_join_rows below the sub-step loop; helper: A and B in substep_team_helper, C in
+    // duo_helper_rates, C2 and D in duo_join_rows, Z in duo_join_rows below its loop) -- plus the one behind the LDS poison fill above when
     // that test hook is on, and, in a -DSOLO_WAVE_TIMING build, the one behind the counters' reset.  All of them sit on paths that
     // depend on kernel arguments only; the helper returns behind Z.
     if (blk * 4u >= (unsigned)N) return;              // a workgroup of the padded grid without an env: both wavefronts leave here
@@ -888,7 +888,7 @@ SD void step_team(T* __restrict__ sf, int* __restrict__ si, const T* __restrict_
     w_[3] = (unsigned long long)(wall_clock64() - wr0_);
     for (int i_ = 0; i_ < 10; i_++) w_[6 + i_] = (unsigned long long)(wts_[i_ + 1] > wts_[i_] && wts_[i_] ? wts_[i_ + 1] - wts_[i_] : 0);
     for (int i_ = 0; i_ < 10; i_++) w_[16 + i_] = solo::solo_pt_acc[i_];       // per-phase sums over the sub-steps (SOLO_PT)
-    for (int i_ = 10; i_ < 12; i_++) w_[18 + i_] = solo::solo_pt_acc[i_];      // (26, 27: the sweep's counters)
+    for (int i_ = 10; i_ < 14; i_++) w_[18 + i_] = solo::solo_pt_acc[i_];      // (26, 27: the sweep's counters)
   }
 #endif
 }

@@ -27,7 +27,7 @@ a = torch.rand(64, N, 12, device="cuda:0", generator=g) * 2 - 1
 for t in range(450): env.step_inplace(a[t % 64])
 L = _native.lib()
 nw = ((N + 3) // 4 + 7) & ~7
-F = 30
+F = 32
 recs, wall = [], []
 buf = (C.c_ulonglong * (nw * F))()
 ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -68,6 +68,7 @@ if hw:      # duo_kernel_team: the stamps are the main wavefront's; the helper r
     # to the end of the base solve (its leg rates, ~0.6 us per step, end in barrier C and are not timed)
     phases[0], phases[1], phases[2] = "R0 + sin/cos", "barrier A", "front || legs (to barrier B) + leg rows"
     phases[3], phases[4], phases[5] = "barrier C (wait for helper)", "HELPER: leg sum + base solve", "(leg rates: helper, untimed)"
+    phases[6] = "row finish (rows 0..15)"     # duo_finish_rows; the helper finishes rows 16.. beside it, up to barrier C2
     phases[8] = "joints + impulse cache"      # behind barrier D; the base pose and the next R0 are the helper's (slot 11)
 phases.append("  of the legs: dynamics above the lsel read (not drained)")
 print("helper wavefront: %s (SOLORL_HELPER_WAVE=0/1 pins it)" % ("on" if hw else "off"))
@@ -75,10 +76,11 @@ print("phases of the sub-steps, summed over a step's %d sub-steps (us; mean over
 for i, n_ in enumerate(phases):
     print("  %-28s %7.2f | %7.2f" % (n_, us(R[:, :, 16 + i].mean()), us(R[:, :, 16 + i][slow_].mean())))
 if hw:
-    for i, n_ in ((28, "barrier D (wait for helper)"), (29, "HELPER: base pose + next R0")):      # slots 10 and 11 of the accumulators
+    for i, n_ in ((28, "barrier D (wait for helper)"), (29, "HELPER: base pose + next R0"), (30, "barrier C2 (wait for helper)")):      # slots 10 to 12 of the accumulators
         print("  %-28s %7.2f | %7.2f" % (n_, us(R[:, :, i].mean()), us(R[:, :, i][slow_].mean())))
-    main_ = R[:, :, 16:25].sum(axis=2) - R[:, :, 20] + R[:, :, 28]      # the main wavefront's own chain: every slot but the helper's two
+    main_ = R[:, :, 16:25].sum(axis=2) - R[:, :, 20] + R[:, :, 28] + R[:, :, 30]      # the main wavefront's own chain: every slot but the helper's two
     print("  main wavefront's chain (all but the helper's slot) %7.2f | %7.2f" % (us(main_.mean()), us(main_[slow_].mean())))
+print("  of the PGS sweep: set-up, call to first sweep %7.2f | %7.2f" % (us(R[:, :, 31].mean()), us(R[:, :, 31][slow_].mean())))
 bw = 10.0
 edges = np.arange(0, us(tot.max()) + bw, bw)
 h, _ = np.histogram(us(tot), bins=edges)
