@@ -44,6 +44,10 @@
  *   solorl_dynamics        <- what the reference's MPC / WBC envs ask Pinocchio for and Isaac-style vec-envs expose as
  *                             jacobian / mass_matrix tensors: joint-space mass matrix, bias and gravity forces, foot Jacobians and their
  *                             Jdot v of a whole batch of state rows, one launch
+ *   solorl_shape_reward    <- no reference counterpart (its reward is baseEnv.py's five terms): sixteen shaped reward terms -- base motion,
+ *                             torques, joint acceleration, action rate, power, foot slip, clearance, contact force, air time, collisions,
+ *                             command tracking -- of a whole batch of state rows added to the step's reward, one launch, with the
+ *                             per-env memory these terms need in caller-owned device rows
  *   solorl_destroy         <- agents/ppo/envs.py:129-135 (close)
  *
  * Plain pointers and sizes only; no torch types.  All array arguments are DEVICE pointers
@@ -381,6 +385,64 @@ typedef struct solorl_env_dyn {
 int solorl_dynamics(const solorl_config* cfg, const solorl_env_state* states /* [n] DEVICE rows */,
                     const uint8_t* mask /* [n] device, or NULL = all */, int n,
                     solorl_env_dyn* out /* [n] DEVICE rows */, int device_id, void* stream);
+
+/* Shaped reward terms of a batch of state rows: the foot, smoothness and energy terms that legged-RL tasks add to a task reward (Isaac-style
+ * legged_gym reward functions; no reference counterpart: the reference pays stand, joint pose, torque, balance and progress only).  A third
+ * row query beside solorl_kinematics and solorl_dynamics: a pure function of its arguments, no handle; ONE kernel launch on `stream`, no
+ * allocation, no host synchronisation (capturable).  A caller issues it after a step, on the state AFTER that step (solorl_get_states), with
+ * the actions, the done flags and the reward of that step; the terms that need the previous step (joint acceleration, action rate, feet air
+ * time) keep it in `mem`, one caller-owned device row per env that this call reads and rewrites.
+ * Notation: R0 = the rotation matrix of the row's quaternion as it is (what solorl_kinematics uses); v_b = R0^T lin_vel, w_b = R0^T ang_vel,
+ * g_b = R0^T (0, 0, -1); j runs over the robot's 8 or 12 joints; dtc = sim_dt * frame_skip; for foot f = FL, FR, HL, HR: p_f, u_f, F_f are
+ * solorl_env_kin's prim_point, prim_vel and prim_force of the foot primitive 13 + 2 f (the same functions compute them), c_f that
+ * primitive's contact_mask bit; a = this call's action row (raw, unclipped).
+ *    k  name               value
+ *    0  lin_vel_z          v_b.z^2
+ *    1  ang_vel_xy         w_b.x^2 + w_b.y^2
+ *    2  orientation        g_b.x^2 + g_b.y^2
+ *    3  base_height        (pos.z - base_height_target)^2
+ *    4  torques            sum_j tau_j^2                    (the row's tau)
+ *    5  joint_vel          sum_j qd_j^2
+ *    6  joint_acc          valid ? sum_j ((qd_j - prev_qd_j) / dtc)^2 : 0
+ *    7  action_rate        valid ? sum_j (a_j - prev_action_j)^2 : 0
+ *    8  power              sum_j |tau_j qd_j|
+ *    9  foot_slip          sum_f c_f (u_f.x^2 + u_f.y^2)
+ *   10  foot_clearance     sum_f (1 - c_f) (p_f.z - foot_clearance_target)^2 sqrt(u_f.x^2 + u_f.y^2)
+ *   11  foot_force         sum_f max(0, F_f - foot_force_max)
+ *   12  feet_air_time      sum_f first_f (air_f - air_time_target)
+ *   13  collision          number of set contact_mask bits among the robot's primitives other than the four foot primitives
+ *   14  tracking_lin_vel   exp(-((v_b.x - cmd_lin_vel[0])^2 + (v_b.y - cmd_lin_vel[1])^2) / tracking_sigma)
+ *   15  tracking_yaw_rate  exp(-(w_b.z - cmd_yaw_rate)^2 / tracking_sigma)
+ *   Term 12, in order: air_f = air_time[f] + dtc; first_f = valid && c_f && !(prev_contact bit f); the term reads air_f; afterwards
+ *   air_time[f] = c_f ? 0 : air_f.  All arithmetic is fp64, sums in index order.  No scaling by dt is applied: the weights carry it.
+ * A live row with done == 0: terms_out[i][k] = the raw value of every term, whatever the weights; s = sum_k weight[k] term_k in index
+ *   order; reward[i] = (float)((double)reward[i] + s), rounded once; ep_sum[k] += weight[k] term_k; prev_action = a, prev_qd = qd,
+ *   prev_contact = (c_f), valid = 1.
+ * A live row with done != 0 (the row holds the post-reset state and the terminal reward is the reference's override): reward[i] is
+ *   untouched, terms_out[i][:] = 0; ep_out[0][i] += 1 and ep_out[1 + k][i] += ep_sum[k] (the contract of ep_stats: the caller reduces
+ *   and zeroes); ep_sum, air_time, prev_contact and valid are zeroed (prev_action and prev_qd are not read while valid is 0).
+ * A masked row (mask byte 0): nothing of it is read or written, in any array.
+ * Null cfg, p, states, actions or mem, n < 1, a robot that is neither SOLORL_ROBOT_*, a non-finite weight or parameter,
+ * tracking_sigma <= 0, sim_dt <= 0 (or non-finite), frame_skip < 1: SOLORL_ERR_INVALID, the message starts with
+ * "solorl_shape_reward:" (checked before any HIP call). */
+#define SOLORL_SHAPE_TERMS 16
+typedef struct solorl_shape_params {
+  double weight[SOLORL_SHAPE_TERMS];           /* 0 = term off */
+  double base_height_target, foot_clearance_target, foot_force_max, air_time_target;
+  double cmd_lin_vel[2], cmd_yaw_rate, tracking_sigma;   /* base frame; sigma > 0 */
+} solorl_shape_params;
+typedef struct solorl_env_shape {              /* per-env memory, caller-owned DEVICE rows, 45 words = 360 B */
+  double prev_action[12], prev_qd[12], air_time[4], ep_sum[SOLORL_SHAPE_TERMS];
+  int32_t prev_contact /* bit f: foot f touched at the previous call */, valid /* 0: no previous step in this episode */;
+} solorl_env_shape;
+int solorl_shape_reward(const solorl_config* cfg, const solorl_shape_params* p,
+                        const solorl_env_state* states /* [n] DEVICE rows, the state AFTER the step */,
+                        const uint8_t* mask /* [n] or NULL */, int n,
+                        const float* actions /* [n][act_dim], the raw actions of that step */,
+                        const uint8_t* done /* [n] or NULL = none */,
+                        solorl_env_shape* mem /* [n], in/out */, float* reward /* [n] in/out, or NULL */,
+                        double* terms_out /* [n][16] raw term values, or NULL */,
+                        double* ep_out /* [17][n] field-major, or NULL */, int device_id, void* stream);
 
 /* Fused return computation over a rollout of T steps x N envs (device arrays, time-major [t][n]).
  * use_gae != 0:  value_preds[T][:] = next_value;  delta_t = r_t + gamma V_{t+1} m_{t+1} - V_t;

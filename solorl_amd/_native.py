@@ -19,7 +19,8 @@ SYMBOLS = ("solorl_default_config", "solorl_create", "solorl_destroy", "solorl_d
            "solorl_abi_version", "solorl_step_act", "solorl_ppo_scratch_count", "solorl_step_n", "solorl_rollout",
            "solorl_get_states", "solorl_set_states", "solorl_reset_masked",
            "solorl_set_perturbation", "solorl_perturb", "solorl_get_perturbation",
-           "solorl_norm_scratch_count", "solorl_normalize_obs", "solorl_normalize_rewards", "solorl_kinematics", "solorl_dynamics")
+           "solorl_norm_scratch_count", "solorl_normalize_obs", "solorl_normalize_rewards", "solorl_kinematics", "solorl_dynamics",
+           "solorl_shape_reward")
 
 
 class PolicyParams(C.Structure):            # solorl_policy_params
@@ -118,6 +119,10 @@ def lib():
         L.solorl_kinematics.restype = C.c_int
         L.solorl_dynamics.argtypes = [C.POINTER(SoloConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.solorl_dynamics.restype = C.c_int
+        # shaped reward terms (shaping.py holds the mirrors): cfg and params are host structs, everything else a device pointer
+        L.solorl_shape_reward.argtypes = [C.POINTER(SoloConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.solorl_shape_reward.restype = C.c_int
         for s in SYMBOLS:
             getattr(L, s)
         # the ctypes mirrors in config.py / this file are written against one layout of include/solorl.h's structs

@@ -13,6 +13,9 @@ Differences that come with the GPU engine (documented, not behavioural):
   * args.push_interval / args.push_max_vel / args.push_max_yaw_rate (train_ppo.py --push-interval LO[:HI] ...; no reference counterpart)
     kick every training env's base at random intervals, drawn and applied on the device in front of every step launch of the eager
     and of the captured rollout alike (SoloVecEnv.set_perturbation); the schedule is keyed by global env id, so ranks kick like one batch;
+  * args.reward_shaping (train_ppo.py --reward-shaping FILE.yaml: a dict with `weights` and the terms' parameters; no reference
+    counterpart) adds shaped reward terms behind every step launch of the eager and of the captured rollout alike
+    (SoloVecEnv.set_reward_shaping); each term's weighted sum per finished episode is logged as sr/<name> beside dr/*;
   * multi-GPU: one process per GPU (`python -m torch.distributed.run --nproc-per-node W ...`), envs
     sharded by rank (global env id = rank*N + i), flat-bucket RCCL gradient all-reduce (ppo.py).
 """
@@ -83,7 +86,9 @@ def train(args, config, env_constructor=None, writer=None):
                                   "are not merged across ranks" % world)
     envs = make_vec_envs(config, N, env_constructor, args.gamma, device, seed=args.seed, env_id_offset=rank * N,
                          norm_obs=norm_obs, norm_ret=norm_ret, push_interval=getattr(args, "push_interval", None),
-                         push_max_vel=getattr(args, "push_max_vel", 0.0), push_max_yaw_rate=getattr(args, "push_max_yaw_rate", 0.0))
+                         push_max_vel=getattr(args, "push_max_vel", 0.0), push_max_yaw_rate=getattr(args, "push_max_yaw_rate", 0.0),
+                         reward_shaping=getattr(args, "reward_shaping", None))
+    shaping = getattr(args, "reward_shaping", None) is not None
     action_dim = envs.action_space.shape[0]
     base = torch.load(args.base_checkpoint) if getattr(args, "base_checkpoint", None) else None
     actor_critic = Policy(envs.observation_space.shape, envs.action_space, base, {"hidden_size": args.hidden_size}).to(device)
@@ -132,6 +137,8 @@ def train(args, config, env_constructor=None, writer=None):
             rec = dict(update=j, timesteps=total, fps=fps, value_loss=value_loss, action_loss=action_loss, entropy=entropy,
                        ep_reward=es["episode_reward"], ep_length=es["episode_length"], success=es["success"],
                        episodes=es["episodes"], **{k: v for k, v in es.items() if k.startswith("dr/")})
+            if shaping:                               # this rank's finished episodes: each shaped term's weighted sum per episode
+                rec.update({k: v for k, v in envs.shaping_stats(reset=True).items() if k.startswith("sr/")})
             history.append(rec)
             if rank == 0:
                 print("Updates {update}, num timesteps {timesteps}, FPS {fps}\n mean reward {ep_reward:.2f} mean length "
@@ -141,6 +148,6 @@ def train(args, config, env_constructor=None, writer=None):
                     for k in ("value_loss", "action_loss", "entropy", "ep_reward", "ep_length", "success"):
                         writer.add_scalar(k, rec[k], total)
                     for k in rec:
-                        if k.startswith("dr/"):          # agents/ppo/train.py:98-100, utils.log of the dr/ deques
+                        if k.startswith("dr/") or k.startswith("sr/"):   # agents/ppo/train.py:98-100, utils.log of the dr/ deques; sr/: shaped terms
                             writer.add_scalar(k, rec[k], total)
     return actor_critic, history

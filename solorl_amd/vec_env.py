@@ -16,6 +16,9 @@
       mass, energy, momentum of every env: include/solorl.h solorl_kinematics, kinematics.py)
   get_dynamics(mask) -> DynBatch   (joint-space mass matrix, bias and gravity forces, foot Jacobians with their Jdot v of every env:
       include/solorl.h solorl_dynamics, dyn_tensors.py)
+  set_reward_shaping(weights, **params), last_shaping_terms, shaping_stats()   (sixteen shaped reward terms -- foot slip, clearance, contact
+      force and air time, action rate, joint acceleration, power, command tracking ... -- added to every step's reward by one launch behind
+      the step launch while set: include/solorl.h solorl_shape_reward, shaping.py)
 
 torch is plumbing only: it owns the device buffers and the stream; all arithmetic happens in
 ``libsolorl_hip.so`` on the caller's current HIP stream (no host synchronisation in step()).
@@ -142,6 +145,12 @@ class SoloVecEnv:
         self._dyn_states = None     # engine-owned StateBatch of get_dynamics(), allocated at its first call
         self._kbuf = {}             # engine-owned [K, ...] rows of step_n_inplace / rollout_inplace, per K
         self.last_kick = None       # [N, 6] float64: the kick of the last perturb(), allocated by set_perturbation(); None = no perturbation set
+        # reward shaping (set_reward_shaping): nothing is allocated or launched unless it is set
+        self._shape_params = None   # ShapeParams; None = shaping off
+        self._shape_mem = None      # ShapeMem: the per-env memory of the shaped terms
+        self._shape_states = None   # engine-owned StateBatch the state after each step is read into
+        self._shape_ep = None       # [17, N] float64: finished episodes and their weighted term sums, per env
+        self.last_shaping_terms = None   # [N, 16] float64: the raw term values of the last step (zeros for an env that finished)
         self._info_c = InfoSoA(ep_stats=self._ep_stats.data_ptr(), applied_torque=None if self._tau is None else self._tau.data_ptr(),
                                **{k: self._info[k].data_ptr() for k in _INFO_KEYS})
         # VecNormalize (agents/running_mean_std.py:73-127; the reference's launcher passes ob=False, ret=False: agents/ppo/envs.py:26):
@@ -278,9 +287,72 @@ class SoloVecEnv:
             raise _native.SoloRLError("%s with a perturbation set: K steps in one launch cannot take kicks between the steps "
                                       "(rollout_supported() is False; step one at a time, or set_perturbation(None))" % name)
 
+    # ---- shaped reward terms (include/solorl.h solorl_shape_reward; shaping.py)
+    def set_reward_shaping(self, weights, **params):
+        """Adds the shaped terms named in ``weights`` (dict term name -> weight, shaping.TERMS; the table is in include/solorl.h) to every
+        step's reward; ``params``: base_height_target, foot_clearance_target, foot_force_max, air_time_target, cmd_lin_vel, cmd_yaw_rate,
+        tracking_sigma (shaping.PARAM_DEFAULTS).  ``weights=None`` switches it off.  Allocates the per-env memory (ShapeMem), an
+        engine-owned StateBatch, ``last_shaping_terms`` [N, 16] and the finished-episode sums [17, N] at the first call and clears them
+        at every call; call it before capturing a HIP graph of steps (the weights are launch arguments).
+
+        While set, step(), step_inplace() and step_act_inplace() issue get_states and ONE solorl_shape_reward launch right behind their
+        step launch, on the same stream and without host synchronisation, before the return normalisation -- which therefore sees the
+        shaped reward.  An env that finished in the step keeps the engine's terminal reward.  The torques and power terms read the state
+        row's ``tau``, which solorl_get_states leaves 0: they are 0 unless the env records the applied torques (``applied_torque=True``),
+        which are then copied into the rows in front of the launch.  step_n*, rollout_inplace run K steps in one
+        launch and cannot take the launch in between: they raise, and rollout_supported() is False."""
+        from .shaping import EP_FIELDS, SHAPE_TERMS, ShapeMem, make_params
+        if weights is None:
+            self._shape_params = self._shape_mem = self._shape_states = self._shape_ep = self.last_shaping_terms = None
+            return
+        p = make_params(weights, **params)
+        if self._shape_mem is None:
+            self._shape_mem = ShapeMem(self.nenvs, self.device)
+            self._shape_states = StateBatch(self.nenvs, self.device)
+            self._shape_ep = torch.zeros((EP_FIELDS, self.nenvs), dtype=torch.float64, device=self.device)
+            self.last_shaping_terms = torch.zeros((self.nenvs, SHAPE_TERMS), dtype=torch.float64, device=self.device)
+        else:
+            for t in (self._shape_mem.data, self._shape_ep, self.last_shaping_terms):
+                t.zero_()
+        self._shape_params = p
+
+    def _shape(self, actions, rew, done):
+        """the shaped terms of a control step, behind its step launch: the state after the step, then one launch"""
+        if self._shape_params is not None:
+            from .shaping import shape_reward
+            self.get_states(out=self._shape_states)
+            if self._tau is not None:                   # solorl_get_states leaves `tau` 0: the torques and power terms read the recorded torques
+                self._shape_states.tau[:, :self.act_dim].copy_(self._tau)
+            shape_reward(self.cfg, self._shape_params, self._shape_states, actions, done, self._shape_mem, rew,
+                         terms_out=self.last_shaping_terms, ep_out=self._shape_ep)
+
+    def _no_shaping(self, name):
+        if self._shape_params is not None:
+            raise _native.SoloRLError("%s with reward shaping set: K steps in one launch cannot take the shaped terms between the steps "
+                                      "(rollout_supported() is False; step one at a time, or set_reward_shaping(None))" % name)
+
+    def shaping_stats(self, reset=True):
+        """Means over the episodes finished since the last call of each term's weighted sum over the episode, ``sr/<name>``, and their
+        count ``episodes`` -- reduced on the device from the per-env sums solorl_shape_reward keeps; one small device->host copy.
+        ``reset`` zeroes the sums."""
+        from .shaping import TERMS
+        if self._shape_ep is None:
+            raise _native.SoloRLError("shaping_stats() without reward shaping set")
+        tot = self._shape_ep.sum(dim=1)
+        if reset:
+            self._shape_ep.zero_()
+        tot = tot.tolist()
+        n = tot[0]
+        out = {"episodes": int(n)}
+        for k, name in enumerate(TERMS):
+            out["sr/" + name] = (tot[1 + k] / n) if n > 0 else float("nan")
+        return out
+
     def reset(self):
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_reset(self._h, C.c_void_p(self._obs.data_ptr()), self._stream()))
+        if self._shape_mem is not None:                 # every env starts an episode
+            self._shape_mem.data.zero_()
         if self._norm is not None:                      # running_mean_std.py:118-121
             self._norm.ret.zero_()
             if self._norm_obs:
@@ -297,6 +369,7 @@ class SoloVecEnv:
             _native.check(self.L.solorl_step(self._h, C.c_void_p(a.data_ptr()), C.c_void_p(self._obs.data_ptr()),
                                              C.c_void_p(self._rew.data_ptr()), C.c_void_p(self._done.data_ptr()),
                                              C.byref(self._info_c), self._stream()))
+        self._shape(a, self._rew, self._done)
         if self._norm is not None:
             self._normalize(self._obs, self._rew, self._done, 1)
         t = {k: v.clone() for k, v in self._info.items()}
@@ -332,6 +405,7 @@ class SoloVecEnv:
         self._kick()
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_step(self._h, a, po, pr, pd, C.byref(self._info_c), self._stream()))
+        self._shape(actions, r, d)
         if self._norm is not None:
             self._normalize(o, r, d, 1)
         return o, r, d, self._info
@@ -358,6 +432,7 @@ class SoloVecEnv:
         self._kick()
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_step_act(self._h, a, po, pr, pd, C.byref(self._info_c), C.byref(params), pn, pv, pa, pl, self._stream()))
+        self._shape(actions, r, d)
         if self._norm_ret:
             self._normalize(o, r, d, 1)
         return o, r, d, self._info
@@ -402,6 +477,7 @@ class SoloVecEnv:
         (overwritten by the next call with the same K) -- or writes observations [K, N, O] / rewards [K, N] or [K, N, 1] / done flags
         (uint8 [K, N]) straight into caller-owned tensors such as rollout-storage rows.  Host-side checks only, capturable."""
         self._no_kicks("step_n")
+        self._no_shaping("step_n")
         K = int(actions.shape[0]) if actions.dim() == 3 else 0
         if K < 1:
             raise AssertionError("actions must be [K, %d, %d] with K >= 1" % (self.nenvs, self.act_dim))
@@ -417,8 +493,8 @@ class SoloVecEnv:
 
     def rollout_supported(self, params):
         """solorl_rollout (K closed-loop steps in one launch) on this handle: the prerequisites of solorl_step_act, and no perturbation
-        set (kicks come between two step launches)."""
-        return self.last_kick is None and self.step_act_supported(params)
+        set (kicks come between two step launches) and no reward shaping set (its launch comes behind every step launch)."""
+        return self.last_kick is None and self._shape_params is None and self.step_act_supported(params)
 
     def rollout_inplace(self, actions, params, noise, value_out, logp_out, obs_out=None, rew_out=None, done_out=None, policy_after_last=False):
         """K closed-loop steps in one launch (solorl_rollout), in rollout-storage rows: actions [K (+1), N, A] -- row 0 drives the
@@ -427,6 +503,7 @@ class SoloVecEnv:
         [K (+1), N, 1], rows from 1 written; obs_out [K, N, O], rew_out [K, N] or [K, N, 1], done_out uint8 [K, N] as step_n_inplace."""
         self._no_policy_tail("rollout_inplace")
         self._no_kicks("rollout_inplace")
+        self._no_shaping("rollout_inplace")
         pal = 1 if policy_after_last else 0
         R = int(actions.shape[0]) if actions.dim() == 3 else 0
         K = R - pal
@@ -572,6 +649,8 @@ class SoloVecEnv:
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_get_observation(self._h, C.c_void_p(self._obs.data_ptr()), self._stream()))
             _native.check(self.L.solorl_reset_masked(self._h, pm, C.c_void_p(self._obs.data_ptr()), self._stream()))
+        if self._shape_mem is not None:                 # the selected envs start an episode (its sums so far are dropped, not counted)
+            self._shape_mem.data.masked_fill_(m.bool().unsqueeze(-1), 0.0)
         if self._norm is not None:
             sel = m.bool()
             self._norm.ret.masked_fill_(sel, 0.0)       # a reset env starts a new return (running_mean_std.py:105)
@@ -609,7 +688,7 @@ class SoloVecEnv:
 
 def make_vec_envs(config, num_envs, env_constructor=None, gamma=0.99, device=None, training=True, seed=1,
                   env_id_offset=0, norm_obs=False, norm_ret=False, clipob=10., cliprew=10., epsilon=1e-8,
-                  push_interval=None, push_max_vel=0.0, push_max_yaw_rate=0.0):
+                  push_interval=None, push_max_vel=0.0, push_max_yaw_rate=0.0, reward_shaping=None):
     """Signature of agents/ppo/envs.py:14.  ``env_constructor`` (the per-process gym env class of the
     reference) is accepted for call-site compatibility and ignored.  ``norm_obs`` / ``norm_ret`` are VecNormalize's ``ob`` /
     ``ret`` (agents/running_mean_std.py:79; the reference's launcher passes False, False, and so do the defaults here) with its
@@ -617,11 +696,19 @@ def make_vec_envs(config, num_envs, env_constructor=None, gamma=0.99, device=Non
     ``training=False`` is its eval() (agents/ppo/envs.py:27-28).
     ``push_interval`` (an int or a (lo, hi) pair of control steps; None = no kicks, and nothing is allocated or launched): random kicks of
     up to ``push_max_vel`` m/s on the base's world x and y velocity and ``push_max_yaw_rate`` rad/s on its yaw rate, in front of every
-    step (SoloVecEnv.set_perturbation)."""
+    step (SoloVecEnv.set_perturbation).
+    ``reward_shaping`` (a dict with ``weights`` and the parameters as further keys, as configs/shaping_walk12.yaml holds it; None = no
+    shaping, and nothing is allocated or launched): shaped reward terms behind every step (SoloVecEnv.set_reward_shaping)."""
     envs = SoloVecEnv(config, num_envs, device=device, seed=seed, env_id_offset=env_id_offset, norm_obs=norm_obs, norm_ret=norm_ret,
                       clipob=clipob, cliprew=cliprew, gamma=gamma, epsilon=epsilon)
     if push_interval is not None:
         envs.set_perturbation(push_interval, (push_max_vel, push_max_vel, 0.0), (0.0, 0.0, push_max_yaw_rate))
+    if reward_shaping is not None:
+        rs = dict(reward_shaping)
+        weights = rs.pop("weights", None)
+        if not isinstance(weights, dict):
+            raise ValueError("reward_shaping needs a `weights` mapping of term name -> weight")
+        envs.set_reward_shaping(weights, **rs)
     if not training:
         envs.eval()
     return envs

@@ -59,6 +59,9 @@ def get_ppo_args(argv=None):
                    help="kick every training env's base every LO..HI control steps (drawn on the device; default: no kicks)")
     p.add_argument("--push-max-vel", type=float, default=0.0, help="a kick adds U(-V, V) m/s to the base's world x and y velocity")
     p.add_argument("--push-max-yaw-rate", type=float, default=0.0, help="... and U(-W, W) rad/s to its yaw rate")
+    p.add_argument("--reward-shaping", type=str, default=None, metavar="FILE.yaml",
+                   help="add shaped reward terms to every step's reward: `weights:` (term name -> weight) and the terms' parameters, "
+                        "e.g. configs/shaping_walk12.yaml (default: the reference's reward alone)")
     p.add_argument("--num-steps", type=int, default=None, help="rollout length (default: episode_length, train_ppo.py:62-63)")
     return p.parse_args(argv)
 
@@ -77,6 +80,14 @@ def main(argv=None):
         raise SystemExit("the rollout engine is GPU-only (no CPU fallback)")
     if args.num_steps is None:
         args.num_steps = config["episode_length"]
+    if args.reward_shaping is not None:
+        from solorl_amd.shaping import params_from_dict
+        shaping = load_yaml(args.reward_shaping)
+        try:
+            params_from_dict(shaping)                 # unknown term and parameter names are refused by name, before anything is built
+        except ValueError as e:
+            raise SystemExit("--reward-shaping %s: %s" % (args.reward_shaping, e))
+        args.reward_shaping = shaping
     writer = None
     rank = int(os.environ.get("RANK", "0"))
     if args.logdir is not None:      # run directory named as training/train_ppo.py:64-72
