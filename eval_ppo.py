@@ -7,7 +7,9 @@ trajectory (base pose, joint angles, action, reward, done) to an .npz.  --push-i
 every K control steps with an xy velocity drawn uniformly from +-V m/s (robustness evaluation; SoloVecEnv.push).
 --gait-metrics says what the gait looks like, from the batched kinematics of every env at every step (SoloVecEnv.get_kinematics,
 reduced on the device): per foot the duty factor, mean and peak normal force, slip distance and peak swing clearance, and the mean
-ratio of the summed normal forces to the robot's weight; --dump then also holds env 0's foot positions and forces."""
+ratio of the summed normal forces to the robot's weight; --dump then also holds env 0's foot positions and forces.
+--obs-noise FILE.yaml --action-delay LO[:HI] --motor-gain-range G (train_ppo.py's flags) evaluate under sensor noise, actuation latency
+and motor gain error (SoloVecEnv.set_obs_noise / set_actuation)."""
 import argparse
 import os
 import sys
@@ -69,6 +71,8 @@ def main(argv=None):
     p.add_argument("--max-steps", type=int, default=0, help="stop after K control steps even if fewer than --num-runs episodes have ended (0 = no limit)")
     p.add_argument("--push-interval", type=int, default=0, help="kick every env's base velocity every K control steps (0 = never)")
     p.add_argument("--push-max-vel", type=float, default=0.0, help="a kick's x and y velocity change is uniform in +-V m/s")
+    from train_ppo import add_channel_flags, load_obs_noise
+    add_channel_flags(p)
     a = p.parse_args(argv)
 
     import numpy as np
@@ -85,7 +89,9 @@ def main(argv=None):
     # a checkpoint trained with --normalize-obs carries the observation statistics: the policy sees observations scaled by them,
     # frozen (testing/test_ppo.py:89-90); rewards are reported raw
     ob_rms = ckpt.get("ob_rms")
-    env = make_vec_envs(config, a.num_agents, None, device=dev, training=False, seed=a.seed, norm_obs=ob_rms is not None)
+    env = make_vec_envs(config, a.num_agents, None, device=dev, training=False, seed=a.seed, norm_obs=ob_rms is not None,
+                        obs_noise=None if a.obs_noise is None else load_obs_noise(a.obs_noise, config), action_delay=a.action_delay,
+                        motor_gain_range=a.motor_gain_range)
     env.ob_rms = ob_rms
     env.eval()
     policy = Policy(env.observation_space.shape, env.action_space, None, {"hidden_size": a.hidden_size}).to(dev)

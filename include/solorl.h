@@ -48,6 +48,9 @@
  *                             torques, joint acceleration, action rate, power, foot slip, clearance, contact force, air time, collisions,
  *                             command tracking -- of a whole batch of state rows added to the step's reward, one launch, with the
  *                             per-env memory these terms need in caller-owned device rows
+ *   solorl_obs_noise / solorl_actuate : what stands between the policy and the engine in a randomised training run (no reference
+ *                             counterpart): uniform sensor noise on observation rows, and actuation latency with a per-joint motor gain
+ *                             error on action rows -- drawn on the device from a Philox stream per env, one launch each, handle-free
  *   solorl_destroy         <- agents/ppo/envs.py:129-135 (close)
  *
  * Plain pointers and sizes only; no torch types.  All array arguments are DEVICE pointers
@@ -443,6 +446,62 @@ int solorl_shape_reward(const solorl_config* cfg, const solorl_shape_params* p,
                         solorl_env_shape* mem /* [n], in/out */, float* reward /* [n] in/out, or NULL */,
                         double* terms_out /* [n][16] raw term values, or NULL */,
                         double* ep_out /* [17][n] field-major, or NULL */, int device_id, void* stream);
+
+/* Observation noise and actuation (no reference counterpart; the "sensor noise", "action latency" and "motor strength" randomisations of
+ * sim-to-real training).  Both calls are handle-free: they work on the two arrays that cross the boundary between policy and engine and
+ * on caller-owned DEVICE memory, know nothing of the step kernels, and are ONE launch on `stream` each, without allocation or host
+ * synchronisation (capturable).  Everything is a function of seed, global env id gid = env_id_offset + i and a per-env count, so W
+ * shards at offsets k n draw what one batch of W n rows draws.  Key of both streams: (seed_lo, seed_hi), as for the env's own stream.
+ *
+ * solorl_obs_noise: obs_out[i][c] = obs_in[i][c] + U(-scale[c], scale[c]) for every row whose mask byte is not 0 (mask == NULL: all).
+ *   counter   (gid_lo, gid_hi, block, 5).  The env's own stream uses 1, 2 and 3 in the last word and the kicks use 4; a draw never
+ *             reads or advances rng_counter.
+ *   block     count[i] * B + b (mod 2^32) with B = ceil(D / 4); word w of block b belongs to component c = 4 b + w, words past D are unused
+ *   uniform   u = (word >> 8) * 2^-24; e = (2 u - 1) * (double)scale[c]: the subtraction is exact, the product rounds once, in double
+ *   output    obs_out[i][c] = (float)((double)obs_in[i][c] + e): one double addition, one rounding to float (no fused multiply-add)
+ *   zero      scale[c] == 0 copies the input's bits (NaN payloads and -0.0 survive); in place such a component is left as it is
+ *   live row  afterwards count[i] += 1
+ *   masked    nothing of the row is read or written and count[i] does not advance
+ *   The additive noise does not re-wrap a wrapped quantity (the Euler angles of the observation).  Rows whose D is a multiple of 4 in
+ *   16-byte aligned arrays move as 16-byte words, every other shape word by word; the values are the same.
+ *   Null scale, count, obs_in or obs_out, n < 1, D < 1 or D > 210 (42 words x 5 levels): SOLORL_ERR_INVALID, the message starts with
+ *   "solorl_obs_noise:" (checked before any HIP call).
+ *
+ * solorl_actuate: actions_out[i] = the action the motors of env i receive for the raw action actions_in[i] -- delayed by the env's
+ *   latency (drawn per episode, in control steps) and scaled by its per-joint gains (drawn per episode).  Per env, in this order:
+ *   1 restart   r = (restart && restart[i]) || mem.episodes == 0: a zeroed row draws at its first call
+ *   2 on r      e = mem.episodes; counter (gid_lo, gid_hi, 4 e, 6) word 0 -> latency = delay_min + word % (delay_max - delay_min + 1);
+ *               counters (.., 4 e + 1 + j / 4, 6) word j % 4 -> gain[j] = (float)(1.0 + (2 u - 1) * gain_range), u as above: the product
+ *               is rounded, then the sum, then the result goes to float (exactly 1.0f for gain_range == 0); fill = 0, episodes = e + 1
+ *   3 delayed   d_j = (latency == 0 || fill == 0) ? in_j : buf[min(latency, fill) - 1][j]: until `latency` actions have arrived the
+ *               episode's FIRST action is held (safe for torque and PD actions alike; never a zero or a stale action of the last episode)
+ *   4 output    out_j = gain_range == 0 ? d_j (its bits) : (float)((double)gain[j] * (double)d_j)
+ *   5 buffer    levels 0 .. delay_max - 2 move up by one, buf[0] = in, fill = min(fill + 1, delay_max); with delay_max == 0 nothing moves
+ *               and fill stays 0.  Levels >= delay_max and joints >= act_dim are never read or written.
+ *   actions_out may be actions_in.  Null p, mem, actions_in or actions_out, n < 1, act_dim not 8 or 12, a delay range outside
+ *   0 <= delay_min <= delay_max <= SOLORL_DELAY_MAX, a gain_range that is not finite or outside [0, 1): SOLORL_ERR_INVALID, the message
+ *   starts with "solorl_actuate:" (checked before any HIP call). */
+int solorl_obs_noise(uint64_t seed, int64_t env_id_offset,
+                     const float* scale   /* [D] device: half-width per observation component; 0 = component untouched */,
+                     const uint8_t* mask  /* [n] device or NULL */, int n, int D,
+                     uint32_t* count      /* [n] device, in/out: noise calls this env has received */,
+                     const float* obs_in  /* [n][D] */, float* obs_out /* [n][D]; may be obs_in */,
+                     int device_id, void* stream);
+#define SOLORL_DELAY_MAX 4
+typedef struct solorl_actuation {
+  uint64_t seed; int64_t env_id_offset;
+  int32_t act_dim /* 8 or 12 */, delay_min, delay_max /* 0 <= min <= max <= SOLORL_DELAY_MAX, control steps */, reserved;
+  double gain_range;   /* per joint and episode: gain = 1 + U(-r, r); 0 <= r < 1; 0 = gains are exactly 1 and nothing is multiplied */
+} solorl_actuation;
+typedef struct solorl_env_actuator {      /* caller-owned DEVICE rows, 64 words = 256 B */
+  float buf[SOLORL_DELAY_MAX][12];        /* buf[k] = the raw action received k + 1 calls ago in this episode */
+  float gain[12];
+  int32_t latency, fill /* raw actions buffered this episode, saturating at delay_max */;
+  uint32_t episodes /* episodes drawn so far */; int32_t reserved;
+} solorl_env_actuator;
+int solorl_actuate(const solorl_actuation* p, int n, const uint8_t* restart /* [n] device or NULL */,
+                   solorl_env_actuator* mem /* [n] in/out */, const float* actions_in /* [n][A] */,
+                   float* actions_out /* [n][A]; may be actions_in */, int device_id, void* stream);
 
 /* Fused return computation over a rollout of T steps x N envs (device arrays, time-major [t][n]).
  * use_gae != 0:  value_preds[T][:] = next_value;  delta_t = r_t + gamma V_{t+1} m_{t+1} - V_t;

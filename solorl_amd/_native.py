@@ -20,7 +20,7 @@ SYMBOLS = ("solorl_default_config", "solorl_create", "solorl_destroy", "solorl_d
            "solorl_get_states", "solorl_set_states", "solorl_reset_masked",
            "solorl_set_perturbation", "solorl_perturb", "solorl_get_perturbation",
            "solorl_norm_scratch_count", "solorl_normalize_obs", "solorl_normalize_rewards", "solorl_kinematics", "solorl_dynamics",
-           "solorl_shape_reward")
+           "solorl_shape_reward", "solorl_obs_noise", "solorl_actuate")
 
 
 class PolicyParams(C.Structure):            # solorl_policy_params
@@ -52,6 +52,19 @@ class PpoStage1(C.Structure):               # solorl_ppo_stage1
 
 class Perturbation(C.Structure):            # solorl_perturbation
     _fields_ = [("interval_min", C.c_int32), ("interval_max", C.c_int32), ("max_lin_vel", C.c_double * 3), ("max_ang_vel", C.c_double * 3)]
+
+
+DELAY_MAX = 4                               # SOLORL_DELAY_MAX
+
+
+class Actuation(C.Structure):               # solorl_actuation
+    _fields_ = [("seed", C.c_uint64), ("env_id_offset", C.c_int64), ("act_dim", C.c_int32), ("delay_min", C.c_int32), ("delay_max", C.c_int32),
+                ("reserved", C.c_int32), ("gain_range", C.c_double)]
+
+
+class EnvActuator(C.Structure):             # solorl_env_actuator
+    _fields_ = [("buf", (C.c_float * 12) * DELAY_MAX), ("gain", C.c_float * 12), ("latency", C.c_int32), ("fill", C.c_int32),
+                ("episodes", C.c_uint32), ("reserved", C.c_int32)]
 
 
 class SoloRLError(RuntimeError):
@@ -123,6 +136,10 @@ def lib():
         L.solorl_shape_reward.argtypes = [C.POINTER(SoloConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.solorl_shape_reward.restype = C.c_int
+        # observation noise and actuation (channel.py): handle-free; params is a host struct, every array a device pointer
+        L.solorl_obs_noise.argtypes = [C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.solorl_actuate.argtypes = [C.POINTER(Actuation), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.solorl_obs_noise.restype = L.solorl_actuate.restype = C.c_int
         for s in SYMBOLS:
             getattr(L, s)
         # the ctypes mirrors in config.py / this file are written against one layout of include/solorl.h's structs

@@ -16,6 +16,11 @@ Differences that come with the GPU engine (documented, not behavioural):
   * args.reward_shaping (train_ppo.py --reward-shaping FILE.yaml: a dict with `weights` and the terms' parameters; no reference
     counterpart) adds shaped reward terms behind every step launch of the eager and of the captured rollout alike
     (SoloVecEnv.set_reward_shaping); each term's weighted sum per finished episode is logged as sr/<name> beside dr/*;
+  * args.obs_noise / args.action_delay / args.motor_gain_range (train_ppo.py --obs-noise FILE.yaml --action-delay LO[:HI]
+    --motor-gain-range G; no reference counterpart) put uniform sensor noise on every observation the rollout stores and the policy reads,
+    and actuation latency with a per-joint motor gain error between the stored raw actions and the engine, in the eager and in the
+    captured rollout alike (SoloVecEnv.set_obs_noise / set_actuation); both are keyed by global env id, so ranks draw like one batch.
+    With noise the policy cannot run inside the step kernel (it would read clean observations): the rollout takes two launches per step;
   * multi-GPU: one process per GPU (`python -m torch.distributed.run --nproc-per-node W ...`), envs
     sharded by rank (global env id = rank*N + i), flat-bucket RCCL gradient all-reduce (ppo.py).
 """
@@ -87,7 +92,8 @@ def train(args, config, env_constructor=None, writer=None):
     envs = make_vec_envs(config, N, env_constructor, args.gamma, device, seed=args.seed, env_id_offset=rank * N,
                          norm_obs=norm_obs, norm_ret=norm_ret, push_interval=getattr(args, "push_interval", None),
                          push_max_vel=getattr(args, "push_max_vel", 0.0), push_max_yaw_rate=getattr(args, "push_max_yaw_rate", 0.0),
-                         reward_shaping=getattr(args, "reward_shaping", None))
+                         reward_shaping=getattr(args, "reward_shaping", None), obs_noise=getattr(args, "obs_noise", None),
+                         action_delay=getattr(args, "action_delay", None), motor_gain_range=getattr(args, "motor_gain_range", 0.0))
     shaping = getattr(args, "reward_shaping", None) is not None
     action_dim = envs.action_space.shape[0]
     base = torch.load(args.base_checkpoint) if getattr(args, "base_checkpoint", None) else None

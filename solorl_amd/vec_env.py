@@ -19,6 +19,9 @@
   set_reward_shaping(weights, **params), last_shaping_terms, shaping_stats()   (sixteen shaped reward terms -- foot slip, clearance, contact
       force and air time, action rate, joint acceleration, power, command tracking ... -- added to every step's reward by one launch behind
       the step launch while set: include/solorl.h solorl_shape_reward, shaping.py)
+  set_obs_noise(scales), set_actuation(delay, gain_range), last_applied_actions   (uniform sensor noise on every observation row the
+      engine writes, and actuation latency with a per-joint motor gain error on every action row it reads, drawn on the device per env:
+      include/solorl.h solorl_obs_noise / solorl_actuate, channel.py)
 
 torch is plumbing only: it owns the device buffers and the stream; all arithmetic happens in
 ``libsolorl_hip.so`` on the caller's current HIP stream (no host synchronisation in step()).
@@ -151,6 +154,14 @@ class SoloVecEnv:
         self._shape_states = None   # engine-owned StateBatch the state after each step is read into
         self._shape_ep = None       # [17, N] float64: finished episodes and their weighted term sums, per env
         self.last_shaping_terms = None   # [N, 16] float64: the raw term values of the last step (zeros for an env that finished)
+        # observation noise and actuation (set_obs_noise, set_actuation): nothing is allocated or launched unless they are set
+        self._seed, self._id0 = int(seed), int(env_id_offset)     # the key and the global env ids of their Philox streams
+        self._noise_scale = None    # [O] float32: the noise half-width per observation component; None = noise off
+        self._noise_count = None    # [N] int32 (uint32 words): the noise calls each env has received
+        self._act = None            # Actuation; None = actuation off
+        self._act_mem = None        # ActuatorMem: the per-env delay line, gains and latency
+        self._act_restart = None    # [N] uint8: the envs whose next action is the first of an episode
+        self.last_applied_actions = None   # [N, A] float32: what the last step launch received for the caller's raw actions
         self._info_c = InfoSoA(ep_stats=self._ep_stats.data_ptr(), applied_torque=None if self._tau is None else self._tau.data_ptr(),
                                **{k: self._info[k].data_ptr() for k in _INFO_KEYS})
         # VecNormalize (agents/running_mean_std.py:73-127; the reference's launcher passes ob=False, ret=False: agents/ppo/envs.py:26):
@@ -223,6 +234,9 @@ class SoloVecEnv:
     def _no_policy_tail(self, name):
         if self._norm_obs:
             raise _native.SoloRLError("%s on an env with norm_obs: the policy inside the step kernel would read raw observations "
+                                      "(step_act_supported() / rollout_supported() are False)" % name)
+        if self._noise_scale is not None:
+            raise _native.SoloRLError("%s with observation noise set: the policy inside the step kernel would read clean observations "
                                       "(step_act_supported() / rollout_supported() are False)" % name)
 
     def _stream(self):
@@ -348,9 +362,94 @@ class SoloVecEnv:
             out["sr/" + name] = (tot[1 + k] / n) if n > 0 else float("nan")
         return out
 
+    # ---- observation noise and actuation (include/solorl.h solorl_obs_noise / solorl_actuate; channel.py)
+    def set_obs_noise(self, scales):
+        """Uniform sensor noise on every observation the engine hands out: ``scales`` is a dict of half-widths in physical units per
+        group (channel.noise_scales: height, orientation, lin_vel, ang_vel, joint_pos, joint_vel, position; or a noise file's dict with
+        ``groups`` and ``history``, configs/noise_solo.yaml) or an ``[obs_dim]`` vector of half-widths in the observation's own units.
+        ``None`` switches it off.  Calling it again restarts every env's noise stream.  Allocates its two arrays here: call it before
+        capturing a HIP graph of steps.
+
+        While set, reset(), step(), step_inplace() and reset_masked() (the selected rows) issue ONE solorl_obs_noise launch on the
+        observation rows the engine has just written, in place, before the observation normalisation -- rollout-storage rows hold what
+        the policy saw; get_observation() stays clean.  The policy inside the step kernel would read clean observations, so
+        step_act_supported() and rollout_supported() are False, step_act_inplace() raises, and so do step_n*, rollout_inplace (K steps in
+        one launch)."""
+        from .channel import noise_scales, scales_from_dict
+        if scales is None:
+            self._noise_scale = self._noise_count = None
+            return
+        if isinstance(scales, dict):
+            v = scales_from_dict(self.cfg, scales) if "groups" in scales else noise_scales(self.cfg, scales)
+        else:
+            v = torch.as_tensor(scales, dtype=torch.float32).detach().reshape(-1)
+        if tuple(v.shape) != (self.obs_dim,) or not bool(torch.isfinite(v).all()) or bool((v < 0).any()):
+            raise AssertionError("observation noise scales must be %d finite values >= 0" % self.obs_dim)
+        self._noise_scale = v.to(self.device).contiguous()
+        if self._noise_count is None:
+            self._noise_count = torch.zeros((self.nenvs,), dtype=torch.int32, device=self.device)
+        else:
+            self._noise_count.zero_()
+
+    def _noise(self, o, mask=None):
+        """the sensor noise of the observation rows the engine has just written, in place"""
+        if self._noise_scale is not None:
+            from .channel import obs_noise
+            obs_noise(self._seed, self._id0, self._noise_scale, self._noise_count, o, mask=mask)
+
+    def set_actuation(self, delay=None, gain_range=0.0):
+        """Actuation latency and motor gain error between the caller's actions and the engine: every env applies the action it received
+        ``delay`` control steps ago (an int, or a (lo, hi) pair within 0..4: uniform, drawn per env and episode; until that many actions
+        have arrived in an episode its first action is held), each joint's action scaled by a gain 1 + U(-gain_range, gain_range) drawn
+        per env, episode and joint.  ``delay=None`` with ``gain_range=0`` switches it off.  Calling it again starts every env over (episode 0's
+        draws, empty delay lines).  Allocates its buffers here: call it before capturing a HIP graph of steps.
+
+        While set, step(), step_inplace() and step_act_inplace() issue ONE solorl_actuate launch in front of the kick and the step
+        launch: it reads the caller's actions, which are never written, and writes ``last_applied_actions`` [N, A], which the step launch
+        receives.  Rollout storage and the shaped reward terms keep the raw actions.  An env restarts its episode draws after a step that
+        finished it, after reset() and after reset_masked() selected it.  step_act_inplace() stays supported (the tail's action is raw and
+        is delayed at the next call); step_n*, rollout_inplace raise, and rollout_supported() is False."""
+        from .channel import ActuatorMem, make_actuation
+        if delay is None and not gain_range:
+            self._act = self._act_mem = self._act_restart = self.last_applied_actions = None
+            return
+        p = make_actuation(self._seed, self._id0, self.act_dim, 0 if delay is None else delay, gain_range)
+        if not (0 <= p.delay_min <= p.delay_max <= _native.DELAY_MAX) or not (0.0 <= p.gain_range < 1.0):
+            raise AssertionError("delay must lie within 0..%d and gain_range in [0, 1), got %r, %r" % (_native.DELAY_MAX, delay, gain_range))
+        if self._act_mem is None:
+            self._act_mem = ActuatorMem(self.nenvs, self.device)
+            self._act_restart = torch.ones((self.nenvs,), dtype=torch.uint8, device=self.device)
+            self.last_applied_actions = torch.zeros((self.nenvs, self.act_dim), dtype=torch.float32, device=self.device)
+        else:
+            self._act_mem.data.zero_()
+            self._act_restart.fill_(1)
+            self.last_applied_actions.zero_()
+        self._act = p
+
+    def _actuate(self, actions):
+        """the actions a step launch receives for the caller's raw ``actions`` [N, A]: themselves, or the delayed and scaled ones"""
+        if self._act is None:
+            return actions
+        from .channel import actuate
+        return actuate(self._act, self._act_mem, actions, out=self.last_applied_actions, restart=self._act_restart)
+
+    def _restarts(self, done):
+        """behind a step launch: the envs it finished start an episode with their next action"""
+        if self._act is not None:
+            self._act_restart.copy_(done)
+
+    def _no_channel(self, name):
+        if self._noise_scale is not None or self._act is not None:
+            raise _native.SoloRLError("%s with observation noise or actuation set: K steps in one launch cannot take their launches between "
+                                      "the steps (rollout_supported() is False; step one at a time, or set_obs_noise(None) / "
+                                      "set_actuation(None))" % name)
+
     def reset(self):
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_reset(self._h, C.c_void_p(self._obs.data_ptr()), self._stream()))
+        if self._act is not None:                       # every env starts an episode
+            self._act_restart.fill_(1)
+        self._noise(self._obs)
         if self._shape_mem is not None:                 # every env starts an episode
             self._shape_mem.data.zero_()
         if self._norm is not None:                      # running_mean_std.py:118-121
@@ -364,12 +463,15 @@ class SoloVecEnv:
             raise AssertionError("actions must be [%d, %d]" % (self.nenvs, self.act_dim))   # solo.py:226
         a = actions.detach().to(device=self.device, dtype=torch.float32).contiguous()
         self._steps_issued += 1
+        applied = self._actuate(a)
         self._kick()
         with torch.cuda.device(self.device):
-            _native.check(self.L.solorl_step(self._h, C.c_void_p(a.data_ptr()), C.c_void_p(self._obs.data_ptr()),
+            _native.check(self.L.solorl_step(self._h, C.c_void_p(applied.data_ptr()), C.c_void_p(self._obs.data_ptr()),
                                              C.c_void_p(self._rew.data_ptr()), C.c_void_p(self._done.data_ptr()),
                                              C.byref(self._info_c), self._stream()))
+        self._restarts(self._done)
         self._shape(a, self._rew, self._done)
+        self._noise(self._obs)
         if self._norm is not None:
             self._normalize(self._obs, self._rew, self._done, 1)
         t = {k: v.clone() for k, v in self._info.items()}
@@ -402,10 +504,14 @@ class SoloVecEnv:
         a = self._raw("actions", actions, (self.nenvs, self.act_dim))
         o, r, d, po, pr, pd = self._outputs((), (self._obs, self._rew, self._done), obs_out, rew_out, done_out)
         self._steps_issued += 1
+        if self._act is not None:
+            a = C.c_void_p(self._actuate(actions).data_ptr())
         self._kick()
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_step(self._h, a, po, pr, pd, C.byref(self._info_c), self._stream()))
+        self._restarts(d)
         self._shape(actions, r, d)
+        self._noise(o)
         if self._norm is not None:
             self._normalize(o, r, d, 1)
         return o, r, d, self._info
@@ -415,6 +521,7 @@ class SoloVecEnv:
         latched at solorl_create, whatever the environment says now: fp32, team mode, no sorting, and an observation size that is a
         multiple of 4 floats and at most 88 (zero or one history level) with the reference's hidden-64 MLP on it."""
         return (not self._norm_obs                 # (the policy inside the step kernel would read the raw observations)
+                and self._noise_scale is None      # (... and the clean ones)
                 and self.get_property("step_n_one_launch") == 1 and self.get_property("f64") == 0 and self.obs_dim % 4 == 0 and self.obs_dim <= 88
                 and params.obs_dim == self.obs_dim and params.act_dim == self.act_dim and params.hidden == 64)
 
@@ -429,9 +536,12 @@ class SoloVecEnv:
         pl = self._per_env("logp_out", logp_out, ())
         pn = C.c_void_p(0) if noise is None else self._raw("noise", noise, (self.nenvs, self.act_dim))
         self._steps_issued += 1
+        if self._act is not None:
+            a = C.c_void_p(self._actuate(actions).data_ptr())
         self._kick()
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_step_act(self._h, a, po, pr, pd, C.byref(self._info_c), C.byref(params), pn, pv, pa, pl, self._stream()))
+        self._restarts(d)
         self._shape(actions, r, d)
         if self._norm_ret:
             self._normalize(o, r, d, 1)
@@ -478,6 +588,7 @@ class SoloVecEnv:
         (uint8 [K, N]) straight into caller-owned tensors such as rollout-storage rows.  Host-side checks only, capturable."""
         self._no_kicks("step_n")
         self._no_shaping("step_n")
+        self._no_channel("step_n")
         K = int(actions.shape[0]) if actions.dim() == 3 else 0
         if K < 1:
             raise AssertionError("actions must be [K, %d, %d] with K >= 1" % (self.nenvs, self.act_dim))
@@ -493,8 +604,9 @@ class SoloVecEnv:
 
     def rollout_supported(self, params):
         """solorl_rollout (K closed-loop steps in one launch) on this handle: the prerequisites of solorl_step_act, and no perturbation
-        set (kicks come between two step launches) and no reward shaping set (its launch comes behind every step launch)."""
-        return self.last_kick is None and self._shape_params is None and self.step_act_supported(params)
+        set (kicks come between two step launches), no reward shaping set (its launch comes behind every step launch) and neither
+        observation noise nor actuation set (their launches stand behind and in front of every step launch)."""
+        return self.last_kick is None and self._shape_params is None and self._act is None and self.step_act_supported(params)
 
     def rollout_inplace(self, actions, params, noise, value_out, logp_out, obs_out=None, rew_out=None, done_out=None, policy_after_last=False):
         """K closed-loop steps in one launch (solorl_rollout), in rollout-storage rows: actions [K (+1), N, A] -- row 0 drives the
@@ -504,6 +616,7 @@ class SoloVecEnv:
         self._no_policy_tail("rollout_inplace")
         self._no_kicks("rollout_inplace")
         self._no_shaping("rollout_inplace")
+        self._no_channel("rollout_inplace")
         pal = 1 if policy_after_last else 0
         R = int(actions.shape[0]) if actions.dim() == 3 else 0
         K = R - pal
@@ -649,6 +762,9 @@ class SoloVecEnv:
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_get_observation(self._h, C.c_void_p(self._obs.data_ptr()), self._stream()))
             _native.check(self.L.solorl_reset_masked(self._h, pm, C.c_void_p(self._obs.data_ptr()), self._stream()))
+        if self._act is not None:                       # the selected envs start an episode with their next action
+            self._act_restart.bitwise_or_(m.ne(0).to(torch.uint8))
+        self._noise(self._obs, m)                       # the rows the engine has just written: the selected ones
         if self._shape_mem is not None:                 # the selected envs start an episode (its sums so far are dropped, not counted)
             self._shape_mem.data.masked_fill_(m.bool().unsqueeze(-1), 0.0)
         if self._norm is not None:
@@ -688,7 +804,8 @@ class SoloVecEnv:
 
 def make_vec_envs(config, num_envs, env_constructor=None, gamma=0.99, device=None, training=True, seed=1,
                   env_id_offset=0, norm_obs=False, norm_ret=False, clipob=10., cliprew=10., epsilon=1e-8,
-                  push_interval=None, push_max_vel=0.0, push_max_yaw_rate=0.0, reward_shaping=None):
+                  push_interval=None, push_max_vel=0.0, push_max_yaw_rate=0.0, reward_shaping=None,
+                  obs_noise=None, action_delay=None, motor_gain_range=0.0):
     """Signature of agents/ppo/envs.py:14.  ``env_constructor`` (the per-process gym env class of the
     reference) is accepted for call-site compatibility and ignored.  ``norm_obs`` / ``norm_ret`` are VecNormalize's ``ob`` /
     ``ret`` (agents/running_mean_std.py:79; the reference's launcher passes False, False, and so do the defaults here) with its
@@ -698,7 +815,12 @@ def make_vec_envs(config, num_envs, env_constructor=None, gamma=0.99, device=Non
     up to ``push_max_vel`` m/s on the base's world x and y velocity and ``push_max_yaw_rate`` rad/s on its yaw rate, in front of every
     step (SoloVecEnv.set_perturbation).
     ``reward_shaping`` (a dict with ``weights`` and the parameters as further keys, as configs/shaping_walk12.yaml holds it; None = no
-    shaping, and nothing is allocated or launched): shaped reward terms behind every step (SoloVecEnv.set_reward_shaping)."""
+    shaping, and nothing is allocated or launched): shaped reward terms behind every step (SoloVecEnv.set_reward_shaping).
+    ``obs_noise`` (a dict of half-widths per observation group, or a noise file's dict with ``groups`` and ``history`` as
+    configs/noise_solo.yaml holds it, or an [obs_dim] vector; None = clean observations): uniform sensor noise on every observation
+    (SoloVecEnv.set_obs_noise).  ``action_delay`` (an int or a (lo, hi) pair of control steps within 0..4; None = none) and
+    ``motor_gain_range`` (each joint's action is scaled by 1 + U(-g, g), drawn per env and episode; 0 = exact): actuation latency and
+    motor gain error in front of every step (SoloVecEnv.set_actuation).  Off, nothing is allocated or launched."""
     envs = SoloVecEnv(config, num_envs, device=device, seed=seed, env_id_offset=env_id_offset, norm_obs=norm_obs, norm_ret=norm_ret,
                       clipob=clipob, cliprew=cliprew, gamma=gamma, epsilon=epsilon)
     if push_interval is not None:
@@ -709,6 +831,10 @@ def make_vec_envs(config, num_envs, env_constructor=None, gamma=0.99, device=Non
         if not isinstance(weights, dict):
             raise ValueError("reward_shaping needs a `weights` mapping of term name -> weight")
         envs.set_reward_shaping(weights, **rs)
+    if obs_noise is not None:
+        envs.set_obs_noise(obs_noise)
+    if action_delay is not None or motor_gain_range:
+        envs.set_actuation(action_delay, motor_gain_range)
     if not training:
         envs.eval()
     return envs

@@ -21,6 +21,51 @@ def push_interval(text):
     return parts[0], parts[-1]
 
 
+def action_delay(text):
+    """--action-delay LO[:HI] -> (lo, hi): control steps of actuation latency, 0 <= lo <= hi <= 4"""
+    try:
+        parts = [int(x) for x in text.split(":")]
+    except ValueError:
+        parts = []
+    if len(parts) not in (1, 2) or parts[0] < 0 or parts[-1] < parts[0] or parts[-1] > 4:
+        raise argparse.ArgumentTypeError("expected LO or LO:HI with 0 <= LO <= HI <= 4, got %r" % text)
+    return parts[0], parts[-1]
+
+
+def motor_gain_range(text):
+    """--motor-gain-range G -> G, 0 <= G < 1"""
+    try:
+        g = float(text)
+    except ValueError:
+        g = -1.0
+    if not 0.0 <= g < 1.0:
+        raise argparse.ArgumentTypeError("expected a gain range in [0, 1), got %r" % text)
+    return g
+
+
+def add_channel_flags(p):
+    """the three flags train_ppo.py and eval_ppo.py share"""
+    p.add_argument("--obs-noise", type=str, default=None, metavar="FILE.yaml",
+                   help="uniform sensor noise on every observation: `groups:` (observation group -> half-width in physical units) and "
+                        "`history:`, e.g. configs/noise_solo.yaml (default: clean observations)")
+    p.add_argument("--action-delay", type=action_delay, default=None, metavar="LO[:HI]",
+                   help="every env applies the action it received LO..HI control steps ago (drawn per env and episode, at most 4; default: none)")
+    p.add_argument("--motor-gain-range", type=motor_gain_range, default=0.0, metavar="G",
+                   help="each joint's action is scaled by 1 + U(-G, G), drawn per env and episode (default: 0, exact)")
+
+
+def load_obs_noise(path, config):
+    """--obs-noise FILE.yaml -> its dict, with unknown groups and keys refused by name before anything is built"""
+    from solorl_amd.channel import scales_from_dict
+    from solorl_amd.config import config_from_dict, load_yaml
+    noise = load_yaml(path)
+    try:
+        scales_from_dict(config_from_dict(config), noise)
+    except (ValueError, AttributeError, TypeError) as e:
+        raise SystemExit("--obs-noise %s: %s" % (path, e))
+    return noise
+
+
 def get_ppo_args(argv=None):
     p = argparse.ArgumentParser("PPO args")
     p.add_argument("--num-agents", type=int, default=32)          # envs PER GPU
@@ -62,6 +107,7 @@ def get_ppo_args(argv=None):
     p.add_argument("--reward-shaping", type=str, default=None, metavar="FILE.yaml",
                    help="add shaped reward terms to every step's reward: `weights:` (term name -> weight) and the terms' parameters, "
                         "e.g. configs/shaping_walk12.yaml (default: the reference's reward alone)")
+    add_channel_flags(p)
     p.add_argument("--num-steps", type=int, default=None, help="rollout length (default: episode_length, train_ppo.py:62-63)")
     return p.parse_args(argv)
 
@@ -88,6 +134,8 @@ def main(argv=None):
         except ValueError as e:
             raise SystemExit("--reward-shaping %s: %s" % (args.reward_shaping, e))
         args.reward_shaping = shaping
+    if args.obs_noise is not None:
+        args.obs_noise = load_obs_noise(args.obs_noise, config)
     writer = None
     rank = int(os.environ.get("RANK", "0"))
     if args.logdir is not None:      # run directory named as training/train_ppo.py:64-72
