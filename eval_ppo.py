@@ -9,7 +9,10 @@ every K control steps with an xy velocity drawn uniformly from +-V m/s (robustne
 reduced on the device): per foot the duty factor, mean and peak normal force, slip distance and peak swing clearance, and the mean
 ratio of the summed normal forces to the robot's weight; --dump then also holds env 0's foot positions and forces.
 --obs-noise FILE.yaml --action-delay LO[:HI] --motor-gain-range G (train_ppo.py's flags) evaluate under sensor noise, actuation latency
-and motor gain error (SoloVecEnv.set_obs_noise / set_actuation)."""
+and motor gain error (SoloVecEnv.set_obs_noise / set_actuation).
+--commands FILE.yaml (train_ppo.py's flag) evaluates a policy trained with per-env velocity commands under commands drawn from the file's
+ranges; --command VX VY WZ gives every env that one command for the whole run (joystick control).  With either, the summary adds the
+mean absolute tracking error of the base-frame velocity xy [m/s] and of the base-frame yaw rate [rad/s] over all envs and steps."""
 import argparse
 import os
 import sys
@@ -56,6 +59,14 @@ class GaitMetrics:
         return out
 
 
+def base_frame(quat, v):
+    """R(quat)^T v for rows of unit quaternions (x, y, z, w) and world-frame vectors [N, 3]: v - 2 w (u x v) + 2 u x (u x v), u = quat.xyz"""
+    import torch
+    u, w = quat[:, :3], quat[:, 3:4]
+    c = torch.cross(u, v, dim=1)
+    return v - 2.0 * w * c + 2.0 * torch.cross(u, c, dim=1)
+
+
 def main(argv=None):
     p = argparse.ArgumentParser("PPO eval")
     p.add_argument("--checkpoint-dir", required=True)
@@ -71,8 +82,11 @@ def main(argv=None):
     p.add_argument("--max-steps", type=int, default=0, help="stop after K control steps even if fewer than --num-runs episodes have ended (0 = no limit)")
     p.add_argument("--push-interval", type=int, default=0, help="kick every env's base velocity every K control steps (0 = never)")
     p.add_argument("--push-max-vel", type=float, default=0.0, help="a kick's x and y velocity change is uniform in +-V m/s")
-    from train_ppo import add_channel_flags, load_obs_noise
+    from train_ppo import add_channel_flags, load_commands, load_obs_noise
     add_channel_flags(p)
+    p.add_argument("--command", type=float, nargs=3, default=None, metavar=("VX", "VY", "WZ"),
+                   help="one fixed velocity command for every env: vx vy [m/s, base frame] and yaw rate [rad/s]; with --commands it keeps "
+                        "the file's obs_scale and replaces its ranges")
     a = p.parse_args(argv)
 
     import numpy as np
@@ -89,9 +103,20 @@ def main(argv=None):
     # a checkpoint trained with --normalize-obs carries the observation statistics: the policy sees observations scaled by them,
     # frozen (testing/test_ppo.py:89-90); rewards are reported raw
     ob_rms = ckpt.get("ob_rms")
+    commands = None if a.commands is None else load_commands(a.commands)
+    if a.command is not None:           # lo == hi, redrawn at every step, never zeroed: every env holds exactly this command
+        vx, vy, wz = a.command
+        commands = dict(obs_scale=(commands or {}).get("obs_scale", (1.0, 1.0, 1.0)), lin_vel_x=(vx, vx), lin_vel_y=(vy, vy), yaw_rate=(wz, wz),
+                        interval=1, zero_prob=0.0, min_lin_norm=0.0)
     env = make_vec_envs(config, a.num_agents, None, device=dev, training=False, seed=a.seed, norm_obs=ob_rms is not None,
                         obs_noise=None if a.obs_noise is None else load_obs_noise(a.obs_noise, config), action_delay=a.action_delay,
-                        motor_gain_range=a.motor_gain_range)
+                        motor_gain_range=a.motor_gain_range, commands=commands)
+    width = ckpt["state_dict"]["base.features.0.weight"].shape[1]
+    if width != env.obs_dim:
+        raise SystemExit("the checkpoint's policy reads %d observation words, this run's observation has %d (%d of the engine%s): "
+                         "a policy trained %s --commands needs them %s" % (
+                             width, env.obs_dim, env.engine_obs_dim, " + 3 command words" if commands is not None else "",
+                             "with" if width == env.engine_obs_dim + 3 else "without", "given here" if commands is None else "left out"))
     env.ob_rms = ob_rms
     env.eval()
     policy = Policy(env.observation_space.shape, env.action_space, None, {"hidden_size": a.hidden_size}).to(dev)
@@ -106,6 +131,8 @@ def main(argv=None):
     rows = kin = None
     obs = env.reset()
     push_gen, steps = None, 0
+    track = torch.zeros(2, dtype=torch.float64, device=dev) if commands is not None else None     # sums of |v_b.xy - cmd.xy| and |w_b.z - cmd.z|
+    track_rows, track_n = None, 0.0
     if a.push_interval > 0:
         push_gen = torch.Generator(device=dev); push_gen.manual_seed(a.seed)
         dv = torch.zeros((a.num_agents, 3), device=dev)
@@ -127,7 +154,16 @@ def main(argv=None):
             s = env.get_state(0)
             traj["pos"].append(list(s.pos)); traj["quat"].append(list(s.quat)); traj["q"].append(list(s.q))
             traj["action"].append(action[0].cpu().numpy())
+        if track is not None:
+            cmd = env.last_commands.clone()              # the command the policy has just acted on (the step may redraw it)
         obs, reward, done, infos = env.step(action)
+        if track is not None:                            # the state after the step against that command; an env the step finished holds
+            track_rows = env.get_states(out=track_rows)  # its reset state and is left out
+            vb, wb = base_frame(track_rows.quat, track_rows.lin_vel), base_frame(track_rows.quat, track_rows.ang_vel)
+            live = (done == 0).to(torch.float64)
+            track[0] += ((vb[:, :2] - cmd[:, :2]).norm(dim=1) * live).sum()
+            track[1] += ((wb[:, 2] - cmd[:, 2]).abs() * live).sum()
+            track_n += float(live.sum())
         ret += reward.view(-1)
         if a.dump:
             traj["reward"].append(float(reward[0])); traj["done"].append(float(done[0]))
@@ -141,6 +177,10 @@ def main(argv=None):
     mean = lambda v: sum(v) / n if n else float("nan")      # (--max-steps can end the run before any episode has)
     print("episodes {} mean length {:.1f} mean reward {:.3f} mean success {:.2f}".format(n, mean(ep_len), mean(ep_R), mean(ep_succ)))
     result = dict(episodes=n, mean_length=mean(ep_len), mean_reward=mean(ep_R), mean_success=mean(ep_succ))
+    if track is not None:
+        e = (track / max(track_n, 1.0)).tolist()
+        print("command tracking over {:.0f} env steps: mean |v_b.xy - cmd.xy| {:.4f} m/s  mean |w_b.z - cmd.z| {:.4f} rad/s".format(track_n, e[0], e[1]))
+        result["tracking_error_lin_vel"], result["tracking_error_yaw_rate"] = e
     if gait is not None:
         result["gait"] = gait.report()
     if a.dump:

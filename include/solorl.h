@@ -51,6 +51,9 @@
  *   solorl_obs_noise / solorl_actuate : what stands between the policy and the engine in a randomised training run (no reference
  *                             counterpart): uniform sensor noise on observation rows, and actuation latency with a per-joint motor gain
  *                             error on action rows -- drawn on the device from a Philox stream per env, one launch each, handle-free
+ *   solorl_commands / solorl_shape_reward_cmd : per-env velocity commands (no reference counterpart): drawn from ranges and resampled on
+ *                             the device from a Philox stream per env, appended to the observation rows as three words, one launch,
+ *                             handle-free; and the shaped reward's two tracking terms against each env's own command
  *   solorl_destroy         <- agents/ppo/envs.py:129-135 (close)
  *
  * Plain pointers and sizes only; no torch types.  All array arguments are DEVICE pointers
@@ -503,6 +506,59 @@ int solorl_actuate(const solorl_actuation* p, int n, const uint8_t* restart /* [
                    solorl_env_actuator* mem /* [n] in/out */, const float* actions_in /* [n][A] */,
                    float* actions_out /* [n][A]; may be actions_in */, int device_id, void* stream);
 
+/* Velocity commands (no reference counterpart; the per-env commands of legged_gym-style tasks): every env holds a command (vx, vy in
+ * m/s and a yaw rate in rad/s, base frame) drawn from ranges and drawn anew after a per-env number of control steps; the policy sees it
+ * as three more observation words and the tracking terms of solorl_shape_reward_cmd compare the env against it.  Handle-free like the
+ * two calls above: ONE launch on `stream`, no allocation, no host synchronisation (capturable); everything is a function of seed,
+ * global env id gid = env_id_offset + i and the env's memory row, so W shards at offsets k n draw what one batch of W n rows draws.
+ * Key (seed_lo, seed_hi).  Per live env, in this order:
+ *   1 decide    the env draws now if (restart && restart[i]) || mem.draws == 0 (a zeroed row draws at its first call); otherwise
+ *               countdown -= 1 and the env draws now if countdown == 0
+ *   2 draw      d = mem.draws; counter (gid_lo, gid_hi, 2 d, 7) -- the env's own stream uses 1, 2, 3 in the last word, the kicks 4, the
+ *               noise 5, the actuator draws 6; a draw never reads or advances rng_counter.
+ *               word 0   interval = interval_min + word % (interval_max - interval_min + 1)
+ *               word 1+k u_k = (word >> 8) * 2^-24; cmd_k = lo_k + u_k * (hi_k - lo_k): fp64, the difference, the product and the sum each
+ *                        rounded (no fused multiply-add), so lo_k == hi_k gives exactly lo_k
+ *               counter (gid_lo, gid_hi, 2 d + 1, 7) word 0: u < zero_prob sets all three components to 0 (stand still)
+ *               then cmd_0 * cmd_0 + cmd_1 * cmd_1 < min_lin_norm * min_lin_norm sets cmd_0 = cmd_1 = 0 (each product rounded, then the sum)
+ *               finally draws = d + 1 (mod 2^32) and countdown = interval
+ *   3 output    cmd_out[i][k] = cmd_k; obs_out[i][0..D) = the bits of obs_in[i][0..D) (NaN payloads and -0.0 survive);
+ *               obs_out[i][D + k] = (float)(cmd_k * obs_scale[k]), the product rounded in double first.  obs_in and obs_out may both be
+ *               NULL: then only mem and cmd_out are written.  obs_in must not overlap obs_out (the row strides differ).
+ *   masked      (mask byte 0) nothing of the row is read or written, in any array
+ *   An obs_in that is 16-byte aligned is read as 16-byte words, any other word by word; obs_out is written word by word; the values
+ *   are the same.  A heading command (a yaw rate derived from a target heading) is not offered: see DESIGN.md.
+ *   Null p or mem, exactly one of obs_in and obs_out null, n < 1, obs_dim < 1 or > 210, a range that is not finite or has lo > hi, an
+ *   obs_scale that is not finite, zero_prob outside [0, 1] (or NaN), min_lin_norm negative or not finite, an interval range outside
+ *   1 <= interval_min <= interval_max <= 1 << 20: SOLORL_ERR_INVALID, the message starts with "solorl_commands:" (checked before any
+ *   HIP call).
+ *
+ * solorl_shape_reward_cmd: solorl_shape_reward with the commands per env.  cmd != NULL: terms 14 and 15 of row i use cmd[i].cmd[0..2] in
+ *   place of p->cmd_lin_vel[0..1] and p->cmd_yaw_rate (only the cmd member is read, of live rows only).  cmd == NULL: solorl_shape_reward,
+ *   which is this call with NULL.  Its refusals carry the prefix "solorl_shape_reward:". */
+typedef struct solorl_command_params {
+  uint64_t seed; int64_t env_id_offset;
+  double lo[3], hi[3];        /* vx, vy [m/s, base frame], yaw rate [rad/s]; finite, lo <= hi */
+  double obs_scale[3];        /* the observation word is (float)(cmd_k * obs_scale[k]); finite */
+  double zero_prob;           /* in [0, 1]: probability that a draw is the zero command (stand still) */
+  double min_lin_norm;        /* >= 0: a drawn (vx, vy) shorter than this becomes (0, 0) */
+  int32_t interval_min, interval_max;   /* control steps between draws, 1 <= min <= max <= 1 << 20 */
+  int32_t obs_dim;            /* D: width of the engine's observation rows; 1 <= D <= 210 */
+  int32_t reserved;
+} solorl_command_params;
+typedef struct solorl_env_command {     /* caller-owned DEVICE rows, 32 B */
+  double cmd[3]; int32_t countdown; uint32_t draws;
+} solorl_env_command;
+int solorl_commands(const solorl_command_params* p, const uint8_t* mask /* [n] or NULL */,
+                    const uint8_t* restart /* [n] or NULL */, int n, solorl_env_command* mem /* [n] in/out */,
+                    const float* obs_in /* [n][D] or NULL */, float* obs_out /* [n][D+3] or NULL */,
+                    double* cmd_out /* [n][3] or NULL */, int device_id, void* stream);
+int solorl_shape_reward_cmd(const solorl_config* cfg, const solorl_shape_params* p,
+                            const solorl_env_state* states, const uint8_t* mask, int n, const float* actions,
+                            const uint8_t* done, solorl_env_shape* mem, float* reward, double* terms_out,
+                            double* ep_out, const solorl_env_command* cmd /* [n] rows or NULL */,
+                            int device_id, void* stream);
+
 /* Fused return computation over a rollout of T steps x N envs (device arrays, time-major [t][n]).
  * use_gae != 0:  value_preds[T][:] = next_value;  delta_t = r_t + gamma V_{t+1} m_{t+1} - V_t;
  *                A_t = delta_t + gamma lambda m_{t+1} A_{t+1};  returns[t] = A_t + V_t      (storage.py:41-50)
@@ -553,7 +609,8 @@ int solorl_ppo_loss(const float* mean, const float* logstd, const float* values,
 
 /* Parameters of the reference's MLP actor-critic in PyTorch layout (nn.Linear weight = [out][in], row-major), device pointers:
  * base.critic.{0,2,4}, base.features.{0,2}, pi_dist.mean, pi_dist.logstd (agents/ppo/policy.py:62-81,138-148).  The kernels
- * are built for hidden = 64 and (obs_dim, act_dim) in {(38|42|76|84, 12), (30|34|60|68, 8)} -- zero or one history level; other shapes
+ * are built for hidden = 64 and (obs_dim, act_dim) in {(38|42|76|84, 12), (30|34|60|68, 8)} -- zero or one history level -- and
+ * {(41|45, 12), (33|37, 8)} -- zero history levels with the three command words of solorl_commands; other shapes
  * return SOLORL_ERR_INVALID and the caller keeps its framework path.  Alignment: the weight matrices critic_w1/w2, actor_w1,
  * mean_w -- and, when obs_dim % 4 == 0, critic_w0, actor_w0 and every `obs` array handed to solorl_policy_act /
  * solorl_ppo_batch -- are read as float4 rows and must start on a 16-byte boundary (checked: SOLORL_ERR_INVALID otherwise). */

@@ -20,7 +20,7 @@ SYMBOLS = ("solorl_default_config", "solorl_create", "solorl_destroy", "solorl_d
            "solorl_get_states", "solorl_set_states", "solorl_reset_masked",
            "solorl_set_perturbation", "solorl_perturb", "solorl_get_perturbation",
            "solorl_norm_scratch_count", "solorl_normalize_obs", "solorl_normalize_rewards", "solorl_kinematics", "solorl_dynamics",
-           "solorl_shape_reward", "solorl_obs_noise", "solorl_actuate")
+           "solorl_shape_reward", "solorl_obs_noise", "solorl_actuate", "solorl_commands", "solorl_shape_reward_cmd")
 
 
 class PolicyParams(C.Structure):            # solorl_policy_params
@@ -65,6 +65,16 @@ class Actuation(C.Structure):               # solorl_actuation
 class EnvActuator(C.Structure):             # solorl_env_actuator
     _fields_ = [("buf", (C.c_float * 12) * DELAY_MAX), ("gain", C.c_float * 12), ("latency", C.c_int32), ("fill", C.c_int32),
                 ("episodes", C.c_uint32), ("reserved", C.c_int32)]
+
+
+class CommandParams(C.Structure):           # solorl_command_params
+    _fields_ = [("seed", C.c_uint64), ("env_id_offset", C.c_int64), ("lo", C.c_double * 3), ("hi", C.c_double * 3), ("obs_scale", C.c_double * 3),
+                ("zero_prob", C.c_double), ("min_lin_norm", C.c_double), ("interval_min", C.c_int32), ("interval_max", C.c_int32),
+                ("obs_dim", C.c_int32), ("reserved", C.c_int32)]
+
+
+class EnvCommand(C.Structure):              # solorl_env_command
+    _fields_ = [("cmd", C.c_double * 3), ("countdown", C.c_int32), ("draws", C.c_uint32)]
 
 
 class SoloRLError(RuntimeError):
@@ -140,6 +150,12 @@ def lib():
         L.solorl_obs_noise.argtypes = [C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.solorl_actuate.argtypes = [C.POINTER(Actuation), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.solorl_obs_noise.restype = L.solorl_actuate.restype = C.c_int
+        # velocity commands (command.py): handle-free; params is a host struct, every array a device pointer.  solorl_shape_reward_cmd is
+        # solorl_shape_reward with the command rows in front of device_id
+        L.solorl_commands.argtypes = [C.POINTER(CommandParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int, C.c_void_p]
+        L.solorl_shape_reward_cmd.argtypes = L.solorl_shape_reward.argtypes[:11] + [C.c_void_p, C.c_int, C.c_void_p]
+        L.solorl_commands.restype = L.solorl_shape_reward_cmd.restype = C.c_int
         for s in SYMBOLS:
             getattr(L, s)
         # the ctypes mirrors in config.py / this file are written against one layout of include/solorl.h's structs

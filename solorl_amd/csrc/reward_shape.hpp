@@ -71,10 +71,11 @@ template <int ROBOT> constexpr int shape_collision_bits() {
 
 // One row.  ld(w): word w of the state row (STATE_SW offsets);  cmask: its contact_mask;  foot(k): word k of the feet's 28 words
 // (shape_foot_slot);  mld(w) / mst(w, v): word w of the solorl_env_shape row (SHAPE_MW offsets; word SHAPE_MW(prev_contact) holds the
-// two int32 members);  tst(k, v): terms_out[k];  ep(k, v): ep_out[k] += v;  a: the row's actions;  reward: the row's reward or nullptr.
+// two int32 members);  tst(k, v): terms_out[k];  ep(k, v): ep_out[k] += v;  a: the row's actions;  reward: the row's reward or nullptr;
+// cmd: the row's own command (vx, vy, yaw rate: solorl_shape_reward_cmd) or nullptr = the one of P.
 template <int ROBOT, typename LD, typename FT, typename MLD, typename MST, typename TST, typename EP>
 SD void shape_row(LD ld, int cmask, FT foot, MLD mld, MST mst, TST tst, EP ep, const solorl_shape_params& P, double sim_dt, double dtc,
-                  const float* a, bool done, float* reward) {
+                  const float* a, bool done, float* reward, const double* cmd = nullptr) {
   constexpr int NQ = Robot<ROBOT>::NQ;
   int32_t iw[2];                                            // prev_contact, valid
   const double ints = mld(SHAPE_MW(prev_contact));
@@ -142,7 +143,8 @@ SD void shape_row(LD ld, int cmask, FT foot, MLD mld, MST mst, TST tst, EP ep, c
   });
   t[9] = slip; t[10] = clear; t[11] = force; t[12] = airt;
   t[13] = (double)__builtin_popcount((unsigned)(cmask & shape_collision_bits<ROBOT>()));
-  const double ex = vb.x - P.cmd_lin_vel[0], ey = vb.y - P.cmd_lin_vel[1], ez = wb.z - P.cmd_yaw_rate;
+  const double cx = cmd ? cmd[0] : P.cmd_lin_vel[0], cy = cmd ? cmd[1] : P.cmd_lin_vel[1], cz = cmd ? cmd[2] : P.cmd_yaw_rate;
+  const double ex = vb.x - cx, ey = vb.y - cy, ez = wb.z - cz;
   t[14] = exp(-(ex * ex + ey * ey) / P.tracking_sigma);
   t[15] = exp(-(ez * ez) / P.tracking_sigma);
   double s = 0.0;
@@ -166,14 +168,14 @@ template <int ROBOT, int L, typename LD, typename PUT> SD void shape_leg(LD ld, 
 
 // one row given as plain memory (the host program): state row, memory row in place, terms [16] or nullptr, ep_out column i of [17][n]
 template <int ROBOT> SD void env_shape_row(const double* in, double* mem, const float* a, bool done, float* reward, double* terms, double* ep,
-                                            size_t n, size_t i, const solorl_shape_params& P, double sim_dt, double dtc) {
+                                            size_t n, size_t i, const solorl_shape_params& P, double sim_dt, double dtc, const double* cmd = nullptr) {
   int32_t cmask;
   __builtin_memcpy(&cmask, in + KIN_IN_MASK_WORD, sizeof(cmask));
   double feet[SHAPE_FEET_WORDS];
   auto ld = [&](int w) { return in[w]; };
   static_for<4>([&](auto lc) { shape_leg<ROBOT, decltype(lc)::value>(ld, cmask, [&](int k, double v) { feet[k] = v; }, sim_dt); });
   shape_row<ROBOT>(ld, cmask, [&](int k) { return feet[k]; }, [&](int w) { return mem[w]; }, [&](int w, double v) { mem[w] = v; },
-                   [&](int k, double v) { if (terms) terms[k] = v; }, [&](int k, double v) { if (ep) ep[(size_t)k * n + i] += v; }, P, sim_dt, dtc, a, done, reward);
+                   [&](int k, double v) { if (terms) terms[k] = v; }, [&](int k, double v) { if (ep) ep[(size_t)k * n + i] += v; }, P, sim_dt, dtc, a, done, reward, cmd);
 }
 
 }  // namespace solo

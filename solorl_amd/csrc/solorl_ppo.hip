@@ -804,8 +804,9 @@ __global__ void __launch_bounds__(1024) ppo_clip_adam_kernel(const AdamArgs K) {
   if (tid == 0) { *K.step = step; if (K.offset) *K.offset += K.inc; }
 }
 
-// observation widths of zero or one history level (14 + 2 n (+ 4 pointGoal), x 1 or x 2), action widths n = 8 / 12
-#define SOLO_DIMS_LIST(X) X(76, 12) X(84, 12) X(38, 12) X(42, 12) X(60, 8) X(68, 8) X(30, 8) X(34, 8)
+// observation widths of zero or one history level (14 + 2 n (+ 4 pointGoal), x 1 or x 2), action widths n = 8 / 12; and the
+// zero-history widths with the three velocity-command words of solorl_commands behind them (odd: every access goes word by word)
+#define SOLO_DIMS_LIST(X) X(76, 12) X(84, 12) X(38, 12) X(42, 12) X(60, 8) X(68, 8) X(30, 8) X(34, 8) X(41, 12) X(45, 12) X(33, 8) X(37, 8)
 bool dims_supported(int O, int A) {
 #define SOLO_DIMS(O_, A_) if (O == O_ && A == A_) return true;
   SOLO_DIMS_LIST(SOLO_DIMS)
@@ -814,7 +815,8 @@ bool dims_supported(int O, int A) {
 }
 int fail_dims() {
   return solorl_fail_(SOLORL_ERR_INVALID, "policy kernels are built for the observation / action sizes of zero or one history level "
-                                          "(38, 42, 76 or 84 x 12; 30, 34, 60 or 68 x 8); use the PyTorch path for other shapes");
+                                          "(38, 42, 76 or 84 x 12; 30, 34, 60 or 68 x 8) and for zero history levels with velocity commands "
+                                          "(41 or 45 x 12; 33 or 37 x 8); use the PyTorch path for other shapes");
 }
 template <typename F> int dispatch_dims(int O, int A, F&& f) {
 #define SOLO_DIMS(O_, A_) if (O == O_ && A == A_) return f(std::integral_constant<int, O_>(), std::integral_constant<int, A_>());

@@ -11,6 +11,8 @@
 // (ep_out is field-major: consecutive lanes, consecutive addresses).  All lanes copy the memory rows and the terms out.
 // One LDS row holds everything of an env: 54 + 45 + 28 + 16 = 143 words.  143 is odd, so the 64 lanes' 8-byte accesses at one immediate
 // offset fall on 64 different bank pairs: no conflict in any phase of the arithmetic.
+// solorl_shape_reward_cmd: the tracking terms' command is the row's own (a solorl_env_command row's three doubles, read by the lane that
+// evaluates the row's terms straight from global memory: 24 B per row, not staged); solorl_shape_reward is that call without rows.
 // Residency, by both limits.  LDS: 143 x 8 B + the live flag = 1148 B per row; two workgroups per CU may hold 80 KB each, 71 rows -- more
 // than the 64 lanes of a wavefront, so the lanes bound it: SHAPE_ENVS = 64, 73 472 B of static LDS, two workgroups 143.5 KB of the CU's
 // 160 (a third would need 215).  Registers: a leg is KinRow's chain without its stores and sums, 100 VGPRs (Solo12) / 98 (Solo8), no
@@ -54,7 +56,8 @@ template <int ROBOT>
 __global__ __launch_bounds__(64 * SHAPE_WAVES) void shape_rows_kernel(const double* __restrict__ states, const uint8_t* __restrict__ mask, int n,
                                                                        const float* __restrict__ actions, const uint8_t* __restrict__ done,
                                                                        double* __restrict__ mem, float* __restrict__ reward, double* __restrict__ terms_out,
-                                                                       double* __restrict__ ep_out, solorl_shape_params P, double sim_dt, double dtc) {
+                                                                       double* __restrict__ ep_out, const solorl_env_command* __restrict__ cmd,
+                                                                       solorl_shape_params P, double sim_dt, double dtc) {
   using namespace solo;
   __shared__ double s_row[SHAPE_ENVS * SHAPE_ROW_WORDS];
   __shared__ int s_live[SHAPE_ENVS];
@@ -79,7 +82,7 @@ __global__ __launch_bounds__(64 * SHAPE_WAVES) void shape_rows_kernel(const doub
     shape_row<ROBOT>(ld, cmask, [&](int k) { return row[SHAPE_OFF_FEET + k]; }, [&](int w) { return row[SHAPE_OFF_MEM + w]; },
                      [&](int w, double v) { row[SHAPE_OFF_MEM + w] = v; }, [&](int k, double v) { row[SHAPE_OFF_TERMS + k] = v; },
                      [&](int k, double v) { if (ep_out) ep_out[(size_t)k * n + i] += v; }, P, sim_dt, dtc,
-                     actions + i * Robot<ROBOT>::NQ, done != nullptr && done[i] != 0, reward ? reward + i : nullptr);
+                     actions + i * Robot<ROBOT>::NQ, done != nullptr && done[i] != 0, reward ? reward + i : nullptr, cmd ? cmd[i].cmd : nullptr);
   }
   __syncthreads();
   rows_copy_out<SHAPE_MEM_WORDS>(mem, s_row, SHAPE_OFF_MEM, s_live);
@@ -88,9 +91,9 @@ __global__ __launch_bounds__(64 * SHAPE_WAVES) void shape_rows_kernel(const doub
 
 }  // namespace
 
-extern "C" int solorl_shape_reward(const solorl_config* cfg, const solorl_shape_params* p, const solorl_env_state* states, const uint8_t* mask, int n,
-                                   const float* actions, const uint8_t* done, solorl_env_shape* mem, float* reward, double* terms_out, double* ep_out,
-                                   int device_id, void* stream) {
+extern "C" int solorl_shape_reward_cmd(const solorl_config* cfg, const solorl_shape_params* p, const solorl_env_state* states, const uint8_t* mask, int n,
+                                       const float* actions, const uint8_t* done, solorl_env_shape* mem, float* reward, double* terms_out, double* ep_out,
+                                       const solorl_env_command* cmd, int device_id, void* stream) {
   const char* fn = "solorl_shape_reward";
   if (int rc = solo::rows_check_args(fn, cfg, states, mem, n)) return rc;
   if (!p || !actions) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_shape_reward: null params or actions");
@@ -102,6 +105,12 @@ extern "C" int solorl_shape_reward(const solorl_config* cfg, const solorl_shape_
   if (cfg->frame_skip < 1) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_shape_reward: frame_skip must be >= 1");
   if (int rc = solo::select_device(device_id)) return rc;
   return ShapeShell::launch("solorl_shape_reward: shape_rows_kernel launch", cfg->robot == SOLORL_ROBOT_SOLO12 ? shape_rows_kernel<1> : shape_rows_kernel<0>, n, stream,
-                            reinterpret_cast<const double*>(states), mask, n, actions, done, reinterpret_cast<double*>(mem), reward, terms_out, ep_out, *p,
+                            reinterpret_cast<const double*>(states), mask, n, actions, done, reinterpret_cast<double*>(mem), reward, terms_out, ep_out, cmd, *p,
                             cfg->sim_dt, cfg->sim_dt * (double)cfg->frame_skip);
+}
+
+extern "C" int solorl_shape_reward(const solorl_config* cfg, const solorl_shape_params* p, const solorl_env_state* states, const uint8_t* mask, int n,
+                                   const float* actions, const uint8_t* done, solorl_env_shape* mem, float* reward, double* terms_out, double* ep_out,
+                                   int device_id, void* stream) {
+  return solorl_shape_reward_cmd(cfg, p, states, mask, n, actions, done, mem, reward, terms_out, ep_out, nullptr, device_id, stream);
 }

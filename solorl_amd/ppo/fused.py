@@ -54,7 +54,8 @@ def fused_ppo_loss(mean, logstd, values, action, old_logp, adv, vpred, ret, clip
 # Hand-written policy kernels (csrc/solorl_ppo.hip): the whole forward of Policy.act in one launch, and one PPO mini-batch's
 # gather + forward + losses + back-propagation in one launch (the weight gradients stay GEMMs).
 
-_SUPPORTED = {(76, 12), (84, 12), (38, 12), (42, 12), (60, 8), (68, 8), (30, 8), (34, 8)}
+_SUPPORTED = {(76, 12), (84, 12), (38, 12), (42, 12), (60, 8), (68, 8), (30, 8), (34, 8),
+              (41, 12), (45, 12), (33, 8), (37, 8)}          # (... and zero history levels + the three command words of solorl_commands)
 
 
 def policy_kernels_supported(actor_critic):

@@ -21,6 +21,10 @@ Differences that come with the GPU engine (documented, not behavioural):
     and actuation latency with a per-joint motor gain error between the stored raw actions and the engine, in the eager and in the
     captured rollout alike (SoloVecEnv.set_obs_noise / set_actuation); both are keyed by global env id, so ranks draw like one batch.
     With noise the policy cannot run inside the step kernel (it would read clean observations): the rollout takes two launches per step;
+  * args.commands (train_ppo.py --commands FILE.yaml: a dict of ranges; no reference counterpart) gives every env a velocity command of
+    its own, drawn and resampled on the device behind every step launch of the eager and of the captured rollout alike
+    (SoloVecEnv(commands=)): the observation and the policy are three words wider, and the tracking terms of args.reward_shaping compare
+    each env against its own command.  The policy cannot run inside the step kernel either (it would not see the command words);
   * multi-GPU: one process per GPU (`python -m torch.distributed.run --nproc-per-node W ...`), envs
     sharded by rank (global env id = rank*N + i), flat-bucket RCCL gradient all-reduce (ppo.py).
 """
@@ -93,7 +97,8 @@ def train(args, config, env_constructor=None, writer=None):
                          norm_obs=norm_obs, norm_ret=norm_ret, push_interval=getattr(args, "push_interval", None),
                          push_max_vel=getattr(args, "push_max_vel", 0.0), push_max_yaw_rate=getattr(args, "push_max_yaw_rate", 0.0),
                          reward_shaping=getattr(args, "reward_shaping", None), obs_noise=getattr(args, "obs_noise", None),
-                         action_delay=getattr(args, "action_delay", None), motor_gain_range=getattr(args, "motor_gain_range", 0.0))
+                         action_delay=getattr(args, "action_delay", None), motor_gain_range=getattr(args, "motor_gain_range", 0.0),
+                         commands=getattr(args, "commands", None))
     shaping = getattr(args, "reward_shaping", None) is not None
     action_dim = envs.action_space.shape[0]
     base = torch.load(args.base_checkpoint) if getattr(args, "base_checkpoint", None) else None

@@ -97,12 +97,14 @@ def _ptr(name, x, n, shapes, dtype):
     return C.c_void_p(x.data_ptr())
 
 
-def shape_reward(cfg, params, states, actions, done, mem, reward, terms_out=None, ep_out=None, mask=None):
+def shape_reward(cfg, params, states, actions, done, mem, reward, terms_out=None, ep_out=None, mask=None, commands=None):
     """``solorl_shape_reward`` on the rows of ``states`` (a StateBatch on a GPU: the state AFTER the step): ``actions`` float32 [N, A] (the
     step's raw actions), ``done`` uint8 [N] or None, ``mem`` a ShapeMem (read and rewritten), ``reward`` float32 [N] or [N, 1] (added to in
     place) or None, ``terms_out`` float64 [N, 16] or None (raw term values), ``ep_out`` float64 [17, N] or None (finished episodes'
-    sums, accumulated), ``mask`` a [N] torch.bool / torch.uint8 tensor (rows whose byte is 0 are neither read nor written).  One launch
-    on the current stream, no host synchronisation: capturable."""
+    sums, accumulated), ``mask`` a [N] torch.bool / torch.uint8 tensor (rows whose byte is 0 are neither read nor written),
+    ``commands`` a command.CommandMem of N rows or None: with rows the two tracking terms of env i compare it against its own command
+    (``solorl_shape_reward_cmd``), without them against the one command of ``params``.  One launch on the current stream, no host
+    synchronisation: capturable."""
     if not isinstance(cfg, SoloConfig) or not isinstance(params, ShapeParams):
         raise AssertionError("cfg must be a SoloConfig and params a ShapeParams")
     if not isinstance(states, StateBatch) or not isinstance(mem, ShapeMem):
@@ -122,8 +124,14 @@ def shape_reward(cfg, params, states, actions, done, mem, reward, terms_out=None
     pt = _ptr("terms_out", terms_out, n, ((n, SHAPE_TERMS),), torch.float64)
     pe = _ptr("ep_out", ep_out, n, ((EP_FIELDS, n),), torch.float64)
     m, pm = mask_arg(mask, n, d.device)
+    args = (C.byref(cfg), C.byref(params), C.c_void_p(d.data_ptr()), pm, n, pa, pd, C.c_void_p(mem.data.data_ptr()), pr, pt, pe)
     with torch.cuda.device(d.device):
-        _native.check(_native.lib().solorl_shape_reward(C.byref(cfg), C.byref(params), C.c_void_p(d.data_ptr()), pm, n, pa, pd,
-                                                        C.c_void_p(mem.data.data_ptr()), pr, pt, pe, torch.cuda.current_device(),
-                                                        _native.stream(d.device)))
+        tail = (torch.cuda.current_device(), _native.stream(d.device))
+        if commands is None:
+            _native.check(_native.lib().solorl_shape_reward(*args, *tail))
+        else:
+            from .command import CommandMem
+            if not (isinstance(commands, CommandMem) and commands.data.device == d.device and commands.data.shape[0] == n):
+                raise AssertionError("commands must be a CommandMem of %d rows on %s" % (n, d.device))
+            _native.check(_native.lib().solorl_shape_reward_cmd(*args, C.c_void_p(commands.data.data_ptr()), *tail))
     return reward

@@ -22,6 +22,9 @@
   set_obs_noise(scales), set_actuation(delay, gain_range), last_applied_actions   (uniform sensor noise on every observation row the
       engine writes, and actuation latency with a per-joint motor gain error on every action row it reads, drawn on the device per env:
       include/solorl.h solorl_obs_noise / solorl_actuate, channel.py)
+  SoloVecEnv(..., commands=dict), set_command_ranges(**ranges), last_commands, engine_obs_dim   (per-env velocity commands drawn from
+      ranges and resampled on the device, appended to every observation row as three words and tracked by the shaped reward's two
+      tracking terms: include/solorl.h solorl_commands / solorl_shape_reward_cmd, command.py)
 
 torch is plumbing only: it owns the device buffers and the stream; all arithmetic happens in
 ``libsolorl_hip.so`` on the caller's current HIP stream (no host synchronisation in step()).
@@ -107,7 +110,7 @@ class SoloVecEnv:
     or a ``SoloConfig``."""
 
     def __init__(self, config, num_envs, device=None, seed=1, env_id_offset=0, applied_torque=False, norm_obs=False, norm_ret=False,
-                 clipob=10.0, cliprew=10.0, gamma=0.99, epsilon=1e-8, **overrides):
+                 clipob=10.0, cliprew=10.0, gamma=0.99, epsilon=1e-8, commands=None, **overrides):
         self.cfg = config.copy() if isinstance(config, SoloConfig) else config_from_dict(config, **overrides)
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
@@ -125,12 +128,24 @@ class SoloVecEnv:
         self._h = h
         o, a, n = C.c_int(), C.c_int(), C.c_int()
         _native.check(self.L.solorl_dims(self._h, C.byref(o), C.byref(a), C.byref(n)))
-        self.obs_dim, self.act_dim = o.value, a.value
+        # velocity commands (``commands``: a dict of ranges, command.KEYS): the observation is the engine's row plus three command words.
+        # The width is fixed here -- the normaliser below is sized by it and a policy is built from observation_space -- the ranges are
+        # not (set_command_ranges).  None: nothing is allocated or launched
+        self.engine_obs_dim, self.act_dim = o.value, a.value
+        self._cmd = self._cmd_mem = self._cmd_all = None
+        if commands is not None:
+            from .command import CommandMem, make_params, ranges_from_dict
+            self._cmd = make_params(seed, env_id_offset, self.engine_obs_dim, **ranges_from_dict(commands))
+            self._cmd_mem = CommandMem(self.nenvs, device)
+            self._cmd_all = torch.ones((self.nenvs,), dtype=torch.uint8, device=device)      # restart flags of reset()
+        self.obs_dim = self.engine_obs_dim + (0 if self._cmd is None else 3)
         self.observation_space = Box(-np.inf * np.ones(self.obs_dim), np.inf * np.ones(self.obs_dim))  # baseEnv.py:27-28
         self.action_space = Box(-np.ones(self.act_dim), np.ones(self.act_dim))                          # baseEnv.py:23-25
         N = self.nenvs
         kw = dict(device=device)
         self._obs = torch.empty((N, self.obs_dim), dtype=torch.float32, **kw)
+        # the rows the engine itself writes: with commands a narrow [N, D] buffer of their own, which solorl_commands widens into _obs
+        self._obs_engine = self._obs if self._cmd is None else torch.empty((N, self.engine_obs_dim), dtype=torch.float32, **kw)
         self._rew = torch.empty((N,), dtype=torch.float32, **kw)
         self._done = torch.empty((N,), dtype=torch.uint8, **kw)
         self._info = {k: torch.zeros((N,), dtype=(torch.uint8 if k in ("timeout", "success", "nan_reset") else
@@ -238,6 +253,9 @@ class SoloVecEnv:
         if self._noise_scale is not None:
             raise _native.SoloRLError("%s with observation noise set: the policy inside the step kernel would read clean observations "
                                       "(step_act_supported() / rollout_supported() are False)" % name)
+        if self._cmd is not None:
+            raise _native.SoloRLError("%s with velocity commands: the policy inside the step kernel would read the engine's rows without the "
+                                      "command words (step_act_supported() / rollout_supported() are False)" % name)
 
     def _stream(self):
         return _native.stream(self.device)
@@ -338,7 +356,7 @@ class SoloVecEnv:
             if self._tau is not None:                   # solorl_get_states leaves `tau` 0: the torques and power terms read the recorded torques
                 self._shape_states.tau[:, :self.act_dim].copy_(self._tau)
             shape_reward(self.cfg, self._shape_params, self._shape_states, actions, done, self._shape_mem, rew,
-                         terms_out=self.last_shaping_terms, ep_out=self._shape_ep)
+                         terms_out=self.last_shaping_terms, ep_out=self._shape_ep, commands=self._cmd_mem)
 
     def _no_shaping(self, name):
         if self._shape_params is not None:
@@ -383,8 +401,8 @@ class SoloVecEnv:
             v = scales_from_dict(self.cfg, scales) if "groups" in scales else noise_scales(self.cfg, scales)
         else:
             v = torch.as_tensor(scales, dtype=torch.float32).detach().reshape(-1)
-        if tuple(v.shape) != (self.obs_dim,) or not bool(torch.isfinite(v).all()) or bool((v < 0).any()):
-            raise AssertionError("observation noise scales must be %d finite values >= 0" % self.obs_dim)
+        if tuple(v.shape) != (self.engine_obs_dim,) or not bool(torch.isfinite(v).all()) or bool((v < 0).any()):
+            raise AssertionError("observation noise scales must be %d finite values >= 0" % self.engine_obs_dim)
         self._noise_scale = v.to(self.device).contiguous()
         if self._noise_count is None:
             self._noise_count = torch.zeros((self.nenvs,), dtype=torch.int32, device=self.device)
@@ -438,6 +456,43 @@ class SoloVecEnv:
         if self._act is not None:
             self._act_restart.copy_(done)
 
+    # ---- velocity commands (include/solorl.h solorl_commands; command.py)
+    @property
+    def last_commands(self):
+        """[N, 3] float64 view of the command rows: the command (vx, vy, yaw rate) every env holds now; None without commands"""
+        return None if self._cmd is None else self._cmd_mem.cmd
+
+    def set_command_ranges(self, **ranges):
+        """Changes what later draws use: ``lin_vel_x``, ``lin_vel_y``, ``yaw_rate`` ([lo, hi] pairs or fixed numbers), ``interval``,
+        ``zero_prob``, ``min_lin_norm``, ``obs_scale`` (command.KEYS); what is not named stays.  The parameters go to every launch by
+        value, so a command curriculum is a host loop around this call -- but a HIP graph captured earlier keeps the values it was
+        captured with.  Every env's countdown is set to 1 (one small fill on the device), so every env draws from the new ranges at its
+        next step: ``lo == hi`` with ``interval=1`` is joystick control, every env holding exactly that command after the next step.  The
+        width of the observation does not change."""
+        from .command import make_params, ranges_of
+        if self._cmd is None:
+            raise _native.SoloRLError("set_command_ranges() on an env made without commands (the observation width is fixed at construction: "
+                                      "SoloVecEnv(..., commands=dict))")
+        self._cmd = make_params(self._seed, self._id0, self.engine_obs_dim, **dict(ranges_of(self._cmd), **ranges))
+        self._cmd_mem.countdown.fill_(1)
+
+    def _commands(self, o, restart, mask=None):
+        """the command step of the engine's rows: the wide rows ``o`` [N, D + 3] = _obs_engine and each env's command words, the envs
+        of ``restart`` (and those whose countdown runs out) drawing a new command first"""
+        if self._cmd is not None:
+            from .command import commands
+            commands(self._cmd, self._cmd_mem, self._obs_engine, out=o, restart=restart, mask=mask)
+
+    def _command_words(self):
+        """[N, 3] float32: the observation words of the commands held now (torch ops: not on the hot path)"""
+        scale = torch.tensor(list(self._cmd.obs_scale), dtype=torch.float64, device=self.device)
+        return (self._cmd_mem.cmd * scale).to(torch.float32)
+
+    def _no_commands(self, name):
+        if self._cmd is not None:
+            raise _native.SoloRLError("%s with velocity commands: K steps in one launch cannot take the command launch between the steps "
+                                      "(rollout_supported() is False; step one at a time)" % name)
+
     def _no_channel(self, name):
         if self._noise_scale is not None or self._act is not None:
             raise _native.SoloRLError("%s with observation noise or actuation set: K steps in one launch cannot take their launches between "
@@ -446,10 +501,11 @@ class SoloVecEnv:
 
     def reset(self):
         with torch.cuda.device(self.device):
-            _native.check(self.L.solorl_reset(self._h, C.c_void_p(self._obs.data_ptr()), self._stream()))
+            _native.check(self.L.solorl_reset(self._h, C.c_void_p(self._obs_engine.data_ptr()), self._stream()))
         if self._act is not None:                       # every env starts an episode
             self._act_restart.fill_(1)
-        self._noise(self._obs)
+        self._noise(self._obs_engine)
+        self._commands(self._obs, self._cmd_all)        # every env draws a command
         if self._shape_mem is not None:                 # every env starts an episode
             self._shape_mem.data.zero_()
         if self._norm is not None:                      # running_mean_std.py:118-121
@@ -466,12 +522,13 @@ class SoloVecEnv:
         applied = self._actuate(a)
         self._kick()
         with torch.cuda.device(self.device):
-            _native.check(self.L.solorl_step(self._h, C.c_void_p(applied.data_ptr()), C.c_void_p(self._obs.data_ptr()),
+            _native.check(self.L.solorl_step(self._h, C.c_void_p(applied.data_ptr()), C.c_void_p(self._obs_engine.data_ptr()),
                                              C.c_void_p(self._rew.data_ptr()), C.c_void_p(self._done.data_ptr()),
                                              C.byref(self._info_c), self._stream()))
         self._restarts(self._done)
-        self._shape(a, self._rew, self._done)
-        self._noise(self._obs)
+        self._shape(a, self._rew, self._done)           # (with commands: against the command the policy acted on, before it is redrawn)
+        self._noise(self._obs_engine)
+        self._commands(self._obs, self._done)
         if self._norm is not None:
             self._normalize(self._obs, self._rew, self._done, 1)
         t = {k: v.clone() for k, v in self._info.items()}
@@ -500,18 +557,21 @@ class SoloVecEnv:
     def step_inplace(self, actions, obs_out=None, rew_out=None, done_out=None):
         """Zero-copy variant for rollout loops: returns views of the engine-owned output buffers (overwritten by the next
         step) -- or writes observations [N, O] / rewards [N] or [N, 1] / done flags (uint8 [N]) straight into caller-owned tensors
-        such as rollout-storage rows (the C ABI takes the caller's pointers anyway).  Host-side checks only, capturable in a HIP graph."""
+        such as rollout-storage rows (the C ABI takes the caller's pointers anyway).  Host-side checks only, capturable in a HIP graph.
+        With velocity commands O is the wide width: the engine writes its own narrow buffer and solorl_commands the caller's rows."""
         a = self._raw("actions", actions, (self.nenvs, self.act_dim))
         o, r, d, po, pr, pd = self._outputs((), (self._obs, self._rew, self._done), obs_out, rew_out, done_out)
+        e = o if self._cmd is None else self._obs_engine
         self._steps_issued += 1
         if self._act is not None:
             a = C.c_void_p(self._actuate(actions).data_ptr())
         self._kick()
         with torch.cuda.device(self.device):
-            _native.check(self.L.solorl_step(self._h, a, po, pr, pd, C.byref(self._info_c), self._stream()))
+            _native.check(self.L.solorl_step(self._h, a, C.c_void_p(e.data_ptr()), pr, pd, C.byref(self._info_c), self._stream()))
         self._restarts(d)
         self._shape(actions, r, d)
-        self._noise(o)
+        self._noise(e)
+        self._commands(o, d)
         if self._norm is not None:
             self._normalize(o, r, d, 1)
         return o, r, d, self._info
@@ -522,6 +582,7 @@ class SoloVecEnv:
         multiple of 4 floats and at most 88 (zero or one history level) with the reference's hidden-64 MLP on it."""
         return (not self._norm_obs                 # (the policy inside the step kernel would read the raw observations)
                 and self._noise_scale is None      # (... and the clean ones)
+                and self._cmd is None              # (... and rows without the command words)
                 and self.get_property("step_n_one_launch") == 1 and self.get_property("f64") == 0 and self.obs_dim % 4 == 0 and self.obs_dim <= 88
                 and params.obs_dim == self.obs_dim and params.act_dim == self.act_dim and params.hidden == 64)
 
@@ -589,6 +650,7 @@ class SoloVecEnv:
         self._no_kicks("step_n")
         self._no_shaping("step_n")
         self._no_channel("step_n")
+        self._no_commands("step_n")
         K = int(actions.shape[0]) if actions.dim() == 3 else 0
         if K < 1:
             raise AssertionError("actions must be [K, %d, %d] with K >= 1" % (self.nenvs, self.act_dim))
@@ -617,6 +679,7 @@ class SoloVecEnv:
         self._no_kicks("rollout_inplace")
         self._no_shaping("rollout_inplace")
         self._no_channel("rollout_inplace")
+        self._no_commands("rollout_inplace")
         pal = 1 if policy_after_last else 0
         R = int(actions.shape[0]) if actions.dim() == 3 else 0
         K = R - pal
@@ -635,8 +698,11 @@ class SoloVecEnv:
         return o, r, d, b["info"]
 
     def get_observation(self):
+        """The clean observation rows; with velocity commands the current command words are appended (by torch ops)"""
         with torch.cuda.device(self.device):
-            _native.check(self.L.solorl_get_observation(self._h, C.c_void_p(self._obs.data_ptr()), self._stream()))
+            _native.check(self.L.solorl_get_observation(self._h, C.c_void_p(self._obs_engine.data_ptr()), self._stream()))
+        if self._cmd is not None:
+            return torch.cat([self._obs_engine, self._command_words()], dim=1)
         return self._obs.clone()
 
     def episode_stat_sums(self, reset=True):
@@ -760,11 +826,14 @@ class SoloVecEnv:
         if m is None:
             raise AssertionError("reset_masked needs a mask (reset() resets every env)")
         with torch.cuda.device(self.device):
-            _native.check(self.L.solorl_get_observation(self._h, C.c_void_p(self._obs.data_ptr()), self._stream()))
-            _native.check(self.L.solorl_reset_masked(self._h, pm, C.c_void_p(self._obs.data_ptr()), self._stream()))
+            _native.check(self.L.solorl_get_observation(self._h, C.c_void_p(self._obs_engine.data_ptr()), self._stream()))
+            _native.check(self.L.solorl_reset_masked(self._h, pm, C.c_void_p(self._obs_engine.data_ptr()), self._stream()))
         if self._act is not None:                       # the selected envs start an episode with their next action
             self._act_restart.bitwise_or_(m.ne(0).to(torch.uint8))
-        self._noise(self._obs, m)                       # the rows the engine has just written: the selected ones
+        if self._cmd is not None:                       # every row with the command it holds; the selected ones are rewritten below
+            self._obs.copy_(torch.cat([self._obs_engine, self._command_words()], dim=1))
+        self._noise(self._obs_engine, m)                # the rows the engine has just written: the selected ones
+        self._commands(self._obs, m, mask=m)            # the selected envs draw a command; no other row is touched
         if self._shape_mem is not None:                 # the selected envs start an episode (its sums so far are dropped, not counted)
             self._shape_mem.data.masked_fill_(m.bool().unsqueeze(-1), 0.0)
         if self._norm is not None:
@@ -805,7 +874,7 @@ class SoloVecEnv:
 def make_vec_envs(config, num_envs, env_constructor=None, gamma=0.99, device=None, training=True, seed=1,
                   env_id_offset=0, norm_obs=False, norm_ret=False, clipob=10., cliprew=10., epsilon=1e-8,
                   push_interval=None, push_max_vel=0.0, push_max_yaw_rate=0.0, reward_shaping=None,
-                  obs_noise=None, action_delay=None, motor_gain_range=0.0):
+                  obs_noise=None, action_delay=None, motor_gain_range=0.0, commands=None):
     """Signature of agents/ppo/envs.py:14.  ``env_constructor`` (the per-process gym env class of the
     reference) is accepted for call-site compatibility and ignored.  ``norm_obs`` / ``norm_ret`` are VecNormalize's ``ob`` /
     ``ret`` (agents/running_mean_std.py:79; the reference's launcher passes False, False, and so do the defaults here) with its
@@ -820,9 +889,12 @@ def make_vec_envs(config, num_envs, env_constructor=None, gamma=0.99, device=Non
     configs/noise_solo.yaml holds it, or an [obs_dim] vector; None = clean observations): uniform sensor noise on every observation
     (SoloVecEnv.set_obs_noise).  ``action_delay`` (an int or a (lo, hi) pair of control steps within 0..4; None = none) and
     ``motor_gain_range`` (each joint's action is scaled by 1 + U(-g, g), drawn per env and episode; 0 = exact): actuation latency and
-    motor gain error in front of every step (SoloVecEnv.set_actuation).  Off, nothing is allocated or launched."""
+    motor gain error in front of every step (SoloVecEnv.set_actuation).  Off, nothing is allocated or launched.
+    ``commands`` (a dict with ``lin_vel_x``, ``lin_vel_y``, ``yaw_rate`` as [lo, hi] pairs, ``interval``, ``zero_prob``, ``min_lin_norm``,
+    ``obs_scale``, as configs/commands_walk12.yaml holds it; None = no commands, and nothing is allocated or launched): per-env velocity
+    commands, three more observation words, and the tracking terms of ``reward_shaping`` against each env's own command."""
     envs = SoloVecEnv(config, num_envs, device=device, seed=seed, env_id_offset=env_id_offset, norm_obs=norm_obs, norm_ret=norm_ret,
-                      clipob=clipob, cliprew=cliprew, gamma=gamma, epsilon=epsilon)
+                      clipob=clipob, cliprew=cliprew, gamma=gamma, epsilon=epsilon, commands=commands)
     if push_interval is not None:
         envs.set_perturbation(push_interval, (push_max_vel, push_max_vel, 0.0), (0.0, 0.0, push_max_yaw_rate))
     if reward_shaping is not None:

@@ -44,7 +44,11 @@ def motor_gain_range(text):
 
 
 def add_channel_flags(p):
-    """the three flags train_ppo.py and eval_ppo.py share"""
+    """the flags train_ppo.py and eval_ppo.py share"""
+    p.add_argument("--commands", type=str, default=None, metavar="FILE.yaml",
+                   help="per-env velocity commands: ranges of lin_vel_x, lin_vel_y and yaw_rate, `interval`, `zero_prob`, `min_lin_norm`, "
+                        "`obs_scale`, e.g. configs/commands_walk12.yaml; the observation gains three words and the tracking terms of "
+                        "--reward-shaping follow each env's own command (default: no commands)")
     p.add_argument("--obs-noise", type=str, default=None, metavar="FILE.yaml",
                    help="uniform sensor noise on every observation: `groups:` (observation group -> half-width in physical units) and "
                         "`history:`, e.g. configs/noise_solo.yaml (default: clean observations)")
@@ -64,6 +68,16 @@ def load_obs_noise(path, config):
     except (ValueError, AttributeError, TypeError) as e:
         raise SystemExit("--obs-noise %s: %s" % (path, e))
     return noise
+
+
+def load_commands(path):
+    """--commands FILE.yaml -> its dict, with unknown keys and bad values refused by name before anything is built"""
+    from solorl_amd.command import ranges_from_dict
+    from solorl_amd.config import load_yaml
+    try:
+        return ranges_from_dict(load_yaml(path))
+    except (ValueError, AttributeError, TypeError) as e:
+        raise SystemExit("--commands %s: %s" % (path, e))
 
 
 def get_ppo_args(argv=None):
@@ -136,6 +150,8 @@ def main(argv=None):
         args.reward_shaping = shaping
     if args.obs_noise is not None:
         args.obs_noise = load_obs_noise(args.obs_noise, config)
+    if args.commands is not None:
+        args.commands = load_commands(args.commands)
     writer = None
     rank = int(os.environ.get("RANK", "0"))
     if args.logdir is not None:      # run directory named as training/train_ppo.py:64-72
