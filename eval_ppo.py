@@ -12,7 +12,9 @@ ratio of the summed normal forces to the robot's weight; --dump then also holds 
 and motor gain error (SoloVecEnv.set_obs_noise / set_actuation).
 --commands FILE.yaml (train_ppo.py's flag) evaluates a policy trained with per-env velocity commands under commands drawn from the file's
 ranges; --command VX VY WZ gives every env that one command for the whole run (joystick control).  With either, the summary adds the
-mean absolute tracking error of the base-frame velocity xy [m/s] and of the base-frame yaw rate [rad/s] over all envs and steps."""
+mean absolute tracking error of the base-frame velocity xy [m/s] and of the base-frame yaw rate [rad/s] over all envs and steps.
+--termination FILE.yaml (train_ppo.py's flag) evaluates under early termination rules (SoloVecEnv.set_termination); the summary adds the
+share of the finished episodes that each rule ended."""
 import argparse
 import os
 import sys
@@ -82,7 +84,7 @@ def main(argv=None):
     p.add_argument("--max-steps", type=int, default=0, help="stop after K control steps even if fewer than --num-runs episodes have ended (0 = no limit)")
     p.add_argument("--push-interval", type=int, default=0, help="kick every env's base velocity every K control steps (0 = never)")
     p.add_argument("--push-max-vel", type=float, default=0.0, help="a kick's x and y velocity change is uniform in +-V m/s")
-    from train_ppo import add_channel_flags, load_commands, load_obs_noise
+    from train_ppo import add_channel_flags, load_commands, load_obs_noise, load_termination
     add_channel_flags(p)
     p.add_argument("--command", type=float, nargs=3, default=None, metavar=("VX", "VY", "WZ"),
                    help="one fixed velocity command for every env: vx vy [m/s, base frame] and yaw rate [rad/s]; with --commands it keeps "
@@ -110,7 +112,8 @@ def main(argv=None):
                         interval=1, zero_prob=0.0, min_lin_norm=0.0)
     env = make_vec_envs(config, a.num_agents, None, device=dev, training=False, seed=a.seed, norm_obs=ob_rms is not None,
                         obs_noise=None if a.obs_noise is None else load_obs_noise(a.obs_noise, config), action_delay=a.action_delay,
-                        motor_gain_range=a.motor_gain_range, commands=commands)
+                        motor_gain_range=a.motor_gain_range, commands=commands,
+                        termination=None if a.termination is None else load_termination(a.termination, config))
     width = ckpt["state_dict"]["base.features.0.weight"].shape[1]
     if width != env.obs_dim:
         raise SystemExit("the checkpoint's policy reads %d observation words, this run's observation has %d (%d of the engine%s): "
@@ -181,6 +184,11 @@ def main(argv=None):
         e = (track / max(track_n, 1.0)).tolist()
         print("command tracking over {:.0f} env steps: mean |v_b.xy - cmd.xy| {:.4f} m/s  mean |w_b.z - cmd.z| {:.4f} rad/s".format(track_n, e[0], e[1]))
         result["tracking_error_lin_vel"], result["tracking_error_yaw_rate"] = e
+    if a.termination is not None:
+        ts = env.termination_stats()
+        print("early termination over {} finished episodes: {}".format(ts["term/episodes"], "  ".join(
+            "{} {:.3f}".format(k[5:], v) for k, v in ts.items() if k != "term/episodes")))
+        result["termination"] = ts
     if gait is not None:
         result["gait"] = gait.report()
     if a.dump:

@@ -54,6 +54,10 @@
  *   solorl_commands / solorl_shape_reward_cmd : per-env velocity commands (no reference counterpart): drawn from ranges and resampled on
  *                             the device from a Philox stream per env, appended to the observation rows as three words, one launch,
  *                             handle-free; and the shaped reward's two tracking terms against each env's own command
+ *   solorl_terminate       <- no reference counterpart (the reference ends an episode at the time limit, at a reached goal and at
+ *                             pos.z < 0.05 only: baseEnv.py:162-180): early termination rules -- base height, tilt, contact of chosen
+ *                             primitives, joint limits -- on a whole batch of state rows after a step, one launch, handle-free; it
+ *                             sets done, the terminal reward and the episode statistics and leaves a mask for solorl_reset_masked
  *   solorl_destroy         <- agents/ppo/envs.py:129-135 (close)
  *
  * Plain pointers and sizes only; no torch types.  All array arguments are DEVICE pointers
@@ -558,6 +562,61 @@ int solorl_shape_reward_cmd(const solorl_config* cfg, const solorl_shape_params*
                             const uint8_t* done, solorl_env_shape* mem, float* reward, double* terms_out,
                             double* ep_out, const solorl_env_command* cmd /* [n] rows or NULL */,
                             int device_id, void* stream);
+
+/* Early termination (no reference counterpart; the "base contact", "orientation" and "dof limit" terminations of legged_gym-style tasks).
+ * The engine ends an episode at the time limit, at a reached goal and at pos.z < 0.05; a robot on its knees, on its side or on its back
+ * stays alive.  A fourth handle-free row query beside solorl_kinematics, solorl_dynamics and solorl_shape_reward: a pure function of its
+ * arguments, ONE kernel launch on `stream`, no allocation, no host synchronisation (capturable).  A caller issues it after a step, on the
+ * state AFTER that step (solorl_get_states), with the done flags, the reward and the info block of that step, and then hands fired_out to
+ * solorl_reset_masked as its mask:   step -> solorl_get_states -> solorl_terminate -> solorl_reset_masked(fired_out, obs rows).
+ * The step kernels know nothing of it.
+ * Rules (all arithmetic fp64, every product and sum rounded on its own, no fused multiply-add: every flag is specified to the bit; a
+ * rule fires only on a FINITE tested value, so NaN and +-Inf members fire nothing -- non-finite states belong to the engine's own guard):
+ *   HEIGHT   z = pos[2]:  z finite and z < min_height
+ *   TILT     up_z = 1 - 2 (qx qx + qy qy) on the quaternion as it is in the row (the z component of the base's z axis, = cos of its
+ *            angle to world z for a unit quaternion):  up_z finite and up_z < min_up_z
+ *   CONTACT  some primitive p of contact_prims that the robot has (0..19 Solo8, 0..23 Solo12) has its contact_mask bit set and
+ *            f = lambda_prev[p] / sim_dt (solorl_env_kin.prim_force) finite and f >= contact_force_min
+ *   JOINT    some joint j < act_dim has q[j] finite and (q[j] < joint_lo[j] or q[j] > joint_hi[j])
+ *   No rule fires on a row whose timestep < min_steps.
+ * Rows:
+ *   live, done[i] != 0 on entry     the engine ended and reset it, the row holds the new episode: fired_out[i] = 0, nothing else is written
+ *   live, done[i] == 0, none fires  fired_out[i] = 0, nothing else is written
+ *   live, done[i] == 0, some fire   fired_out[i] = all the bits that fire; done[i] = 1; reward[i] = (float)terminal_reward (an override,
+ *                                   as the engine's own -10 is); the info and term_stats writes below
+ *   masked (mask byte 0)            nothing of the row is read or written, in any array (a caller that uses fired_out as a mask zeroes
+ *                                   it first)
+ * Info writes of a row where a rule fires, what the engine writes when its own fall rule ends an episode (each member may be NULL):
+ *   timeout[i] = 0, success[i] = 0, episode_reward[i] = reward[i];  the ep_stats column: [0] += 1, [1] += reward, [2] += (float)timestep,
+ *   [3] += 0, [4 + k] += (float)dr[k];  the other info fields already hold this step's values.
+ *   term_stats ([1 + SOLORL_TERM_RULES][n] floats, field-major, or NULL): [0][i] += 1 and [1 + k][i] += 1 for every rule bit k that fired
+ *   -- the contract of ep_stats: one column per env, no atomics, the caller reduces and zeroes.
+ * A function of the rows, *p and cfg's robot and sim_dt only.
+ * Null cfg, p, states, done, reward or fired_out, n < 1, a robot that is neither SOLORL_ROBOT_*, sim_dt <= 0 (or non-finite), rules == 0 or
+ * bits outside the four, min_steps < 0, a non-finite threshold of an enabled rule (joint limits: of the joints j < act_dim),
+ * contact_force_min < 0, joint_lo[j] > joint_hi[j] for a j < act_dim, a non-finite terminal_reward, contact_prims naming primitives the
+ * robot does not have while CONTACT is enabled: SOLORL_ERR_INVALID, the message starts with "solorl_terminate:" (checked before any HIP
+ * call). */
+#define SOLORL_TERM_RULES 4
+enum { SOLORL_TERM_HEIGHT = 1, SOLORL_TERM_TILT = 2, SOLORL_TERM_CONTACT = 4, SOLORL_TERM_JOINT = 8 };
+typedef struct solorl_termination {
+  uint32_t rules;            /* bit set of the enabled rules; 0 is refused */
+  int32_t  min_steps;        /* >= 0: no rule fires on a row whose timestep < min_steps */
+  uint32_t contact_prims;    /* bit p (0..23): primitive p counts for the contact rule */
+  int32_t  reserved;
+  double   min_height;       /* HEIGHT:  pos.z < min_height */
+  double   min_up_z;         /* TILT:    up_z < min_up_z (cos of the largest allowed angle between the base's z axis and world z) */
+  double   contact_force_min;/* CONTACT: some p in contact_prims has its contact_mask bit set and lambda_prev[p] / sim_dt >= contact_force_min (>= 0) */
+  double   joint_lo[12], joint_hi[12];   /* JOINT: some j < act_dim has q[j] < joint_lo[j] or q[j] > joint_hi[j] */
+  double   terminal_reward;  /* the reward a terminated row receives (an override, as the engine's own -10 is) */
+} solorl_termination;
+int solorl_terminate(const solorl_config* cfg, const solorl_termination* p,
+                     const solorl_env_state* states /* [n] DEVICE rows, the state AFTER the step */,
+                     const uint8_t* mask /* [n] or NULL */, int n,
+                     uint8_t* done /* [n] in/out */, float* reward /* [n] in/out */,
+                     uint8_t* fired_out /* [n]: the rule bits that fired, 0 where none */,
+                     const solorl_info_soa* info /* or NULL; arrays of n elements, ep_stats [FIELDS][n] */,
+                     float* term_stats /* [1 + SOLORL_TERM_RULES][n] or NULL */, int device_id, void* stream);
 
 /* Fused return computation over a rollout of T steps x N envs (device arrays, time-major [t][n]).
  * use_gae != 0:  value_preds[T][:] = next_value;  delta_t = r_t + gamma V_{t+1} m_{t+1} - V_t;

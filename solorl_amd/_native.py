@@ -20,7 +20,8 @@ SYMBOLS = ("solorl_default_config", "solorl_create", "solorl_destroy", "solorl_d
            "solorl_get_states", "solorl_set_states", "solorl_reset_masked",
            "solorl_set_perturbation", "solorl_perturb", "solorl_get_perturbation",
            "solorl_norm_scratch_count", "solorl_normalize_obs", "solorl_normalize_rewards", "solorl_kinematics", "solorl_dynamics",
-           "solorl_shape_reward", "solorl_obs_noise", "solorl_actuate", "solorl_commands", "solorl_shape_reward_cmd")
+           "solorl_shape_reward", "solorl_obs_noise", "solorl_actuate", "solorl_commands", "solorl_shape_reward_cmd",
+           "solorl_terminate")
 
 
 class PolicyParams(C.Structure):            # solorl_policy_params
@@ -75,6 +76,15 @@ class CommandParams(C.Structure):           # solorl_command_params
 
 class EnvCommand(C.Structure):              # solorl_env_command
     _fields_ = [("cmd", C.c_double * 3), ("countdown", C.c_int32), ("draws", C.c_uint32)]
+
+
+TERM_RULES = 4                              # SOLORL_TERM_RULES
+
+
+class Termination(C.Structure):             # solorl_termination
+    _fields_ = [("rules", C.c_uint32), ("min_steps", C.c_int32), ("contact_prims", C.c_uint32), ("reserved", C.c_int32), ("min_height", C.c_double),
+                ("min_up_z", C.c_double), ("contact_force_min", C.c_double), ("joint_lo", C.c_double * 12), ("joint_hi", C.c_double * 12),
+                ("terminal_reward", C.c_double)]
 
 
 class SoloRLError(RuntimeError):
@@ -156,6 +166,10 @@ def lib():
                                       C.c_int, C.c_void_p]
         L.solorl_shape_reward_cmd.argtypes = L.solorl_shape_reward.argtypes[:11] + [C.c_void_p, C.c_int, C.c_void_p]
         L.solorl_commands.restype = L.solorl_shape_reward_cmd.restype = C.c_int
+        # early termination (termination.py): handle-free; cfg, params and the info block are host structs, every array a device pointer
+        L.solorl_terminate.argtypes = [C.POINTER(SoloConfig), C.POINTER(Termination), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.POINTER(InfoSoA), C.c_void_p, C.c_int, C.c_void_p]
+        L.solorl_terminate.restype = C.c_int
         for s in SYMBOLS:
             getattr(L, s)
         # the ctypes mirrors in config.py / this file are written against one layout of include/solorl.h's structs

@@ -25,6 +25,11 @@ Differences that come with the GPU engine (documented, not behavioural):
     its own, drawn and resampled on the device behind every step launch of the eager and of the captured rollout alike
     (SoloVecEnv(commands=)): the observation and the policy are three words wider, and the tracking terms of args.reward_shaping compare
     each env against its own command.  The policy cannot run inside the step kernel either (it would not see the command words);
+  * args.termination (train_ppo.py --termination FILE.yaml: a dict of rules; no reference counterpart) ends an episode early when the
+    state after a step breaks a rule -- base height, tilt, contact of chosen primitives, joint limits -- by one launch behind every
+    step launch of the eager and of the captured rollout alike (SoloVecEnv.set_termination), the envs it ends reset on the device; the
+    share of the finished episodes each rule ended is logged as term/<rule> beside dr/* and sr/*.  The policy cannot run inside the step
+    kernel (it would act on the observation of an env that is about to be reset): the rollout takes two launches per step;
   * multi-GPU: one process per GPU (`python -m torch.distributed.run --nproc-per-node W ...`), envs
     sharded by rank (global env id = rank*N + i), flat-bucket RCCL gradient all-reduce (ppo.py).
 """
@@ -98,8 +103,9 @@ def train(args, config, env_constructor=None, writer=None):
                          push_max_vel=getattr(args, "push_max_vel", 0.0), push_max_yaw_rate=getattr(args, "push_max_yaw_rate", 0.0),
                          reward_shaping=getattr(args, "reward_shaping", None), obs_noise=getattr(args, "obs_noise", None),
                          action_delay=getattr(args, "action_delay", None), motor_gain_range=getattr(args, "motor_gain_range", 0.0),
-                         commands=getattr(args, "commands", None))
+                         commands=getattr(args, "commands", None), termination=getattr(args, "termination", None))
     shaping = getattr(args, "reward_shaping", None) is not None
+    termination = getattr(args, "termination", None) is not None
     action_dim = envs.action_space.shape[0]
     base = torch.load(args.base_checkpoint) if getattr(args, "base_checkpoint", None) else None
     actor_critic = Policy(envs.observation_space.shape, envs.action_space, base, {"hidden_size": args.hidden_size}).to(device)
@@ -150,6 +156,8 @@ def train(args, config, env_constructor=None, writer=None):
                        episodes=es["episodes"], **{k: v for k, v in es.items() if k.startswith("dr/")})
             if shaping:                               # this rank's finished episodes: each shaped term's weighted sum per episode
                 rec.update({k: v for k, v in envs.shaping_stats(reset=True).items() if k.startswith("sr/")})
+            if termination:                           # this rank's finished episodes: the share each rule ended
+                rec.update(envs.termination_stats(reset=True))
             history.append(rec)
             if rank == 0:
                 print("Updates {update}, num timesteps {timesteps}, FPS {fps}\n mean reward {ep_reward:.2f} mean length "
@@ -159,6 +167,6 @@ def train(args, config, env_constructor=None, writer=None):
                     for k in ("value_loss", "action_loss", "entropy", "ep_reward", "ep_length", "success"):
                         writer.add_scalar(k, rec[k], total)
                     for k in rec:
-                        if k.startswith("dr/") or k.startswith("sr/"):   # agents/ppo/train.py:98-100, utils.log of the dr/ deques; sr/: shaped terms
+                        if k.startswith(("dr/", "sr/", "term/")):   # agents/ppo/train.py:98-100, utils.log of the dr/ deques; sr/: shaped terms; term/: early terminations
                             writer.add_scalar(k, rec[k], total)
     return actor_critic, history

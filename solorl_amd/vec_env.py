@@ -25,6 +25,9 @@
   SoloVecEnv(..., commands=dict), set_command_ranges(**ranges), last_commands, engine_obs_dim   (per-env velocity commands drawn from
       ranges and resampled on the device, appended to every observation row as three words and tracked by the shaped reward's two
       tracking terms: include/solorl.h solorl_commands / solorl_shape_reward_cmd, command.py)
+  set_termination(**rules), last_termination, termination_stats()   (early termination rules -- base height, tilt, contact of chosen
+      primitives, joint limits -- checked on the state after every step by one launch, the envs they end reset on the device:
+      include/solorl.h solorl_terminate, termination.py)
 
 torch is plumbing only: it owns the device buffers and the stream; all arithmetic happens in
 ``libsolorl_hip.so`` on the caller's current HIP stream (no host synchronisation in step()).
@@ -177,6 +180,12 @@ class SoloVecEnv:
         self._act_mem = None        # ActuatorMem: the per-env delay line, gains and latency
         self._act_restart = None    # [N] uint8: the envs whose next action is the first of an episode
         self.last_applied_actions = None   # [N, A] float32: what the last step launch received for the caller's raw actions
+        # early termination (set_termination): nothing is allocated or launched unless it is set
+        self._term = None           # Termination; None = early termination off
+        self._term_states = None    # engine-owned StateBatch the state after each step is read into (shared with the shaped terms)
+        self._term_stats = None     # [5, N] float32: early terminations and the rules that fired in them, per env
+        self._term_eps = None       # [2] float64: finished episodes already flushed out of ep_stats, and the ep_stats count they start from
+        self.last_termination = None   # [N] uint8: the rule bits that ended each env's episode in the last step, 0 where none
         self._info_c = InfoSoA(ep_stats=self._ep_stats.data_ptr(), applied_torque=None if self._tau is None else self._tau.data_ptr(),
                                **{k: self._info[k].data_ptr() for k in _INFO_KEYS})
         # VecNormalize (agents/running_mean_std.py:73-127; the reference's launcher passes ob=False, ret=False: agents/ppo/envs.py:26):
@@ -256,6 +265,9 @@ class SoloVecEnv:
         if self._cmd is not None:
             raise _native.SoloRLError("%s with velocity commands: the policy inside the step kernel would read the engine's rows without the "
                                       "command words (step_act_supported() / rollout_supported() are False)" % name)
+        if self._term is not None:
+            raise _native.SoloRLError("%s with a termination set: the policy inside the step kernel would act on the observation of an env "
+                                      "that is about to be reset (step_act_supported() / rollout_supported() are False)" % name)
 
     def _stream(self):
         return _native.stream(self.device)
@@ -348,14 +360,16 @@ class SoloVecEnv:
                 t.zero_()
         self._shape_params = p
 
-    def _shape(self, actions, rew, done):
-        """the shaped terms of a control step, behind its step launch: the state after the step, then one launch"""
+    def _shape(self, actions, rew, done, rows=None):
+        """the shaped terms of a control step, behind its step launch: the state after the step (``rows``: the rows _terminate has
+        already read, taken before its reset), then one launch"""
         if self._shape_params is not None:
             from .shaping import shape_reward
-            self.get_states(out=self._shape_states)
+            if rows is None:
+                rows = self.get_states(out=self._shape_states)
             if self._tau is not None:                   # solorl_get_states leaves `tau` 0: the torques and power terms read the recorded torques
-                self._shape_states.tau[:, :self.act_dim].copy_(self._tau)
-            shape_reward(self.cfg, self._shape_params, self._shape_states, actions, done, self._shape_mem, rew,
+                rows.tau[:, :self.act_dim].copy_(self._tau)
+            shape_reward(self.cfg, self._shape_params, rows, actions, done, self._shape_mem, rew,
                          terms_out=self.last_shaping_terms, ep_out=self._shape_ep, commands=self._cmd_mem)
 
     def _no_shaping(self, name):
@@ -378,6 +392,77 @@ class SoloVecEnv:
         out = {"episodes": int(n)}
         for k, name in enumerate(TERMS):
             out["sr/" + name] = (tot[1 + k] / n) if n > 0 else float("nan")
+        return out
+
+    # ---- early termination (include/solorl.h solorl_terminate; termination.py)
+    def set_termination(self, rules=None, **more):
+        """Ends an episode early when the state after a step breaks a rule: ``base_height`` [m], ``max_tilt_deg``, ``contacts`` (group
+        names ``base``, ``knees``, ``shoulders`` or primitive indices) with ``contact_force_min`` [N], ``joint_limits`` ([lo, hi], or one
+        pair per joint), and ``min_steps``, ``terminal_reward`` (default -10) -- termination.make_termination; a rule is enabled by
+        naming its key, as keywords or as one dict.  ``set_termination(None)`` switches it off.  Allocates ``last_termination`` (uint8 [N]:
+        the rule bits that ended each env's episode in the last step), the statistics block and an engine-owned StateBatch at the first
+        call and clears them at every call; call it before capturing a HIP graph of steps (the rules are launch arguments).
+
+        While set, step() and step_inplace() issue, right behind their step launch and on the same stream: get_states (one launch,
+        shared with the shaped reward terms when those are set), ONE solorl_terminate launch on the step's done flags, reward and info
+        arrays, and solorl_reset_masked(last_termination) into the observation rows the engine has just written.  Everything behind it
+        sees the merged done flags: the shaped terms (on the rows taken before the reset: they leave the terminal reward alone and flush
+        their episode sums), actuation and commands (the env restarts its episode), return normalisation (a new return starts).  The
+        policy inside the step kernel would act on the observation of an env that is about to be reset, so step_act_supported() and
+        rollout_supported() are False, step_act_inplace() raises, and so do step_n*, rollout_inplace (K steps in one launch)."""
+        from .termination import STAT_FIELDS, make_termination
+        if rules is None and not more:
+            self._term = self._term_states = self._term_stats = self._term_eps = self.last_termination = None
+            return
+        p = make_termination(self.cfg, **dict(rules or {}, **more))
+        if self._term_states is None:
+            self._term_states = StateBatch(self.nenvs, self.device)
+            self._term_stats = torch.zeros((STAT_FIELDS, self.nenvs), dtype=torch.float32, device=self.device)
+            self._term_eps = torch.zeros((2,), dtype=torch.float64, device=self.device)
+            self.last_termination = torch.zeros((self.nenvs,), dtype=torch.uint8, device=self.device)
+        else:
+            for t in (self._term_stats, self._term_eps, self.last_termination):
+                t.zero_()
+        self._term_eps[1] = self._ep_stats[0].sum(dtype=torch.float64)      # episodes finished before now are not this termination's
+        self._term = p
+
+    def _terminate(self, e, rew, done):
+        """the early termination of a control step, behind its step launch: the state after the step, one launch on the step's
+        outputs, and the reset of the envs it ended into the engine's observation rows ``e`` -> the rows (pre-reset) or None"""
+        if self._term is None:
+            return None
+        from .termination import terminate
+        rows = self.get_states(out=self._term_states)
+        terminate(self.cfg, self._term, rows, done, rew, self.last_termination, info=self._info_c, term_stats=self._term_stats)
+        with torch.cuda.device(self.device):
+            _native.check(self.L.solorl_reset_masked(self._h, C.c_void_p(self.last_termination.data_ptr()), C.c_void_p(e.data_ptr()), self._stream()))
+        return rows
+
+    def _no_termination(self, name):
+        if self._term is not None:
+            raise _native.SoloRLError("%s with a termination set: K steps in one launch cannot take the termination launch between the steps "
+                                      "(rollout_supported() is False; step one at a time, or set_termination(None))" % name)
+
+    def termination_stats(self, reset=True):
+        """``term/episodes``: the episodes finished since the last call, by any cause; ``term/early``: the share of them that a rule
+        ended, and ``term/<rule>`` (height, tilt, contact, joint; the enabled ones): the share each rule ended -- an episode that
+        several rules ended at once counts for each.  Reduced on the device from the per-env counts solorl_terminate keeps and the
+        engine's finished-episode count; one small device->host copy.  ``reset`` starts the next window."""
+        from .termination import RULES
+        if self._term is None:
+            raise _native.SoloRLError("termination_stats() without a termination set")
+        cur = self._ep_stats[0].sum(dtype=torch.float64)
+        tot = torch.cat([self._term_stats.sum(dim=1, dtype=torch.float64), (self._term_eps[0] + cur - self._term_eps[1]).reshape(1)])
+        if reset:
+            self._term_stats.zero_()
+            self._term_eps[0] = 0.0
+            self._term_eps[1] = cur
+        tot = tot.tolist()
+        n = tot[-1]
+        out = {"term/episodes": int(n), "term/early": (tot[0] / n) if n > 0 else float("nan")}
+        for k, name in enumerate(RULES):
+            if (self._term.rules >> k) & 1:
+                out["term/" + name] = (tot[1 + k] / n) if n > 0 else float("nan")
         return out
 
     # ---- observation noise and actuation (include/solorl.h solorl_obs_noise / solorl_actuate; channel.py)
@@ -508,6 +593,8 @@ class SoloVecEnv:
         self._commands(self._obs, self._cmd_all)        # every env draws a command
         if self._shape_mem is not None:                 # every env starts an episode
             self._shape_mem.data.zero_()
+        if self.last_termination is not None:
+            self.last_termination.zero_()
         if self._norm is not None:                      # running_mean_std.py:118-121
             self._norm.ret.zero_()
             if self._norm_obs:
@@ -525,8 +612,9 @@ class SoloVecEnv:
             _native.check(self.L.solorl_step(self._h, C.c_void_p(applied.data_ptr()), C.c_void_p(self._obs_engine.data_ptr()),
                                              C.c_void_p(self._rew.data_ptr()), C.c_void_p(self._done.data_ptr()),
                                              C.byref(self._info_c), self._stream()))
+        rows = self._terminate(self._obs_engine, self._rew, self._done)
         self._restarts(self._done)
-        self._shape(a, self._rew, self._done)           # (with commands: against the command the policy acted on, before it is redrawn)
+        self._shape(a, self._rew, self._done, rows)     # (with commands: against the command the policy acted on, before it is redrawn)
         self._noise(self._obs_engine)
         self._commands(self._obs, self._done)
         if self._norm is not None:
@@ -568,8 +656,9 @@ class SoloVecEnv:
         self._kick()
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_step(self._h, a, C.c_void_p(e.data_ptr()), pr, pd, C.byref(self._info_c), self._stream()))
+        rows = self._terminate(e, r, d)
         self._restarts(d)
-        self._shape(actions, r, d)
+        self._shape(actions, r, d, rows)
         self._noise(e)
         self._commands(o, d)
         if self._norm is not None:
@@ -583,6 +672,7 @@ class SoloVecEnv:
         return (not self._norm_obs                 # (the policy inside the step kernel would read the raw observations)
                 and self._noise_scale is None      # (... and the clean ones)
                 and self._cmd is None              # (... and rows without the command words)
+                and self._term is None             # (... and act on the observation of an env that is about to be reset)
                 and self.get_property("step_n_one_launch") == 1 and self.get_property("f64") == 0 and self.obs_dim % 4 == 0 and self.obs_dim <= 88
                 and params.obs_dim == self.obs_dim and params.act_dim == self.act_dim and params.hidden == 64)
 
@@ -651,6 +741,7 @@ class SoloVecEnv:
         self._no_shaping("step_n")
         self._no_channel("step_n")
         self._no_commands("step_n")
+        self._no_termination("step_n")
         K = int(actions.shape[0]) if actions.dim() == 3 else 0
         if K < 1:
             raise AssertionError("actions must be [K, %d, %d] with K >= 1" % (self.nenvs, self.act_dim))
@@ -680,6 +771,7 @@ class SoloVecEnv:
         self._no_shaping("rollout_inplace")
         self._no_channel("rollout_inplace")
         self._no_commands("rollout_inplace")
+        self._no_termination("rollout_inplace")
         pal = 1 if policy_after_last else 0
         R = int(actions.shape[0]) if actions.dim() == 3 else 0
         K = R - pal
@@ -710,6 +802,9 @@ class SoloVecEnv:
         ranks before dividing by field 0)."""
         tot = self._ep_stats.sum(dim=1)
         if reset:
+            if self._term_eps is not None:              # termination_stats() counts finished episodes from this block: keep what is zeroed
+                self._term_eps[0] += self._ep_stats[0].sum(dtype=torch.float64) - self._term_eps[1]
+                self._term_eps[1] = 0.0
             self._ep_stats.zero_()
         return tot
 
@@ -874,7 +969,7 @@ class SoloVecEnv:
 def make_vec_envs(config, num_envs, env_constructor=None, gamma=0.99, device=None, training=True, seed=1,
                   env_id_offset=0, norm_obs=False, norm_ret=False, clipob=10., cliprew=10., epsilon=1e-8,
                   push_interval=None, push_max_vel=0.0, push_max_yaw_rate=0.0, reward_shaping=None,
-                  obs_noise=None, action_delay=None, motor_gain_range=0.0, commands=None):
+                  obs_noise=None, action_delay=None, motor_gain_range=0.0, commands=None, termination=None):
     """Signature of agents/ppo/envs.py:14.  ``env_constructor`` (the per-process gym env class of the
     reference) is accepted for call-site compatibility and ignored.  ``norm_obs`` / ``norm_ret`` are VecNormalize's ``ob`` /
     ``ret`` (agents/running_mean_std.py:79; the reference's launcher passes False, False, and so do the defaults here) with its
@@ -892,7 +987,10 @@ def make_vec_envs(config, num_envs, env_constructor=None, gamma=0.99, device=Non
     motor gain error in front of every step (SoloVecEnv.set_actuation).  Off, nothing is allocated or launched.
     ``commands`` (a dict with ``lin_vel_x``, ``lin_vel_y``, ``yaw_rate`` as [lo, hi] pairs, ``interval``, ``zero_prob``, ``min_lin_norm``,
     ``obs_scale``, as configs/commands_walk12.yaml holds it; None = no commands, and nothing is allocated or launched): per-env velocity
-    commands, three more observation words, and the tracking terms of ``reward_shaping`` against each env's own command."""
+    commands, three more observation words, and the tracking terms of ``reward_shaping`` against each env's own command.
+    ``termination`` (a dict with ``base_height``, ``max_tilt_deg``, ``contacts``, ``contact_force_min``, ``joint_limits``, ``min_steps``,
+    ``terminal_reward``, as configs/termination_walk12.yaml holds it; None = the engine's own endings only, and nothing is allocated or
+    launched): early termination rules behind every step (SoloVecEnv.set_termination)."""
     envs = SoloVecEnv(config, num_envs, device=device, seed=seed, env_id_offset=env_id_offset, norm_obs=norm_obs, norm_ret=norm_ret,
                       clipob=clipob, cliprew=cliprew, gamma=gamma, epsilon=epsilon, commands=commands)
     if push_interval is not None:
@@ -907,6 +1005,9 @@ def make_vec_envs(config, num_envs, env_constructor=None, gamma=0.99, device=Non
         envs.set_obs_noise(obs_noise)
     if action_delay is not None or motor_gain_range:
         envs.set_actuation(action_delay, motor_gain_range)
+    if termination is not None:
+        from .termination import rules_from_dict
+        envs.set_termination(**rules_from_dict(termination))
     if not training:
         envs.eval()
     return envs

@@ -49,6 +49,10 @@ def add_channel_flags(p):
                    help="per-env velocity commands: ranges of lin_vel_x, lin_vel_y and yaw_rate, `interval`, `zero_prob`, `min_lin_norm`, "
                         "`obs_scale`, e.g. configs/commands_walk12.yaml; the observation gains three words and the tracking terms of "
                         "--reward-shaping follow each env's own command (default: no commands)")
+    p.add_argument("--termination", type=str, default=None, metavar="FILE.yaml",
+                   help="early termination rules checked on the state after every step: `base_height`, `max_tilt_deg`, `contacts` with "
+                        "`contact_force_min`, `joint_limits`, `min_steps`, `terminal_reward`, e.g. configs/termination_walk12.yaml (default: "
+                        "the engine's own endings only)")
     p.add_argument("--obs-noise", type=str, default=None, metavar="FILE.yaml",
                    help="uniform sensor noise on every observation: `groups:` (observation group -> half-width in physical units) and "
                         "`history:`, e.g. configs/noise_solo.yaml (default: clean observations)")
@@ -78,6 +82,18 @@ def load_commands(path):
         return ranges_from_dict(load_yaml(path))
     except (ValueError, AttributeError, TypeError) as e:
         raise SystemExit("--commands %s: %s" % (path, e))
+
+
+def load_termination(path, config):
+    """--termination FILE.yaml -> its dict, with unknown keys and bad values refused by name before anything is built"""
+    from solorl_amd.config import config_from_dict, load_yaml
+    from solorl_amd.termination import make_termination, rules_from_dict
+    try:
+        rules = rules_from_dict(load_yaml(path))
+        make_termination(config_from_dict(config), **rules)
+        return rules
+    except (ValueError, AttributeError, TypeError) as e:
+        raise SystemExit("--termination %s: %s" % (path, e))
 
 
 def get_ppo_args(argv=None):
@@ -152,6 +168,8 @@ def main(argv=None):
         args.obs_noise = load_obs_noise(args.obs_noise, config)
     if args.commands is not None:
         args.commands = load_commands(args.commands)
+    if args.termination is not None:
+        args.termination = load_termination(args.termination, config)
     writer = None
     rank = int(os.environ.get("RANK", "0"))
     if args.logdir is not None:      # run directory named as training/train_ppo.py:64-72
