@@ -14,7 +14,8 @@ and motor gain error (SoloVecEnv.set_obs_noise / set_actuation).
 ranges; --command VX VY WZ gives every env that one command for the whole run (joystick control).  With either, the summary adds the
 mean absolute tracking error of the base-frame velocity xy [m/s] and of the base-frame yaw rate [rad/s] over all envs and steps.
 --termination FILE.yaml (train_ppo.py's flag) evaluates under early termination rules (SoloVecEnv.set_termination); the summary adds the
-share of the finished episodes that each rule ended."""
+share of the finished episodes that each rule ended.
+--reset-randomization FILE.yaml (train_ppo.py's flag) evaluates from randomised initial states (SoloVecEnv.set_reset_randomization)."""
 import argparse
 import os
 import sys
@@ -84,7 +85,7 @@ def main(argv=None):
     p.add_argument("--max-steps", type=int, default=0, help="stop after K control steps even if fewer than --num-runs episodes have ended (0 = no limit)")
     p.add_argument("--push-interval", type=int, default=0, help="kick every env's base velocity every K control steps (0 = never)")
     p.add_argument("--push-max-vel", type=float, default=0.0, help="a kick's x and y velocity change is uniform in +-V m/s")
-    from train_ppo import add_channel_flags, load_commands, load_obs_noise, load_termination
+    from train_ppo import add_channel_flags, load_commands, load_obs_noise, load_reset_randomization, load_termination
     add_channel_flags(p)
     p.add_argument("--command", type=float, nargs=3, default=None, metavar=("VX", "VY", "WZ"),
                    help="one fixed velocity command for every env: vx vy [m/s, base frame] and yaw rate [rad/s]; with --commands it keeps "
@@ -113,7 +114,8 @@ def main(argv=None):
     env = make_vec_envs(config, a.num_agents, None, device=dev, training=False, seed=a.seed, norm_obs=ob_rms is not None,
                         obs_noise=None if a.obs_noise is None else load_obs_noise(a.obs_noise, config), action_delay=a.action_delay,
                         motor_gain_range=a.motor_gain_range, commands=commands,
-                        termination=None if a.termination is None else load_termination(a.termination, config))
+                        termination=None if a.termination is None else load_termination(a.termination, config),
+                        reset_randomization=None if a.reset_randomization is None else load_reset_randomization(a.reset_randomization, config))
     width = ckpt["state_dict"]["base.features.0.weight"].shape[1]
     if width != env.obs_dim:
         raise SystemExit("the checkpoint's policy reads %d observation words, this run's observation has %d (%d of the engine%s): "

@@ -58,7 +58,12 @@
  *                             pos.z < 0.05 only: baseEnv.py:162-180): early termination rules -- base height, tilt, contact of chosen
  *                             primitives, joint limits -- on a whole batch of state rows after a step, one launch, handle-free; it
  *                             sets done, the terminal reward and the episode statistics and leaves a mask for solorl_reset_masked
- *   solorl_destroy         <- agents/ppo/envs.py:129-135 (close)
+ *   solorl_randomize_reset / solorl_restart_history : randomised initial states (no reference counterpart: its reset is one fixed pose
+ *                             and a random settle count): joint angles and velocities, base velocity and heading, roll and pitch of a
+ *                             whole batch of state rows drawn on the device from a Philox stream per env, the robot placed on the
+ *                             ground by the kinematics of the new pose, one launch, handle-free; and the handle's history restarted
+ *                             from the state it holds, so that the first observation's delta words are exactly 0
+ *   solorl_destroy        <- agents/ppo/envs.py:129-135 (close)
  *
  * Plain pointers and sizes only; no torch types.  All array arguments are DEVICE pointers
  * (HIP, the device the handle was created on); the engine never retains them past the stream
@@ -264,7 +269,7 @@ int solorl_set_state(solorl_env* env, int env_index, const solorl_env_state* in 
  *   env_goals_reached, dr, treadmill_y | COUNTERS timestep, need_reset, rng_counter.
  *   NOTHING ELSE IS DERIVED on a partial write: a caller who moves a pointgoal env with POSE also writes `potential` (the distance to the
  *   goal the next step's `progress` is measured from) with TASK; one who changes q leaves the history's old angles unless it writes
- *   HISTORY.  fields == 0 or bits outside SOLORL_SF_ALL: SOLORL_ERR_INVALID.
+ *   HISTORY -- or calls solorl_restart_history afterwards, which rebuilds the levels from the new state bit for bit.  fields == 0 or bits outside SOLORL_SF_ALL: SOLORL_ERR_INVALID.
  *   "Has been reset": solorl_set_states(mask = NULL, fields = SOLORL_SF_ALL) gives every env a complete state and marks the handle as
  *   reset, whatever the rows' need_reset members say -- the host cannot read them without synchronising, so they are the caller's
  *   business (solorl_set_state, which sees its one host row, marks the handle only when that row's need_reset is 0).  Any other
@@ -617,6 +622,75 @@ int solorl_terminate(const solorl_config* cfg, const solorl_termination* p,
                      uint8_t* fired_out /* [n]: the rule bits that fired, 0 where none */,
                      const solorl_info_soa* info /* or NULL; arrays of n elements, ep_stats [FIELDS][n] */,
                      float* term_stats /* [1 + SOLORL_TERM_RULES][n] or NULL */, int device_id, void* stream);
+
+/* Randomised initial states (no reference counterpart; the "initial state distribution" of domain-randomised legged-robot training).  A
+ * reset copies one of 7 snapshots (14 with the treadmill): every episode starts at rest, facing +x, with the same joint angles.  A fifth
+ * handle-free row query beside solorl_kinematics, solorl_dynamics, solorl_shape_reward and solorl_terminate: a pure function of its
+ * arguments, ONE kernel launch on `stream`, no allocation, no host synchronisation (capturable).  It changes state ROWS in place; a
+ * caller moves them in and out of a handle with solorl_get_states / solorl_set_states and then restarts the handle's history:
+ *   solorl_get_states(mask, rows) -> solorl_randomize_reset(rows, mask, count) ->
+ *   solorl_set_states(mask, rows, POSE | VEL | JOINT_POS | JOINT_VEL | CONTACT) -> solorl_restart_history(mask, obs rows).
+ * The step kernels know nothing of it.
+ * Draws (all of them a function of seed, global env id, the env's episode index and *p -- never of the state or the actions; all
+ * arithmetic fp64, every product and sum rounded on its own, no fused multiply-add):
+ *   episode    k = count[i] on entry; count[i] = k + 1 on return, for every selected row.  Valid for k < 2^28 (16 k + b is a 32-bit word).
+ *   key        the seed (lo, hi), as for the env's own stream
+ *   counter    (gid_lo, gid_hi, 16 k + b, 8) with gid = env_id_offset + i.  The env's own stream uses 1, 2 and 3 in the last word, the
+ *              kicks 4, the noise 5, the actuator draws 6, the commands 7; none of these draws reads or advances rng_counter.
+ *   block b = 0, 1, 2    words 0..3 -> q[4 b .. 4 b + 3], half-widths joint_pos[..]
+ *   block b = 3, 4, 5    words 0..3 -> qd[4 (b - 3) .. 4 (b - 3) + 3], half-widths joint_vel[..]
+ *   block b = 6          words 0, 1, 2 -> lin_vel x, y, z, half-widths lin_vel[..]; word 3 -> the yaw angle psi, half-width yaw
+ *   block b = 7          words 0, 1, 2 -> ang_vel x, y, z, half-widths ang_vel[..]; word 3 -> the roll angle phi, half-width roll
+ *   block b = 8          word 0 -> the pitch angle theta, half-width pitch
+ *   A Solo8 draws nothing for joints 8..11 (blocks 2 and 5) and leaves those words of the row alone.
+ *   uniform    u = (word >> 8) * 2^-24;  d = (2 u - 1) * a in double (2 u - 1 is exact: one rounding);  member <- member + d
+ *   zero       a half-width of 0 is an exact no-op: the word is not written, -0.0 survives (the convention of solorl_perturb)
+ *   q          q[j] <- fmin(fmax(q[j] + d, -joint_limit), +joint_limit) with cfg's joint_limit, where joint_pos[j] != 0 (C's fmax / fmin:
+ *              a q[j] that is NaN on entry comes out as -joint_limit)
+ * Orientation, unless yaw, roll and pitch are all 0 (then quat is not touched, not even normalised):
+ *   quat <- Rz(psi) * quat * Rx(phi) * Ry(theta), then divided by its norm, then negated as a whole if w < 0: the yaw turns the robot
+ *   about the WORLD's z axis, roll and pitch follow about the BODY's x and y axes.  (Rz(psi) = (0, 0, sin psi/2, cos psi/2) in the
+ *   row's x, y, z, w order.)
+ * Placing, if place_on_ground != 0: zmin = the smallest z of the support points of the robot's collision primitives on the NEW row
+ *   (solorl_env_kin.prim_point[p][2], by the code solorl_kinematics runs; p = 0..19 on a Solo8, 0..23 on a Solo12; a NaN point is
+ *   skipped);  pos.z <- pos.z + (clearance - zmin), up or down.  pos.x and pos.y are never written: a treadmill strip and a pointgoal
+ *   potential stay valid.
+ * Contact cache: lambda_prev[0..23] <- 0 and bits 0..23 of contact_mask <- 0 (bits 24.. and rng_counter keep their bits) if and only if
+ *   the pose can change: some joint_pos[j], j < act_dim, or yaw, roll or pitch is non-zero, or place_on_ground is set.  (An impulse
+ *   cached for a primitive that has moved is wrong.)  The four feet words of the next observation therefore read 0 until the first step.
+ * Rows:
+ *   selected   words pos .. qd (the first 37), and with the contact cache the 24 lambda_prev words and the contact_mask word, are
+ *              written; no other word of the row is.  A non-finite member gives non-finite members of that row only; no index is
+ *              computed from a row's data.
+ *   masked (mask byte 0)   nothing of the row and not count[i] is read or written
+ * Null cfg, p, rows or count, n < 1, a robot that is neither SOLORL_ROBOT_*, a negative or non-finite half-width or clearance, yaw, roll
+ * or pitch above pi, a negative or non-finite cfg->joint_limit: SOLORL_ERR_INVALID, the message starts with "solorl_randomize_reset:"
+ * (checked before any HIP call).
+ * Shards: keyed by global env id: W batches of n rows at offsets k n draw like one batch of W n rows. */
+typedef struct solorl_reset_randomization {
+  uint64_t seed; int64_t env_id_offset;
+  double joint_pos[12];   /* q[j]  += U(-a, a) [rad], then clamped to +-cfg->joint_limit */
+  double joint_vel[12];   /* qd[j] += U(-a, a) [rad/s] */
+  double lin_vel[3], ang_vel[3];   /* world frame, += U(-a, a) */
+  double yaw, roll, pitch;         /* half-widths [rad] of the rotations above, each <= pi */
+  double clearance;       /* [m] height of the lowest support point above z = 0 after placing */
+  int32_t place_on_ground, reserved;
+} solorl_reset_randomization;
+int solorl_randomize_reset(const solorl_config* cfg, const solorl_reset_randomization* p,
+                           solorl_env_state* rows /* [n] DEVICE rows, changed in place */,
+                           const uint8_t* mask /* [n] or NULL */, uint32_t* count /* [n] device, in/out */, int n,
+                           int device_id, void* stream);
+
+/* solorl_restart_history: for the envs whose mask byte is non-zero, every history level the handle uses (0 .. num_history_stack - 1)
+ * <- the observation words of the state the env holds NOW (SoloBase.get_current_state), in the engine's own arithmetic type, and then
+ * -- if obs_out is not NULL -- the env's observation row, whose delta words are therefore exactly 0 and whose first D words equal
+ * solorl_get_observation's.  Nothing else of the env and nothing of an unselected env is read or written; with contact-count sorting the
+ * mask is read through the slot -> env map, as in solorl_reset_masked.  One launch on `stream`, no host synchronisation (capturable).
+ * This is what a caller who writes q (or anything else the observation holds) with solorl_set_states needs instead of rebuilding the
+ * HISTORY group on the host: see the JOINT_POS remark there.  Null handle or mask: SOLORL_ERR_INVALID, the message names the function;
+ * SOLORL_ERR_STATE on a handle that has not been reset. */
+int solorl_restart_history(solorl_env* env, const uint8_t* mask /* [N] device, not NULL */,
+                           float* obs_out /* [N*O] or NULL */, void* stream);
 
 /* Fused return computation over a rollout of T steps x N envs (device arrays, time-major [t][n]).
  * use_gae != 0:  value_preds[T][:] = next_value;  delta_t = r_t + gamma V_{t+1} m_{t+1} - V_t;

@@ -21,7 +21,7 @@ SYMBOLS = ("solorl_default_config", "solorl_create", "solorl_destroy", "solorl_d
            "solorl_set_perturbation", "solorl_perturb", "solorl_get_perturbation",
            "solorl_norm_scratch_count", "solorl_normalize_obs", "solorl_normalize_rewards", "solorl_kinematics", "solorl_dynamics",
            "solorl_shape_reward", "solorl_obs_noise", "solorl_actuate", "solorl_commands", "solorl_shape_reward_cmd",
-           "solorl_terminate")
+           "solorl_terminate", "solorl_randomize_reset", "solorl_restart_history")
 
 
 class PolicyParams(C.Structure):            # solorl_policy_params
@@ -85,6 +85,12 @@ class Termination(C.Structure):             # solorl_termination
     _fields_ = [("rules", C.c_uint32), ("min_steps", C.c_int32), ("contact_prims", C.c_uint32), ("reserved", C.c_int32), ("min_height", C.c_double),
                 ("min_up_z", C.c_double), ("contact_force_min", C.c_double), ("joint_lo", C.c_double * 12), ("joint_hi", C.c_double * 12),
                 ("terminal_reward", C.c_double)]
+
+
+class ResetRandomization(C.Structure):      # solorl_reset_randomization
+    _fields_ = [("seed", C.c_uint64), ("env_id_offset", C.c_int64), ("joint_pos", C.c_double * 12), ("joint_vel", C.c_double * 12),
+                ("lin_vel", C.c_double * 3), ("ang_vel", C.c_double * 3), ("yaw", C.c_double), ("roll", C.c_double), ("pitch", C.c_double),
+                ("clearance", C.c_double), ("place_on_ground", C.c_int32), ("reserved", C.c_int32)]
 
 
 class SoloRLError(RuntimeError):
@@ -170,6 +176,12 @@ def lib():
         L.solorl_terminate.argtypes = [C.POINTER(SoloConfig), C.POINTER(Termination), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.POINTER(InfoSoA), C.c_void_p, C.c_int, C.c_void_p]
         L.solorl_terminate.restype = C.c_int
+        # randomised initial states (reset_random.py): the row query is handle-free (cfg and params are host structs, rows, mask and count
+        # device pointers); the history restart takes the handle, a device mask and the observation rows
+        L.solorl_randomize_reset.argtypes = [C.POINTER(SoloConfig), C.POINTER(ResetRandomization), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_int, C.c_void_p]
+        L.solorl_restart_history.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.solorl_randomize_reset.restype = L.solorl_restart_history.restype = C.c_int
         for s in SYMBOLS:
             getattr(L, s)
         # the ctypes mirrors in config.py / this file are written against one layout of include/solorl.h's structs

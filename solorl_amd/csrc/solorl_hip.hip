@@ -1007,6 +1007,34 @@ __global__ void obs_kernel(const T* sf, const int* si, Layout L, int N, int task
   write_obs<T, ROBOT>(E, sf, L, (idx_t)N, e, (idx_t)si[SX(I_ENVID, e, NI)], task, obs);
 }
 
+// solorl_restart_history: every history level the handle uses <- current_state of the state the env holds, for the envs whose mask byte
+// is set (read through the slot -> env map, as reset_kernel<.., true> does), then the env's observation row as write_obs lays it out:
+// the state words, and per level cs - level = cs - cs, exactly 0 (NaN where cs is not finite, as write_obs gives).  ONE current_state
+// feeds the levels and the row.  A second copy behind the stores (write_obs's own) was merged with the first one only in part, and with
+// its products shared between the copies the compiler fused other multiply-adds than it does in obs_kernel: the yaw word of one env in 65
+// came out 1 ulp from solorl_get_observation's.  Nothing else of the env is written.  (Launched with 256 threads and bounded so.)
+template <typename T, int ROBOT>
+__global__ void __launch_bounds__(256) restart_history_kernel(T* sf, const int* si, Layout L, int N, int task, float* obs, const unsigned char* mask) {
+  const idx_t e = (idx_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (idx_t)N) return;
+  const idx_t env = (idx_t)si[SX(I_ENVID, e, NI)];
+  if (!mask[env]) return;                                  // (in front of the state's loads)
+  Env<T, Robot<ROBOT>::NQ> E;
+  load_env(E, sf, si, L, (idx_t)N, e);
+  T cs[DMAX];
+  current_state<T, ROBOT>(E, task, cs);
+  float* o = obs ? obs + env * (idx_t)(L.D * (1 + L.H)) : nullptr;
+#pragma unroll
+  for (int d = 0; d < DMAX; d++)
+    if (d < L.D) {
+      for (int h = 0; h < L.H; h++) sf[SX(L.hist + h * HSTRIDE + d, e, L.NF)] = cs[d];
+      if (o) {
+        o[d] = (float)cs[d];
+        for (int h = 0; h < L.H; h++) o[(h + 1) * L.D + d] = (float)(cs[d] - cs[d]);
+      }
+    }
+}
+
 // initial pose of SoloBase.robot_specific_reset (solo.py:291-296) for every env of a buffer
 template <typename T>
 __global__ void init_pose_kernel(T* sf, int* si, Layout L, int N, T tmy) {
@@ -2054,6 +2082,20 @@ int solorl_reset_masked(solorl_env* h, const uint8_t* mask, float* obs_out, void
   if (!mask) return fail(SOLORL_ERR_INVALID, "solorl_reset_masked: null mask");
   if (!h->reset_called) return fail(SOLORL_ERR_STATE, "solorl_reset_masked: needs a handle that has been reset");
   return launch_reset<true>(h, mask, obs_out, stream);
+}
+
+int solorl_restart_history(solorl_env* h, const uint8_t* mask, float* obs_out, void* stream) {
+  if (!h) return fail(SOLORL_ERR_INVALID, "solorl_restart_history: null handle");
+  if (!mask) return fail(SOLORL_ERR_INVALID, "solorl_restart_history: null mask");
+  if (!h->reset_called) return fail(SOLORL_ERR_STATE, "solorl_restart_history: needs a handle that has been reset");
+  HIP_TRY(hipSetDevice(h->device));
+  with_instantiation(h, [&](auto t, auto robot) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((restart_history_kernel<T, decltype(robot)::value>), dim3((h->N + 255) / 256), dim3(256), 0, (hipStream_t)stream, (T*)h->sf, (const int*)h->si,
+                       h->L, h->N, h->cfg.task, obs_out, mask);
+  });
+  HIP_TRY(hipGetLastError());
+  return 0;
 }
 
 // ---- device-side kicks (perturb_kernel above; the draw rules are in include/solorl.h)

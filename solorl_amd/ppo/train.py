@@ -30,6 +30,11 @@ Differences that come with the GPU engine (documented, not behavioural):
     step launch of the eager and of the captured rollout alike (SoloVecEnv.set_termination), the envs it ends reset on the device; the
     share of the finished episodes each rule ended is logged as term/<rule> beside dr/* and sr/*.  The policy cannot run inside the step
     kernel (it would act on the observation of an env that is about to be reset): the rollout takes two launches per step;
+  * args.reset_randomization (train_ppo.py --reset-randomization FILE.yaml: a dict of half-widths; no reference counterpart) starts every
+    episode from a randomised state -- joint angles and velocities, base velocity, heading, roll and pitch, the robot placed on the
+    ground -- by four launches behind every step launch of the eager and of the captured rollout alike
+    (SoloVecEnv.set_reset_randomization), keyed by global env id, so ranks draw like one batch.  The policy cannot run inside the step
+    kernel (it would act on the observation of the un-randomised reset): the rollout takes two launches per step;
   * multi-GPU: one process per GPU (`python -m torch.distributed.run --nproc-per-node W ...`), envs
     sharded by rank (global env id = rank*N + i), flat-bucket RCCL gradient all-reduce (ppo.py).
 """
@@ -103,7 +108,8 @@ def train(args, config, env_constructor=None, writer=None):
                          push_max_vel=getattr(args, "push_max_vel", 0.0), push_max_yaw_rate=getattr(args, "push_max_yaw_rate", 0.0),
                          reward_shaping=getattr(args, "reward_shaping", None), obs_noise=getattr(args, "obs_noise", None),
                          action_delay=getattr(args, "action_delay", None), motor_gain_range=getattr(args, "motor_gain_range", 0.0),
-                         commands=getattr(args, "commands", None), termination=getattr(args, "termination", None))
+                         commands=getattr(args, "commands", None), termination=getattr(args, "termination", None),
+                         reset_randomization=getattr(args, "reset_randomization", None))
     shaping = getattr(args, "reward_shaping", None) is not None
     termination = getattr(args, "termination", None) is not None
     action_dim = envs.action_space.shape[0]

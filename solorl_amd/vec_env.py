@@ -28,6 +28,9 @@
   set_termination(**rules), last_termination, termination_stats()   (early termination rules -- base height, tilt, contact of chosen
       primitives, joint limits -- checked on the state after every step by one launch, the envs they end reset on the device:
       include/solorl.h solorl_terminate, termination.py)
+  set_reset_randomization(**ranges), reset_randomization_count   (randomised initial states -- joint angles and velocities, base
+      velocity, heading, roll and pitch drawn per env and episode on the device, the robot placed on the ground -- behind every reset:
+      include/solorl.h solorl_randomize_reset / solorl_restart_history, reset_random.py)
 
 torch is plumbing only: it owns the device buffers and the stream; all arithmetic happens in
 ``libsolorl_hip.so`` on the caller's current HIP stream (no host synchronisation in step()).
@@ -41,7 +44,9 @@ from . import _native
 from .config import SoloConfig, EnvState, InfoSoA, config_from_dict, EPSTAT_FIELDS, EPSTAT_NAMES
 from .normalize import RunningMeanStd, VecNormalizer
 from .rows import mask_arg
-from .state import StateBatch, field_bits, SF_VEL
+from .state import StateBatch, field_bits, SF_POSE, SF_VEL, SF_JOINT_POS, SF_JOINT_VEL, SF_CONTACT
+
+_RR_FIELDS = SF_POSE | SF_VEL | SF_JOINT_POS | SF_JOINT_VEL | SF_CONTACT      # what solorl_randomize_reset may change of a row
 
 
 class Box:
@@ -186,6 +191,11 @@ class SoloVecEnv:
         self._term_stats = None     # [5, N] float32: early terminations and the rules that fired in them, per env
         self._term_eps = None       # [2] float64: finished episodes already flushed out of ep_stats, and the ep_stats count they start from
         self.last_termination = None   # [N] uint8: the rule bits that ended each env's episode in the last step, 0 where none
+        # randomised initial states (set_reset_randomization): nothing is allocated or launched unless it is set
+        self._rr = None             # ResetRandomization; None = the engine's own snapshots
+        self._rr_states = None      # engine-owned StateBatch the freshly reset envs are read into and written back from
+        self._rr_all = None         # [N] uint8 of ones: the mask of reset()
+        self.reset_randomization_count = None   # [N] int32 (uint32 words): the episodes each env has drawn an initial state for
         self._info_c = InfoSoA(ep_stats=self._ep_stats.data_ptr(), applied_torque=None if self._tau is None else self._tau.data_ptr(),
                                **{k: self._info[k].data_ptr() for k in _INFO_KEYS})
         # VecNormalize (agents/running_mean_std.py:73-127; the reference's launcher passes ob=False, ret=False: agents/ppo/envs.py:26):
@@ -268,6 +278,9 @@ class SoloVecEnv:
         if self._term is not None:
             raise _native.SoloRLError("%s with a termination set: the policy inside the step kernel would act on the observation of an env "
                                       "that is about to be reset (step_act_supported() / rollout_supported() are False)" % name)
+        if self._rr is not None:
+            raise _native.SoloRLError("%s with a reset randomization set: the policy inside the step kernel would act on the observation of the "
+                                      "un-randomised reset (step_act_supported() / rollout_supported() are False)" % name)
 
     def _stream(self):
         return _native.stream(self.device)
@@ -465,6 +478,53 @@ class SoloVecEnv:
                 out["term/" + name] = (tot[1 + k] / n) if n > 0 else float("nan")
         return out
 
+    # ---- randomised initial states (include/solorl.h solorl_randomize_reset / solorl_restart_history; reset_random.py)
+    def set_reset_randomization(self, ranges=None, **more):
+        """Every episode starts from a randomised state: half-widths ``joint_pos`` [rad] and ``joint_vel`` [rad/s] (a scalar or one value per
+        joint), ``lin_vel`` [m/s] and ``ang_vel`` [rad/s] (a scalar or x, y, z; world frame), ``yaw``, ``roll``, ``pitch`` [rad], and
+        ``place_on_ground`` (default True) with ``clearance`` [m] -- reset_random.make_reset_randomization; as keywords or as one dict.
+        ``set_reset_randomization(None)`` switches it off.  Allocates an engine-owned StateBatch and ``reset_randomization_count``
+        (int32 [N]: the episodes each env has drawn for) at the first call and zeroes the count at every call; call it before capturing
+        a HIP graph of steps (the ranges are launch arguments).
+
+        While set, four launches on the same stream follow every reset of an env -- get_states(mask), ONE solorl_randomize_reset,
+        solorl_set_states(mask, pose | vel | joint_pos | joint_vel | contact) and solorl_restart_history(mask) into the observation rows
+        the engine has just written -- with mask = the merged done flags in step() and step_inplace(), every env in reset(), the selected
+        envs in reset_masked().  In a step they stand behind the shaped terms and in front of the noise: the shaped terms and the
+        termination see what they see without it; noise, commands and normalisation see the randomised first observation, whose delta
+        words are exactly 0 and whose four feet words are 0 (the contact cache is dropped with the pose).  The policy inside the step
+        kernel would act on the observation of the un-randomised reset, so step_act_supported() and rollout_supported() are False,
+        step_act_inplace() raises, and so do step_n*, rollout_inplace (K steps in one launch)."""
+        from .reset_random import make_reset_randomization
+        if ranges is None and not more:
+            self._rr = self._rr_states = self._rr_all = self.reset_randomization_count = None
+            return
+        p = make_reset_randomization(self.cfg, self._seed, self._id0, **dict(ranges or {}, **more))
+        if self._rr_states is None:
+            self._rr_states = StateBatch(self.nenvs, self.device)
+            self._rr_all = torch.ones((self.nenvs,), dtype=torch.uint8, device=self.device)
+            self.reset_randomization_count = torch.zeros((self.nenvs,), dtype=torch.int32, device=self.device)
+        else:
+            self.reset_randomization_count.zero_()
+        self._rr = p
+
+    def _randomize(self, e, mask):
+        """the randomised initial state of the envs ``mask`` selects (uint8 [N]: they have just been reset), and their rows of the
+        engine's observation rows ``e``"""
+        if self._rr is None:
+            return
+        from .reset_random import randomize_reset
+        rows = self.get_states(mask, out=self._rr_states)
+        randomize_reset(self.cfg, self._rr, rows, self.reset_randomization_count, mask=mask)
+        self.set_states(rows, mask, _RR_FIELDS)
+        with torch.cuda.device(self.device):
+            _native.check(self.L.solorl_restart_history(self._h, C.c_void_p(mask.data_ptr()), C.c_void_p(e.data_ptr()), self._stream()))
+
+    def _no_reset_randomization(self, name):
+        if self._rr is not None:
+            raise _native.SoloRLError("%s with a reset randomization set: K steps in one launch cannot take its launches behind a reset between "
+                                      "the steps (rollout_supported() is False; step one at a time, or set_reset_randomization(None))" % name)
+
     # ---- observation noise and actuation (include/solorl.h solorl_obs_noise / solorl_actuate; channel.py)
     def set_obs_noise(self, scales):
         """Uniform sensor noise on every observation the engine hands out: ``scales`` is a dict of half-widths in physical units per
@@ -589,6 +649,7 @@ class SoloVecEnv:
             _native.check(self.L.solorl_reset(self._h, C.c_void_p(self._obs_engine.data_ptr()), self._stream()))
         if self._act is not None:                       # every env starts an episode
             self._act_restart.fill_(1)
+        self._randomize(self._obs_engine, self._rr_all)
         self._noise(self._obs_engine)
         self._commands(self._obs, self._cmd_all)        # every env draws a command
         if self._shape_mem is not None:                 # every env starts an episode
@@ -615,6 +676,7 @@ class SoloVecEnv:
         rows = self._terminate(self._obs_engine, self._rew, self._done)
         self._restarts(self._done)
         self._shape(a, self._rew, self._done, rows)     # (with commands: against the command the policy acted on, before it is redrawn)
+        self._randomize(self._obs_engine, self._done)
         self._noise(self._obs_engine)
         self._commands(self._obs, self._done)
         if self._norm is not None:
@@ -659,6 +721,7 @@ class SoloVecEnv:
         rows = self._terminate(e, r, d)
         self._restarts(d)
         self._shape(actions, r, d, rows)
+        self._randomize(e, d)
         self._noise(e)
         self._commands(o, d)
         if self._norm is not None:
@@ -673,6 +736,7 @@ class SoloVecEnv:
                 and self._noise_scale is None      # (... and the clean ones)
                 and self._cmd is None              # (... and rows without the command words)
                 and self._term is None             # (... and act on the observation of an env that is about to be reset)
+                and self._rr is None               # (... or on the observation of the un-randomised reset)
                 and self.get_property("step_n_one_launch") == 1 and self.get_property("f64") == 0 and self.obs_dim % 4 == 0 and self.obs_dim <= 88
                 and params.obs_dim == self.obs_dim and params.act_dim == self.act_dim and params.hidden == 64)
 
@@ -742,6 +806,7 @@ class SoloVecEnv:
         self._no_channel("step_n")
         self._no_commands("step_n")
         self._no_termination("step_n")
+        self._no_reset_randomization("step_n")
         K = int(actions.shape[0]) if actions.dim() == 3 else 0
         if K < 1:
             raise AssertionError("actions must be [K, %d, %d] with K >= 1" % (self.nenvs, self.act_dim))
@@ -772,6 +837,7 @@ class SoloVecEnv:
         self._no_channel("rollout_inplace")
         self._no_commands("rollout_inplace")
         self._no_termination("rollout_inplace")
+        self._no_reset_randomization("rollout_inplace")
         pal = 1 if policy_after_last else 0
         R = int(actions.shape[0]) if actions.dim() == 3 else 0
         K = R - pal
@@ -923,6 +989,7 @@ class SoloVecEnv:
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_get_observation(self._h, C.c_void_p(self._obs_engine.data_ptr()), self._stream()))
             _native.check(self.L.solorl_reset_masked(self._h, pm, C.c_void_p(self._obs_engine.data_ptr()), self._stream()))
+        self._randomize(self._obs_engine, m)
         if self._act is not None:                       # the selected envs start an episode with their next action
             self._act_restart.bitwise_or_(m.ne(0).to(torch.uint8))
         if self._cmd is not None:                       # every row with the command it holds; the selected ones are rewritten below
@@ -969,7 +1036,7 @@ class SoloVecEnv:
 def make_vec_envs(config, num_envs, env_constructor=None, gamma=0.99, device=None, training=True, seed=1,
                   env_id_offset=0, norm_obs=False, norm_ret=False, clipob=10., cliprew=10., epsilon=1e-8,
                   push_interval=None, push_max_vel=0.0, push_max_yaw_rate=0.0, reward_shaping=None,
-                  obs_noise=None, action_delay=None, motor_gain_range=0.0, commands=None, termination=None):
+                  obs_noise=None, action_delay=None, motor_gain_range=0.0, commands=None, termination=None, reset_randomization=None):
     """Signature of agents/ppo/envs.py:14.  ``env_constructor`` (the per-process gym env class of the
     reference) is accepted for call-site compatibility and ignored.  ``norm_obs`` / ``norm_ret`` are VecNormalize's ``ob`` /
     ``ret`` (agents/running_mean_std.py:79; the reference's launcher passes False, False, and so do the defaults here) with its
@@ -990,7 +1057,10 @@ def make_vec_envs(config, num_envs, env_constructor=None, gamma=0.99, device=Non
     commands, three more observation words, and the tracking terms of ``reward_shaping`` against each env's own command.
     ``termination`` (a dict with ``base_height``, ``max_tilt_deg``, ``contacts``, ``contact_force_min``, ``joint_limits``, ``min_steps``,
     ``terminal_reward``, as configs/termination_walk12.yaml holds it; None = the engine's own endings only, and nothing is allocated or
-    launched): early termination rules behind every step (SoloVecEnv.set_termination)."""
+    launched): early termination rules behind every step (SoloVecEnv.set_termination).
+    ``reset_randomization`` (a dict with ``joint_pos``, ``joint_vel``, ``lin_vel``, ``ang_vel``, ``yaw``, ``roll``, ``pitch``, ``clearance``,
+    ``place_on_ground``, as configs/reset_walk12.yaml holds it; None = the engine's own snapshots, and nothing is allocated or launched):
+    randomised initial states behind every reset (SoloVecEnv.set_reset_randomization)."""
     envs = SoloVecEnv(config, num_envs, device=device, seed=seed, env_id_offset=env_id_offset, norm_obs=norm_obs, norm_ret=norm_ret,
                       clipob=clipob, cliprew=cliprew, gamma=gamma, epsilon=epsilon, commands=commands)
     if push_interval is not None:
@@ -1008,6 +1078,9 @@ def make_vec_envs(config, num_envs, env_constructor=None, gamma=0.99, device=Non
     if termination is not None:
         from .termination import rules_from_dict
         envs.set_termination(**rules_from_dict(termination))
+    if reset_randomization is not None:
+        from .reset_random import ranges_from_dict
+        envs.set_reset_randomization(**ranges_from_dict(reset_randomization))
     if not training:
         envs.eval()
     return envs

@@ -1,0 +1,327 @@
+"""solorl_randomize_reset and solorl_restart_history on the GPU: the kernel against the host program (tests/host/reset_random_main.cpp,
+the same arithmetic compiled by g++), the history restart on every engine mode, the four-launch chain through SoloVecEnv, determinism,
+the refused paths, and a captured graph beside termination and observation noise."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from solorl_amd import _native, reset_random
+from solorl_amd.config import EnvState, PRECISION_F64, ROBOT_SOLO8, ROBOT_SOLO12, TASK_STAND, TASK_WALK, default_config
+from solorl_amd.state import StateBatch
+from tests import reset_util as ru
+from tests.reset_util import W
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+ENVS = reset_random.ENVS_PER_WORKGROUP
+RANGES = dict(joint_pos=0.2, joint_vel=1.0, lin_vel=0.3, ang_vel=0.3, yaw=3.14, roll=0.1, pitch=0.1, clearance=0.01)
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    return ru.build_host(tmp_path_factory.mktemp("reset_gpu"))
+
+
+# ---- 1: the kernel against the host program
+def gpu_reset(robot12, p, rows, count, mask=None):
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    sb = StateBatch(data=dev(rows))
+    cnt = dev(count.view(np.int32))
+    m = None if mask is None else dev(np.asarray(mask, np.uint8))
+    out = reset_random.randomize_reset(p.config(robot12), p.struct(), sb, cnt, mask=m)
+    torch.cuda.synchronize()
+    assert out is sb
+    return sb.data.cpu().numpy(), cnt.cpu().numpy().view(np.uint32)
+
+
+def _against_host(exe, robot12, p, rows, count, mask, live, what):
+    got = gpu_reset(robot12, p, rows, count, mask)
+    want = ru.host_reset(exe, robot12, p, rows, count, mask)
+    return ru.check(got[0], got[1], want[0], want[1], rows, mask, live, what)
+
+
+@pytest.mark.parametrize("masked", (False, True), ids=("all", "masked"))
+@pytest.mark.parametrize("n", (1, ENVS + 2, 2 * ENVS + 2))
+@pytest.mark.parametrize("robot12", (1, 0), ids=("solo12", "solo8"))
+def test_kernel_equals_the_host_program(gpu_device, exe, robot12, n, masked):
+    """the crafted batch plus random rows (poison in every word the call does not own), a ragged last workgroup and more than one
+    workgroup: drawn members, count and contact words bitwise, quat and pos.z to 1e-12, everything else untouched"""
+    assert ENVS == 64 and 2 * ENVS + 2 == 130
+    rows = ru.batch(robot12, n)
+    live = np.ones(n, bool)
+    if n > 40:                                           # non-finite members: they stay in their row (its own bits are not compared)
+        for i, (w, v) in enumerate(((W("q") + 1, float("nan")), (W("quat") + 2, float("inf")), (ru.POS_Z, float("-inf")), (W("qd"), float("nan")))):
+            rows[30 + i, w] = v
+            live[30 + i] = False
+    count = (np.arange(n, dtype=np.uint32) * 3) % 11
+    mask = ((np.arange(n) % 3 != 1).astype(np.uint8) if n > 1 else np.ones(1, np.uint8)) if masked else None
+    p = ru.full(robot12, clearance=0.02)
+    err = _against_host(exe, robot12, p, rows, count, mask, live, "full")
+    print("robot12=%d n=%d: max |quat, pos.z| difference to the host program %.3e" % (robot12, n, err))
+    if n == 2 * ENVS + 2:
+        for name, q in (("no placing", p.but(place_on_ground=0)), ("velocities only", ru.Params(seed=4, id0=1 << 40, joint_vel=2.0, lin_vel=0.5, ang_vel=[0.0, 0.1, 0.0])),
+                        ("nothing", ru.Params(seed=9)), ("placing only", ru.Params(seed=9, place_on_ground=1, clearance=0.0)),
+                        ("solo8 widths for joints it lacks", ru.Params(seed=2, joint_pos=[0.0] * 8 + [0.3] * 4, joint_vel=[0.0] * 8 + [0.3] * 4))):
+            _against_host(exe, robot12, q, rows, count, mask, live, name)
+        got = gpu_reset(robot12, ru.Params(seed=4, joint_vel=2.0), rows, count, mask)[0]
+        assert np.array_equal(ru.bits(got[:, W("lambda_prev"):]), ru.bits(rows[:, W("lambda_prev"):])), "no pose change: the contact cache stays"
+
+
+# ---- 2: the history restart
+#        name            robot         task        f64  environment
+MODES = {"walk12_team":  (ROBOT_SOLO12, TASK_WALK,  0, {}),
+         "walk12_lane":  (ROBOT_SOLO12, TASK_WALK,  0, {"SOLORL_TEAM": "0"}),
+         "walk12_sort":  (ROBOT_SOLO12, TASK_WALK,  0, {"SOLORL_SORT": "1"}),
+         "stand8_f64":   (ROBOT_SOLO8,  TASK_STAND, 1, {})}
+
+
+def _make(mode, N, monkeypatch, H=1, seed=5, off=0, **fields):
+    from solorl_amd.vec_env import SoloVecEnv
+    robot, task, f64, env = MODES[mode]
+    c = default_config(robot, task)
+    c.num_history_stack = H
+    if f64:
+        c.precision = PRECISION_F64
+    for k, v in fields.items():
+        setattr(c, k, v)
+    for k in ("SOLORL_SORT", "SOLORL_TEAM"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)                         # (read at solorl_create)
+    return SoloVecEnv(c, N, device=DEV, seed=seed, env_id_offset=off)
+
+
+def _actions(N, A, steps, seed=11):
+    g = torch.Generator(device=DEV); g.manual_seed(seed)
+    return [(torch.rand(N, A, device=DEV, generator=g) * 2 - 1).contiguous() for _ in range(steps)]
+
+
+def _member_bytes(batch, name):
+    f = getattr(EnvState, name)
+    return batch.bytes()[:, f.offset:f.offset + f.size]
+
+
+@pytest.mark.parametrize("H", (0, 1, 2))
+@pytest.mark.parametrize("mode", tuple(MODES))
+def test_restart_history(gpu_device, monkeypatch, mode, H):
+    """after 5 random steps, half of the envs selected: their obs_out rows are solorl_get_observation's bit for bit with delta words
+    exactly 0, the levels in use hold the current state, everything else of every env keeps its bits.  (walk12_sort at 130 envs is the
+    case in which a kernel that computed the observation words twice gave one yaw word 1 ulp off.)"""
+    L = _native.lib()
+    for N in (6, 130):
+        env = _make(mode, N, monkeypatch, H=H)
+        mask = (torch.arange(N, device=DEV) % 2 == 0).to(torch.uint8)
+        sel = mask.bool()
+        poison = torch.full((N, env.engine_obs_dim), 7.5, device=DEV)
+        rc = L.solorl_restart_history(env._h, C.c_void_p(mask.data_ptr()), C.c_void_p(poison.data_ptr()), env._stream())
+        assert rc != 0 and b"solorl_restart_history: needs a handle that has been reset" in L.solorl_last_error()
+        env.reset()
+        for a in _actions(N, env.act_dim, 5):
+            env.step_inplace(a)
+        before, obs_before = env.get_states().clone(), env.get_observation()
+        _native.check(L.solorl_restart_history(env._h, C.c_void_p(mask.data_ptr()), C.c_void_p(poison.data_ptr()), env._stream()))
+        after, obs_after = env.get_states(), env.get_observation()
+        torch.cuda.synchronize()
+        D = env.engine_obs_dim // (1 + H)
+        diff = (poison[sel].view(torch.int32) != obs_after[sel].view(torch.int32)).nonzero()
+        assert diff.numel() == 0, ("selected rows are the observation", N, diff[:8].tolist(), poison[sel][diff[:8, 0], diff[:8, 1]].tolist(),
+                                   obs_after[sel][diff[:8, 0], diff[:8, 1]].tolist())
+        assert bool((poison[~sel] == 7.5).all()), "unselected rows of obs_out are not written"
+        assert torch.equal(obs_after[~sel].view(torch.int32), obs_before[~sel].view(torch.int32))
+        assert torch.equal(obs_after[:, :D].view(torch.int32), obs_before[:, :D].view(torch.int32)), "the state words do not move"
+        if H:
+            assert bool((poison[sel][:, D:] == 0).all()), "delta words are exactly 0"
+            assert bool((obs_before[sel][:, D:] != 0).any()), "(they were not before)"
+        hist = after.hist                                 # [N, 4, 42]
+        for h in range(H):
+            assert torch.equal(hist[sel, h, :D].view(torch.int64), hist[sel, 0, :D].view(torch.int64)), h
+            assert torch.equal(hist[sel, h, :D].float(), obs_after[sel, :D]), "a level is the current state"
+        assert torch.equal(after.hist[~sel].view(torch.int64), before.hist[~sel].view(torch.int64))
+        assert torch.equal(after.hist[:, H:].view(torch.int64), before.hist[:, H:].view(torch.int64)), "levels the handle does not use"
+        assert torch.equal(after.hist[:, :, D:].view(torch.int64), before.hist[:, :, D:].view(torch.int64))
+        for name, _ in EnvState._fields_:
+            if name != "hist":
+                assert torch.equal(_member_bytes(after, name), _member_bytes(before, name)), name
+        # obs_out = NULL: the levels alone
+        env.step_inplace(_actions(N, env.act_dim, 1, seed=2)[0])
+        _native.check(L.solorl_restart_history(env._h, C.c_void_p(mask.data_ptr()), None, env._stream()))
+        o = env.get_observation()
+        if H:
+            assert bool((o[sel][:, D:] == 0).all()) and bool((o[~sel][:, D:] != 0).any())
+        env.close()
+
+
+# ---- 3: the chain through SoloVecEnv
+def _distinct(rows):
+    return len({bytes(r) for r in rows.cpu().numpy().view(np.uint8)})
+
+
+def test_chain_through_the_vec_env(gpu_device, monkeypatch):
+    N = 130
+    env, twin = _make("walk12_team", N, monkeypatch, episode_length=7), _make("walk12_team", N, monkeypatch, episode_length=7)
+    assert env._rr is None and env._rr_states is None and env.reset_randomization_count is None       # off: nothing is allocated
+    twin.reset()
+    assert _distinct(twin.get_states().q.contiguous()) <= 7, "without the feature: the settle snapshots"
+    env.set_reset_randomization(RANGES)
+    obs = env.reset()
+    s = env.get_states()
+    assert _distinct(s.q.contiguous()) == N
+    zmin = env.get_kinematics().prim_point[:, :, 2].min(dim=1).values
+    print("max |lowest support z - clearance| after reset(): %.3e" % float((zmin - RANGES["clearance"]).abs().max()))
+    assert float((zmin - RANGES["clearance"]).abs().max()) <= 1e-6
+    D = env.engine_obs_dim // 2
+    assert bool((obs[:, D:] == 0).all()) and bool((obs[:, D - 4:D] == 0).all()), "delta words and feet words of the first observation"
+    assert bool((s.contact_mask & 0xFFFFFF == 0).all()) and bool((s.lambda_prev == 0).all())
+    assert bool((env.reset_randomization_count == 1).all())
+    yaw = 2 * torch.atan2(s.quat[:, 2], s.quat[:, 3])
+    assert float(yaw.abs().max()) > 2.0, "headings other than +x"
+    finished = 0
+    for t, a in enumerate(_actions(N, 12, 20)):
+        twin.set_states(env.get_states())
+        count = env.reset_randomization_count.clone()
+        o, r, d, info = env.step_inplace(a)
+        o2, r2, d2, _ = twin.step_inplace(a)
+        torch.cuda.synchronize()
+        assert not bool(info["nan_reset"].any()), t
+        assert torch.equal(d, d2) and torch.equal(r.view(torch.int32), r2.view(torch.int32)), t
+        done = d.bool()
+        assert torch.equal(env.reset_randomization_count, count + d.to(torch.int32)), t
+        assert torch.equal(o[~done].view(torch.int32), o2[~done].view(torch.int32)), t
+        assert torch.equal(env.get_states().bytes()[~done], twin.get_states().bytes()[~done]), t
+        if done.any():
+            assert bool((o[done][:, D:] == 0).all()), "first observation of the new episode"
+            z = env.get_kinematics().prim_point[:, :, 2].min(dim=1).values[done]
+            assert float((z - RANGES["clearance"]).abs().max()) <= 1e-6
+            assert _distinct(env.get_states().q[done].contiguous()) == int(done.sum())
+        finished += int(done.sum())
+    assert finished >= 2 * N                             # the time limit at steps 7 and 14, and whoever fell
+    # reset_masked: the selected envs draw again, the others keep their state
+    mask = (torch.arange(N, device=DEV) % 3 == 0)
+    before, count = env.get_states().clone(), env.reset_randomization_count.clone()
+    o = env.reset_masked(mask)
+    after = env.get_states()
+    assert torch.equal(after.bytes()[~mask], before.bytes()[~mask]) and _distinct(after.q[mask].contiguous()) == int(mask.sum())
+    assert torch.equal(env.reset_randomization_count, count + mask.to(torch.int32)) and bool((o[mask][:, D:] == 0).all())
+    env.close(); twin.close()
+
+
+# ---- 4: determinism
+def _run(env, acts):
+    out = [env.reset()]
+    for a in acts:
+        o, r, d, _ = env.step_inplace(a)
+        out += [o.clone(), r.clone().unsqueeze(-1), d.clone().float().unsqueeze(-1)]
+    out.append(env.get_states().data.clone())
+    return out
+
+
+def test_two_runs_and_two_shards(gpu_device, monkeypatch):
+    acts = _actions(130, 12, 10, seed=3)
+    runs = []
+    for _ in range(2):
+        env = _make("walk12_team", 130, monkeypatch, episode_length=4)
+        env.set_reset_randomization(RANGES)
+        runs.append(_run(env, acts))
+        env.close()
+    for x, y in zip(*runs):
+        assert torch.equal(x.view(torch.int32), y.view(torch.int32))
+    for s in (0, 1):
+        env = _make("walk12_team", 65, monkeypatch, off=65 * s, episode_length=4)
+        env.set_reset_randomization(RANGES)
+        part = _run(env, [a[65 * s:65 * (s + 1)].contiguous() for a in acts])
+        env.close()
+        for k, (x, y) in enumerate(zip(part, runs[0])):
+            assert torch.equal(x.view(torch.int32), y[65 * s:65 * (s + 1)].view(torch.int32)), (s, k)
+
+
+# ---- 5: guards, and off is off
+def test_refused_paths_and_off_is_off(gpu_device, monkeypatch):
+    from solorl_amd.ppo import Policy
+    from solorl_amd.ppo.fused import policy_params
+    from solorl_amd.vec_env import Box, make_vec_envs
+    N = 8
+    torch.manual_seed(3)
+    P = policy_params(Policy((76,), Box(-np.ones(12), np.ones(12)), None, {"hidden_size": 64}).to(DEV))
+    plain, env = _make("walk12_team", N, monkeypatch), _make("walk12_team", N, monkeypatch)
+    assert plain.step_act_supported(P) and plain.rollout_supported(P)
+    env.set_reset_randomization(dict(joint_pos=0.1), yaw=1.0)
+    assert env._rr.yaw == 1.0 and env.reset_randomization_count.dtype == torch.int32
+    assert not env.step_act_supported(P) and not env.rollout_supported(P)
+    plain.reset(); env.reset()
+    acts = torch.zeros(2, N, 12, device=DEV)
+    val, lp = torch.zeros(2, N, device=DEV), torch.zeros(2, N, device=DEV)
+    with pytest.raises(_native.SoloRLError, match="step_n.*reset randomization"):
+        env.step_n_inplace(acts)
+    with pytest.raises(_native.SoloRLError, match="step_n.*reset randomization"):
+        env.step_n(acts)
+    with pytest.raises(_native.SoloRLError, match="rollout_inplace.*reset randomization"):
+        env.rollout_inplace(acts, P, None, val, lp)
+    with pytest.raises(_native.SoloRLError, match="step_act_inplace.*reset randomization"):
+        env.step_act_inplace(acts[0], P, None, val[0], acts[1], lp[0])
+    with pytest.raises(ValueError, match="heading"):
+        env.set_reset_randomization(heading=1.0)
+    assert env._rr.yaw == 1.0                            # a refused call leaves it as it was
+    env.step_inplace(acts[0])
+    env.set_reset_randomization(yaw=2.0)
+    assert bool((env.reset_randomization_count == 0).all()), "every call zeroes the count"
+    env.set_reset_randomization(None)
+    assert env._rr is None and env._rr_states is None and env.reset_randomization_count is None
+    assert env.step_act_supported(P) and env.rollout_supported(P)
+    # off is off: from the same state, the env that set and cleared it steps like the one that never had it
+    env.set_states(plain.get_states())
+    for t, a in enumerate(_actions(N, 12, 10, seed=4)):
+        (o1, r1, d1, _), (o2, r2, d2, _) = plain.step_inplace(a), env.step_inplace(a)
+        assert torch.equal(o1.view(torch.int32), o2.view(torch.int32)) and torch.equal(r1.view(torch.int32), r2.view(torch.int32)) and torch.equal(d1, d2), t
+    assert torch.equal(plain.get_states().bytes(), env.get_states().bytes())
+    assert torch.equal(plain.reset().view(torch.int32), env.reset().view(torch.int32))
+    plain.close(); env.close()
+    config = dict(episode_length=10, solo12=True, task="walk", num_history_stack=1)
+    made = make_vec_envs(config, N, device=DEV, reset_randomization=dict(RANGES, place_on_ground=False))
+    assert made._rr.place_on_ground == 0 and made._rr.yaw == 3.14 and list(made._rr.joint_vel) == [1.0] * 12
+    with pytest.raises(ValueError, match="jointpos"):
+        make_vec_envs(config, N, device=DEV, reset_randomization=dict(jointpos=0.1))
+    made.close()
+
+
+# ---- 6: composition under capture
+def _composed(N, monkeypatch):
+    env = _make("walk12_team", N, monkeypatch, seed=9, episode_length=5)
+    env.set_termination(max_tilt_deg=50, contacts=["base"], min_steps=1)
+    env.set_obs_noise(dict(height=0.01, orientation=0.02, lin_vel=0.05, ang_vel=0.1, joint_pos=0.01, joint_vel=0.5))
+    env.set_reset_randomization(RANGES)
+    return env
+
+
+def test_three_captured_steps_equal_an_eager_twin(gpu_device, monkeypatch):
+    N = 130
+    A, B = _composed(N, monkeypatch), _composed(N, monkeypatch)
+    assert torch.equal(A.reset().view(torch.int32), B.reset().view(torch.int32))
+    acts = _actions(N, 12, 3 + 9, seed=21)
+    for a in acts[:3]:                                   # (a warm-up: every engine-owned buffer exists before the capture)
+        A.step_inplace(a); B.step_inplace(a)
+    act = [torch.zeros(N, 12, device=DEV) for _ in range(3)]
+    out = [(torch.zeros(N, A.obs_dim, device=DEV), torch.zeros(N, device=DEV), torch.zeros(N, dtype=torch.uint8, device=DEV)) for _ in range(3)]
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for k in range(3):
+            A.step_inplace(act[k], obs_out=out[k][0], rew_out=out[k][1], done_out=out[k][2])
+    seen = 0
+    for r in range(3):
+        for k in range(3):
+            act[k].copy_(acts[3 + 3 * r + k])
+        graph.replay()
+        for k in range(3):
+            ob, rb, db, _ = B.step_inplace(acts[3 + 3 * r + k])
+            torch.cuda.synchronize()
+            assert torch.equal(out[k][0].view(torch.int32), ob.view(torch.int32)) and torch.equal(out[k][1].view(torch.int32), rb.view(torch.int32)), (r, k)
+            assert torch.equal(out[k][2], db), (r, k)
+            seen += int(db.sum())
+        assert torch.equal(A.reset_randomization_count, B.reset_randomization_count) and torch.equal(A._noise_count, B._noise_count), r
+        assert torch.equal(A.get_states().bytes(), B.get_states().bytes()), r
+    assert seen >= N                                     # episodes ended, and were randomised, inside the replayed steps
+    A.close(); B.close()

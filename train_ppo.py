@@ -53,6 +53,10 @@ def add_channel_flags(p):
                    help="early termination rules checked on the state after every step: `base_height`, `max_tilt_deg`, `contacts` with "
                         "`contact_force_min`, `joint_limits`, `min_steps`, `terminal_reward`, e.g. configs/termination_walk12.yaml (default: "
                         "the engine's own endings only)")
+    p.add_argument("--reset-randomization", type=str, default=None, metavar="FILE.yaml",
+                   help="randomised initial states behind every reset: half-widths `joint_pos`, `joint_vel`, `lin_vel`, `ang_vel`, `yaw`, "
+                        "`roll`, `pitch`, and `place_on_ground` with `clearance`, e.g. configs/reset_walk12.yaml (default: the engine's own "
+                        "snapshots)")
     p.add_argument("--obs-noise", type=str, default=None, metavar="FILE.yaml",
                    help="uniform sensor noise on every observation: `groups:` (observation group -> half-width in physical units) and "
                         "`history:`, e.g. configs/noise_solo.yaml (default: clean observations)")
@@ -94,6 +98,18 @@ def load_termination(path, config):
         return rules
     except (ValueError, AttributeError, TypeError) as e:
         raise SystemExit("--termination %s: %s" % (path, e))
+
+
+def load_reset_randomization(path, config):
+    """--reset-randomization FILE.yaml -> its dict, with unknown keys and bad values refused by name before anything is built"""
+    from solorl_amd.config import config_from_dict, load_yaml
+    from solorl_amd.reset_random import make_reset_randomization, ranges_from_dict
+    try:
+        ranges = ranges_from_dict(load_yaml(path))
+        make_reset_randomization(config_from_dict(config), 0, 0, **ranges)
+        return ranges
+    except (ValueError, AttributeError, TypeError) as e:
+        raise SystemExit("--reset-randomization %s: %s" % (path, e))
 
 
 def get_ppo_args(argv=None):
@@ -170,6 +186,8 @@ def main(argv=None):
         args.commands = load_commands(args.commands)
     if args.termination is not None:
         args.termination = load_termination(args.termination, config)
+    if args.reset_randomization is not None:
+        args.reset_randomization = load_reset_randomization(args.reset_randomization, config)
     writer = None
     rank = int(os.environ.get("RANK", "0"))
     if args.logdir is not None:      # run directory named as training/train_ppo.py:64-72
