@@ -16,7 +16,7 @@ import torch
 from . import _native
 from ._native import Actuation, EnvActuator, DELAY_MAX
 from .config import SoloConfig, TASK_POINTGOAL
-from .rows import mask_arg
+from .rows import RowBatch, known_keys, mask_arg, tensor_arg
 
 MAX_OBS = 210                       # 42 words x (1 + 4 history levels): the widest observation row
 ROW_BYTES = C.sizeof(EnvActuator)
@@ -51,9 +51,7 @@ def noise_scales(cfg, groups, history=1.0):
     The noise is additive and the wrapped orientation is NOT re-wrapped: a noisy angle component may leave [0, 1)."""
     if not isinstance(cfg, SoloConfig):
         raise AssertionError("cfg must be a SoloConfig")
-    unknown = sorted(set(groups) - set(GROUPS))
-    if unknown:
-        raise ValueError("unknown observation noise group(s) %s (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(GROUPS)))
+    known_keys("observation noise group", groups, GROUPS)
     if "position" in groups and cfg.task != TASK_POINTGOAL:
         raise ValueError("observation noise group 'position' exists in the pointgoal observation only")
     level = np.zeros(cfg.state_dim, dtype=np.float64)
@@ -74,38 +72,16 @@ def scales_from_dict(cfg, d):
     if not isinstance(groups, dict):
         raise ValueError("an observation noise file needs a `groups:` mapping of group name -> half-width")
     history = d.pop("history", 1.0)
-    if d:
-        raise ValueError("unknown observation noise key(s) %s (known: groups, history)" % ", ".join(map(repr, sorted(d))))
+    known_keys("observation noise key", d, ("groups", "history"))
     return noise_scales(cfg, groups, history)
 
 
-class ActuatorMem:
+class ActuatorMem(RowBatch):
     """``data``: float32 ``[N, 64]`` (contiguous), one ``solorl_env_actuator`` row per env.  Views: ``buf [N,4,12]`` (level k = the raw
     action received k + 1 calls ago), ``gain [N,12]`` (float32) and ``latency [N]``, ``fill [N]``, ``episodes [N]`` (int32 views; episodes
     is the engine's uint32).  A zeroed row is an env that has drawn nothing yet: it draws at its first call."""
-
-    def __init__(self, num_envs=None, device=None, data=None):
-        if data is None:
-            data = torch.zeros((int(num_envs), ROW_WORDS), dtype=torch.float32, device=device)
-        if not (data.dtype == torch.float32 and data.dim() == 2 and data.shape[1] == ROW_WORDS and data.is_contiguous()):
-            raise AssertionError("ActuatorMem data must be a contiguous float32 [N, %d] tensor" % ROW_WORDS)
-        self.data = data
-        ints = data.view(torch.int32)
-        w = lambda name: getattr(EnvActuator, name).offset // 4
-        self.buf = data[:, w("buf"):w("buf") + DELAY_MAX * 12].unflatten(1, (DELAY_MAX, 12))
-        self.gain = data[:, w("gain"):w("gain") + 12]
-        self.latency, self.fill, self.episodes = ints[:, w("latency")], ints[:, w("fill")], ints[:, w("episodes")]
-
-    @property
-    def num_envs(self):
-        return self.data.shape[0]
-
-    def clone(self):
-        return ActuatorMem(data=self.data.clone())
-
-    def bytes(self):
-        """uint8 [N, 256] view: for bitwise comparisons"""
-        return self.data.view(torch.uint8)
+    MIRROR = EnvActuator
+    WORD = torch.float32
 
 
 def make_actuation(seed, env_id_offset, act_dim, delay=0, gain_range=0.0):
@@ -116,32 +92,25 @@ def make_actuation(seed, env_id_offset, act_dim, delay=0, gain_range=0.0):
     return Actuation(int(seed) & (2 ** 64 - 1), int(env_id_offset), int(act_dim), int(lo), int(hi), 0, float(gain_range))
 
 
-def _f32(name, x, shape):
-    if not (x.is_cuda and x.dtype == torch.float32 and tuple(x.shape) == tuple(shape) and x.is_contiguous()):
-        raise AssertionError("%s must be a contiguous float32 %s tensor on a GPU" % (name, list(shape)))
-    return C.c_void_p(x.data_ptr())
-
-
 def obs_noise(seed, env_id_offset, scale, count, obs, out=None, mask=None):
     """``solorl_obs_noise``: ``obs`` float32 [n, D] on a GPU (dense rows; its first element need not be 16-byte aligned), ``scale`` float32
     [D], ``count`` int32 [n] (the engine's uint32 words: the noise calls each env has received, advanced by one for every live row),
     ``out`` = where the noisy rows go (default: in place), ``mask`` a [n] torch.bool / torch.uint8 tensor (rows whose byte is 0 are
     neither read nor written and their count stays).  One launch on the current stream, no host synchronisation: capturable."""
-    if not (obs.is_cuda and obs.dim() == 2):
+    if not (isinstance(obs, torch.Tensor) and obs.dim() == 2):
+        raise AssertionError("obs must be a float32 [n, D] tensor, got %r" % (tuple(obs.shape) if isinstance(obs, torch.Tensor) else obs,))
+    dev = obs.device if obs.is_cuda or not isinstance(count, torch.Tensor) else count.device     # (obs alone on the host is a bad argument)
+    if dev.type != "cuda":
         raise _native.SoloRLError("obs_noise() needs observation rows [n, D] on a GPU (there is no CPU fallback)")
     n, D = obs.shape
     out = obs if out is None else out
-    po, pq = _f32("obs", obs, (n, D)), _f32("out", out, (n, D))
-    ps = _f32("scale", scale, (D,))
-    if not (count.is_cuda and count.dtype == torch.int32 and tuple(count.shape) == (n,) and count.is_contiguous()):
-        raise AssertionError("count must be a contiguous int32 [%d] tensor on the GPU" % n)
-    for x in (scale, count, out):
-        if x.device != obs.device:
-            raise AssertionError("every tensor must be on %s" % (obs.device,))
-    m, pm = mask_arg(mask, n, obs.device)
-    with torch.cuda.device(obs.device):
-        _native.check(_native.lib().solorl_obs_noise(int(seed) & (2 ** 64 - 1), int(env_id_offset), ps, pm, n, D, C.c_void_p(count.data_ptr()),
-                                                     po, pq, torch.cuda.current_device(), _native.stream(obs.device)))
+    po, pq = tensor_arg("obs", obs, ((n, D),), torch.float32, dev), tensor_arg("out", out, ((n, D),), torch.float32, dev)
+    ps = tensor_arg("scale", scale, ((D,),), torch.float32, dev)
+    pc = tensor_arg("count", count, ((n,),), torch.int32, dev)
+    m, pm = mask_arg(mask, n, dev)
+    with torch.cuda.device(dev):
+        _native.check(_native.lib().solorl_obs_noise(int(seed) & (2 ** 64 - 1), int(env_id_offset), ps, pm, n, D, pc,
+                                                     po, pq, torch.cuda.current_device(), _native.stream(dev)))
     return out
 
 
@@ -156,12 +125,11 @@ def actuate(params, mem, actions, out=None, restart=None):
     n = d.shape[0]
     if not d.is_cuda:
         raise _native.SoloRLError("actuate() needs its memory rows on a GPU (there is no CPU fallback)")
+    pa = tensor_arg("actions", actions, ((n, params.act_dim),), torch.float32, d.device)
     if out is None:
         out = torch.empty_like(actions)
-    pa, po = _f32("actions", actions, (n, params.act_dim)), _f32("out", out, (n, params.act_dim))
-    if actions.device != d.device or out.device != d.device:
-        raise AssertionError("every tensor must be on %s" % (d.device,))
-    r, pr = mask_arg(restart, n, d.device)
+    po = tensor_arg("out", out, ((n, params.act_dim),), torch.float32, d.device)
+    r, pr = mask_arg(restart, n, d.device, "restart")
     with torch.cuda.device(d.device):
         _native.check(_native.lib().solorl_actuate(C.byref(params), n, pr, C.c_void_p(d.data_ptr()), pa, po, torch.cuda.current_device(),
                                                    _native.stream(d.device)))

@@ -13,7 +13,7 @@ import torch
 
 from . import _native
 from ._native import CommandParams, EnvCommand
-from .rows import mask_arg
+from .rows import RowBatch, known_keys, mask_arg, tensor_arg
 
 MAX_OBS = 210                       # the widest observation row the call widens
 INTERVAL_MAX = 1 << 20
@@ -27,31 +27,11 @@ DEFAULTS = {"lin_vel_x": (0.0, 0.0), "lin_vel_y": (0.0, 0.0), "yaw_rate": (0.0, 
             "obs_scale": (1.0, 1.0, 1.0)}
 
 
-class CommandMem:
+class CommandMem(RowBatch):
     """``data``: float64 ``[N, 4]`` (contiguous), one ``solorl_env_command`` row per env.  Views: ``cmd [N, 3]`` (float64) and
     ``countdown [N]``, ``draws [N]`` (int32 views; draws is the engine's uint32).  A zeroed row is an env that has drawn nothing yet: it
     draws at its first call."""
-
-    def __init__(self, num_envs=None, device=None, data=None):
-        if data is None:
-            data = torch.zeros((int(num_envs), ROW_WORDS), dtype=torch.float64, device=device)
-        if not (data.dtype == torch.float64 and data.dim() == 2 and data.shape[1] == ROW_WORDS and data.is_contiguous()):
-            raise AssertionError("CommandMem data must be a contiguous float64 [N, %d] tensor" % ROW_WORDS)
-        self.data = data
-        ints = data.view(torch.int32)
-        self.cmd = data[:, EnvCommand.cmd.offset // 8:EnvCommand.cmd.offset // 8 + 3]
-        self.countdown, self.draws = ints[:, EnvCommand.countdown.offset // 4], ints[:, EnvCommand.draws.offset // 4]
-
-    @property
-    def num_envs(self):
-        return self.data.shape[0]
-
-    def clone(self):
-        return CommandMem(data=self.data.clone())
-
-    def bytes(self):
-        """uint8 [N, 32] view: for bitwise comparisons"""
-        return self.data.view(torch.uint8)
+    MIRROR = EnvCommand
 
 
 def _pair(name, v):
@@ -66,9 +46,7 @@ def make_params(seed, env_id_offset, obs_dim, **ranges):
     """``solorl_command_params`` from ``lin_vel_x``, ``lin_vel_y``, ``yaw_rate`` (each a [lo, hi] pair, or a number = a fixed value),
     ``interval`` (an int or a [lo, hi] pair of control steps between draws), ``zero_prob``, ``min_lin_norm`` and ``obs_scale`` (three
     factors, default 1).  Unknown names are refused by name; what is not named takes DEFAULTS."""
-    unknown = sorted(set(ranges) - set(KEYS))
-    if unknown:
-        raise ValueError("unknown command key(s) %s (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(KEYS)))
+    known_keys("command key", ranges, KEYS)
     r = dict(DEFAULTS, **ranges)
     p = CommandParams()
     p.seed, p.env_id_offset, p.obs_dim = int(seed) & (2 ** 64 - 1), int(env_id_offset), int(obs_dim)
@@ -101,19 +79,9 @@ def ranges_from_dict(d):
     """A command file's dict (configs/commands_walk12.yaml) -> the keyword arguments of make_params, unknown keys refused by name"""
     if not isinstance(d, dict):
         raise ValueError("a command file holds a mapping with the keys %s" % ", ".join(KEYS))
-    unknown = sorted(set(d) - set(KEYS))
-    if unknown:
-        raise ValueError("unknown command key(s) %s (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(KEYS)))
+    known_keys("command key", d, KEYS)
     make_params(0, 0, 1, **d)           # (the values are checked here, by the one place that knows them)
     return dict(d)
-
-
-def _ptr(name, x, shape, dtype, device):
-    if x is None:
-        return C.c_void_p(0)
-    if not (x.is_cuda and x.device == device and x.dtype == dtype and tuple(x.shape) == tuple(shape) and x.is_contiguous()):
-        raise AssertionError("%s must be a contiguous %s %s tensor on %s" % (name, str(dtype).replace("torch.", ""), list(shape), device))
-    return C.c_void_p(x.data_ptr())
 
 
 def commands(params, mem, obs=None, out=None, cmd_out=None, restart=None, mask=None):
@@ -132,9 +100,10 @@ def commands(params, mem, obs=None, out=None, cmd_out=None, restart=None, mask=N
         raise AssertionError("out without obs")
     if obs is not None and out is None:
         out = torch.empty((n, D + 3), dtype=torch.float32, device=d.device)
-    po, pq = _ptr("obs", obs, (n, D), torch.float32, d.device), _ptr("out", out, (n, D + 3), torch.float32, d.device)
-    pc = _ptr("cmd_out", cmd_out, (n, 3), torch.float64, d.device)
-    r, pr = mask_arg(restart, n, d.device)
+    po = tensor_arg("obs", obs, ((n, D),), torch.float32, d.device, optional=True)
+    pq = tensor_arg("out", out, ((n, D + 3),), torch.float32, d.device, optional=True)
+    pc = tensor_arg("cmd_out", cmd_out, ((n, 3),), torch.float64, d.device, optional=True)
+    r, pr = mask_arg(restart, n, d.device, "restart")
     m, pm = mask_arg(mask, n, d.device)
     with torch.cuda.device(d.device):
         _native.check(_native.lib().solorl_commands(C.byref(params), pm, pr, n, C.c_void_p(d.data_ptr()), po, pq, pc, torch.cuda.current_device(),

@@ -17,7 +17,7 @@ import torch
 from . import _native
 from ._native import ResetRandomization
 from .config import ROBOT_SOLO12, SoloConfig
-from .rows import StateBatch, mask_arg
+from .rows import known_keys, mask_arg, state_rows, tensor_arg
 
 ENVS_PER_WORKGROUP = 64     # RESET_ENVS of csrc/solorl_reset.hip
 KEYS = ("joint_pos", "joint_vel", "lin_vel", "ang_vel", "yaw", "roll", "pitch", "clearance", "place_on_ground")
@@ -41,9 +41,7 @@ def make_reset_randomization(cfg, seed, id0, **ranges):
       ``place_on_ground`` (default True) with ``clearance`` [m] (default 0): the base height is changed until the lowest support point
       of the robot's collision primitives lies ``clearance`` above z = 0.
     Everything defaults to 0 (an exact no-op for that member).  Unknown keys are refused by name."""
-    unknown = sorted(set(ranges) - set(KEYS))
-    if unknown:
-        raise ValueError("unknown reset randomization key(s) %s (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(KEYS)))
+    known_keys("reset randomization key", ranges, KEYS)
     if not isinstance(cfg, SoloConfig):
         raise AssertionError("cfg must be a SoloConfig")
     nq = 12 if cfg.robot == ROBOT_SOLO12 else 8
@@ -70,9 +68,7 @@ def ranges_from_dict(d):
     refused by name"""
     if not isinstance(d, dict):
         raise ValueError("a reset randomization file holds a mapping with the keys %s" % ", ".join(KEYS))
-    unknown = sorted(set(d) - set(KEYS))
-    if unknown:
-        raise ValueError("unknown reset randomization key(s) %s (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(KEYS)))
+    known_keys("reset randomization key", d, KEYS)
     return dict(d)
 
 
@@ -80,19 +76,12 @@ def randomize_reset(cfg, params, states, count, mask=None):
     """``solorl_randomize_reset`` on the rows of ``states`` (a StateBatch on a GPU), in place: ``count`` int32 [N] (uint32 words: each
     selected env's episode index, advanced by one), ``mask`` a [N] torch.bool / torch.uint8 tensor (rows whose byte is 0 and their
     count are neither read nor written).  -> ``states``.  One launch on the current stream, no host synchronisation: capturable."""
-    if not isinstance(cfg, SoloConfig) or not isinstance(params, ResetRandomization):
-        raise AssertionError("cfg must be a SoloConfig and params a ResetRandomization (make_reset_randomization)")
-    if not isinstance(states, StateBatch):
-        raise AssertionError("states must be a StateBatch")
-    d = states.data
-    n = d.shape[0]
-    if not d.is_cuda:
-        raise _native.SoloRLError("randomize_reset() needs state rows on a GPU (there is no CPU fallback)")
-    if not (isinstance(count, torch.Tensor) and count.is_cuda and count.device == d.device and count.dtype == torch.int32 and count.is_contiguous()
-            and tuple(count.shape) == (n,)):
-        raise AssertionError("count must be a contiguous int32 [%d] tensor on %s" % (n, d.device))
-    m, pm = mask_arg(mask, n, d.device)
-    with torch.cuda.device(d.device):
-        _native.check(_native.lib().solorl_randomize_reset(C.byref(cfg), C.byref(params), C.c_void_p(d.data_ptr()), pm, C.c_void_p(count.data_ptr()), n,
-                                                           torch.cuda.current_device(), _native.stream(d.device)))
+    if not isinstance(params, ResetRandomization):
+        raise AssertionError("params must be a ResetRandomization (make_reset_randomization)")
+    d, n, dev = state_rows("randomize_reset", cfg, states)
+    pc = tensor_arg("count", count, ((n,),), torch.int32, dev)
+    m, pm = mask_arg(mask, n, dev)
+    with torch.cuda.device(dev):
+        _native.check(_native.lib().solorl_randomize_reset(C.byref(cfg), C.byref(params), C.c_void_p(d.data_ptr()), pm, pc, n,
+                                                           torch.cuda.current_device(), _native.stream(dev)))
     return states

@@ -1,9 +1,14 @@
 """Batches of rows and the calls that turn state rows into derived rows (include/solorl.h solorl_kinematics, solorl_dynamics).
 
-A batch is ONE float64 ``[N, sizeof(struct) / 8]`` tensor, row i = env i, with every member of the C struct as a named view of it.
-``RowBatch`` is that, for any ctypes mirror; ``StateBatch`` is the batch of ``solorl_env_state`` (solorl_amd/state.py describes its
-member groups), ``KinBatch`` and ``DynBatch`` (kinematics.py, dyn_tensors.py) the two derived ones.  Every offset and shape is taken
-from the mirrors; none is written down.  ``call_rows`` is the one call behind ``kinematics()`` and ``dynamics()``.
+A batch is ONE ``[N, sizeof(struct) / word size]`` tensor of float64 (or float32) words, row i = env i, with every member of the C struct as
+a named view of it.  ``RowBatch`` is that, for any ctypes mirror; ``StateBatch`` is the batch of ``solorl_env_state`` (solorl_amd/state.py
+describes its member groups), ``KinBatch`` and ``DynBatch`` (kinematics.py, dyn_tensors.py) the two derived ones, ``ShapeMem``,
+``CommandMem`` and ``ActuatorMem`` (shaping.py, command.py, channel.py) the per-env memories.  Every offset and shape is taken from the
+mirrors; none is written down.  ``call_rows`` is the one call behind ``kinematics()`` and ``dynamics()``.
+
+What every wrapper of a handle-free entry point shares is here too: ``tensor_arg`` (the one check of an argument that goes to the C ABI as
+a raw pointer), ``mask_arg``, ``state_rows`` (the front matter of a call on state rows) and ``known_keys`` (the one refusal of an unknown
+key).
 """
 import ctypes as C
 import functools
@@ -23,34 +28,63 @@ def _shape(ctype):
     return tuple(s), ctype
 
 
+_INTS = (C.c_int32, C.c_uint32)
+
+
 @functools.lru_cache(maxsize=None)
-def members_of(struct, int32=False):
-    """member -> (byte offset, shape per row) of a ctypes mirror made of doubles; with ``int32`` its members may be int32 too and
-    the values are (byte offset, shape per row, is int32)"""
+def members_of(struct, int32=False, word=C.c_double):
+    """member -> (byte offset, shape per row) of a ctypes mirror made of ``word`` members; with ``int32`` its members may be (u)int32 too
+    and the values are (byte offset, shape per row, is int32)"""
     out = {}
     for name, ctype in struct._fields_:
         s, base = _shape(ctype)
-        assert base is C.c_double or (int32 and base is C.c_int32), name
-        out[name] = (getattr(struct, name).offset, s) + ((base is C.c_int32,) if int32 else ())
+        assert base is word or (int32 and base in _INTS), name
+        out[name] = (getattr(struct, name).offset, s) + ((base in _INTS,) if int32 else ())
     return out
 
 
+def tensor_arg(name, x, shapes, dtype, device, optional=False):
+    """The one check of an argument the C ABI takes as a raw pointer: ``x`` must be a tensor on ``device`` (same index), of ``dtype``,
+    contiguous, of one of ``shapes`` -> its pointer; with ``optional``, None -> a null pointer"""
+    if x is None and optional:
+        return C.c_void_p(0)
+    if not (isinstance(x, torch.Tensor) and x.device == device and x.dtype == dtype and x.is_contiguous() and tuple(x.shape) in shapes):
+        got = ("%s %s%s on %s" % (x.dtype, tuple(x.shape), "" if x.is_contiguous() else " (not contiguous)", x.device)
+               if isinstance(x, torch.Tensor) else "None" if x is None else "a %s" % type(x).__name__)
+        raise AssertionError("%s must be a contiguous %s %s tensor on %s, got %s" % (
+            name, str(dtype).replace("torch.", ""), " or ".join(str(list(sh)) for sh in shapes), device, got))
+    return C.c_void_p(x.data_ptr())
+
+
+def known_keys(what, given, known):
+    """Refuses by name what ``given`` holds beyond ``known``"""
+    unknown = sorted(set(given) - set(known))
+    if unknown:
+        raise ValueError("unknown %s(s) %s (known: %s)" % (what, ", ".join(map(repr, unknown)), ", ".join(known)))
+
+
 class RowBatch:
-    """``data``: float64 ``[N, sizeof(MIRROR) / 8]`` (contiguous).  Attributes named after the float64 members of the ctypes mirror
-    ``MIRROR`` (set by the subclass) are views of it; writing through a view writes the row array."""
+    """``data``: ``[N, sizeof(MIRROR) / word size]`` of ``WORD`` (float64 or float32, contiguous).  Attributes named after the members of
+    the ctypes mirror ``MIRROR`` (both set by the subclass) are views of it -- its (u)int32 members as int32 views; writing through a view
+    writes the row array."""
     MIRROR = None
+    WORD = torch.float64
 
     def __init__(self, num_envs=None, device=None, data=None):
-        words = C.sizeof(self.MIRROR) // 8
+        size, ctype = (8, C.c_double) if self.WORD == torch.float64 else (4, C.c_float)
+        words = C.sizeof(self.MIRROR) // size
         if data is None:
-            data = torch.zeros((int(num_envs), words), dtype=torch.float64, device=device)
-        if not (data.dtype == torch.float64 and data.dim() == 2 and data.shape[1] == words and data.is_contiguous()):
-            raise AssertionError("%s data must be a contiguous float64 [N, %d] tensor" % (type(self).__name__, words))
+            data = torch.zeros((int(num_envs), words), dtype=self.WORD, device=device)
+        if not (data.dtype == self.WORD and data.dim() == 2 and data.shape[1] == words and data.is_contiguous()):
+            raise AssertionError("%s data must be a contiguous %s [N, %d] tensor" % (type(self).__name__, str(self.WORD).replace("torch.", ""), words))
         self.data = data
-        for name, (off, shape, is_int) in members_of(self.MIRROR, int32=True).items():
-            if not is_int:
+        ints = data.view(torch.int32)
+        for name, (off, shape, is_int) in members_of(self.MIRROR, True, ctype).items():
+            if is_int:
+                setattr(self, name, ints[:, off // 4])
+            else:
                 n = int(np.prod(shape)) if shape else 1
-                v = data[:, off // 8: off // 8 + n]
+                v = data[:, off // size: off // size + n]
                 setattr(self, name, v.unflatten(1, shape) if len(shape) > 1 else (v if shape else v[:, 0]))
 
     @property
@@ -76,13 +110,6 @@ class StateBatch(RowBatch):
     ``timestep [N]``, ``need_reset``, ``contact_mask``, ``rng_counter`` (int32).  Writing through a view writes the row array."""
     MIRROR = EnvState
 
-    def __init__(self, num_envs=None, device=None, data=None):
-        super().__init__(num_envs, device, data)
-        ints = self.data.view(torch.int32)                 # [N, 2 * ROW_WORDS]
-        for name, (off, _, is_int) in members_of(EnvState, int32=True).items():
-            if is_int:
-                setattr(self, name, ints[:, off // 4])
-
     def env_state(self, i):
         """Row i as a host ``EnvState`` (what the oracle's and the engine's per-env ``set_state`` take)."""
         row = self.data[int(i)].detach().cpu().contiguous().view(torch.uint8).numpy()
@@ -98,28 +125,33 @@ class StateBatch(RowBatch):
         return cls(data=t.view(torch.float64))
 
 
-def mask_arg(mask, n, device):
+def mask_arg(mask, n, device, name="mask"):
     """None, or a [n] torch.bool / torch.uint8 tensor on ``device`` -> (tensor kept alive for the call, pointer)"""
     if mask is None:
         return None, C.c_void_p(0)
     if not (mask.is_cuda and mask.device == device and mask.dtype in (torch.bool, torch.uint8) and mask.is_contiguous()
             and tuple(mask.shape) == (n,)):
-        raise AssertionError("mask must be a contiguous torch.bool or torch.uint8 [%d] tensor on %s" % (n, device))
+        raise AssertionError("%s must be a contiguous torch.bool or torch.uint8 [%d] tensor on %s" % (name, n, device))
     m = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
     return m, C.c_void_p(m.data_ptr())
 
 
-def call_rows(entry, cfg, states, batch_cls, mask=None, out=None):
-    """``solorl_<entry>`` on the rows of ``states`` (a StateBatch on a GPU) -> ``batch_cls`` on the same device: one kernel launch on
-    the current stream, no host synchronisation."""
+def state_rows(fn, cfg, states):
+    """The front matter of a row query ``fn``: ``cfg`` a SoloConfig, ``states`` a StateBatch on a GPU -> (its data, rows, device)"""
     if not isinstance(cfg, SoloConfig):
         raise AssertionError("cfg must be a SoloConfig")
     if not isinstance(states, StateBatch):
         raise AssertionError("states must be a StateBatch")
     d = states.data
-    n = d.shape[0]
     if not d.is_cuda:
-        raise _native.SoloRLError("%s() needs state rows on a GPU (there is no CPU fallback)" % entry)
+        raise _native.SoloRLError("%s() needs state rows on a GPU (there is no CPU fallback)" % fn)
+    return d, d.shape[0], d.device
+
+
+def call_rows(entry, cfg, states, batch_cls, mask=None, out=None):
+    """``solorl_<entry>`` on the rows of ``states`` (a StateBatch on a GPU) -> ``batch_cls`` on the same device: one kernel launch on
+    the current stream, no host synchronisation."""
+    d, n, _ = state_rows(entry, cfg, states)
     if out is None:
         out = batch_cls(n, d.device)
     if not (isinstance(out, batch_cls) and out.data.device == d.device and out.data.shape[0] == n):

@@ -11,8 +11,7 @@ import ctypes as C
 import torch
 
 from . import _native
-from .config import SoloConfig
-from .rows import RowBatch, StateBatch, mask_arg, members_of
+from .rows import RowBatch, known_keys, mask_arg, members_of, state_rows, tensor_arg
 
 TERMS = ("lin_vel_z", "ang_vel_xy", "orientation", "base_height", "torques", "joint_vel", "joint_acc", "action_rate", "power",
          "foot_slip", "foot_clearance", "foot_force", "feet_air_time", "collision", "tracking_lin_vel", "tracking_yaw_rate")
@@ -47,12 +46,8 @@ PARAM_DEFAULTS = {"base_height_target": 0.24, "foot_clearance_target": 0.06, "fo
 def make_params(weights, **params):
     """``weights``: dict term name -> weight (terms not named are off); ``params``: the members of solorl_shape_params other than the
     weights (PARAM_DEFAULTS).  Unknown names are refused by name."""
-    unknown = sorted(set(weights) - set(TERMS))
-    if unknown:
-        raise ValueError("unknown reward shaping term(s) %s (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(TERMS)))
-    unknown = sorted(set(params) - set(PARAM_DEFAULTS))
-    if unknown:
-        raise ValueError("unknown reward shaping parameter(s) %s (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(PARAM_DEFAULTS)))
+    known_keys("reward shaping term", weights, TERMS)
+    known_keys("reward shaping parameter", params, PARAM_DEFAULTS)
     p = ShapeParams()
     for k, name in enumerate(TERMS):
         p.weight[k] = float(weights.get(name, 0.0))
@@ -80,22 +75,6 @@ class ShapeMem(RowBatch):
     an episode."""
     MIRROR = EnvShape
 
-    def __init__(self, num_envs=None, device=None, data=None):
-        super().__init__(num_envs, device, data)
-        ints = self.data.view(torch.int32)
-        for name, (off, _, is_int) in MEMBERS.items():
-            if is_int:
-                setattr(self, name, ints[:, off // 4])
-
-
-def _ptr(name, x, n, shapes, dtype):
-    if x is None:
-        return C.c_void_p(0)
-    if not (x.is_cuda and x.dtype == dtype and x.is_contiguous() and tuple(x.shape) in shapes):
-        raise AssertionError("%s must be a contiguous %s %s tensor on the states' device" % (name, str(dtype).replace("torch.", ""),
-                                                                                         " or ".join(str(list(s)) for s in shapes)))
-    return C.c_void_p(x.data_ptr())
-
 
 def shape_reward(cfg, params, states, actions, done, mem, reward, terms_out=None, ep_out=None, mask=None, commands=None):
     """``solorl_shape_reward`` on the rows of ``states`` (a StateBatch on a GPU: the state AFTER the step): ``actions`` float32 [N, A] (the
@@ -105,25 +84,17 @@ def shape_reward(cfg, params, states, actions, done, mem, reward, terms_out=None
     ``commands`` a command.CommandMem of N rows or None: with rows the two tracking terms of env i compare it against its own command
     (``solorl_shape_reward_cmd``), without them against the one command of ``params``.  One launch on the current stream, no host
     synchronisation: capturable."""
-    if not isinstance(cfg, SoloConfig) or not isinstance(params, ShapeParams):
-        raise AssertionError("cfg must be a SoloConfig and params a ShapeParams")
-    if not isinstance(states, StateBatch) or not isinstance(mem, ShapeMem):
-        raise AssertionError("states must be a StateBatch and mem a ShapeMem")
-    d = states.data
-    n = d.shape[0]
-    if not d.is_cuda:
-        raise _native.SoloRLError("shape_reward() needs state rows on a GPU (there is no CPU fallback)")
-    if not (mem.data.device == d.device and mem.data.shape[0] == n):
-        raise AssertionError("mem must hold %d rows on %s" % (n, d.device))
-    for x in (actions, done, reward, terms_out, ep_out):
-        if x is not None and x.device != d.device:
-            raise AssertionError("every tensor must be on %s" % (d.device,))
-    pa = _ptr("actions", actions, n, ((n, cfg.n_joints),), torch.float32)
-    pd = _ptr("done", done, n, ((n,),), torch.uint8)
-    pr = _ptr("reward", reward, n, ((n,), (n, 1)), torch.float32)
-    pt = _ptr("terms_out", terms_out, n, ((n, SHAPE_TERMS),), torch.float64)
-    pe = _ptr("ep_out", ep_out, n, ((EP_FIELDS, n),), torch.float64)
-    m, pm = mask_arg(mask, n, d.device)
+    if not isinstance(params, ShapeParams) or not isinstance(mem, ShapeMem):
+        raise AssertionError("params must be a ShapeParams and mem a ShapeMem")
+    d, n, dev = state_rows("shape_reward", cfg, states)
+    if not (mem.data.device == dev and mem.data.shape[0] == n):
+        raise AssertionError("mem must hold %d rows on %s" % (n, dev))
+    pa = tensor_arg("actions", actions, ((n, cfg.n_joints),), torch.float32, dev, optional=True)
+    pd = tensor_arg("done", done, ((n,),), torch.uint8, dev, optional=True)
+    pr = tensor_arg("reward", reward, ((n,), (n, 1)), torch.float32, dev, optional=True)
+    pt = tensor_arg("terms_out", terms_out, ((n, SHAPE_TERMS),), torch.float64, dev, optional=True)
+    pe = tensor_arg("ep_out", ep_out, ((EP_FIELDS, n),), torch.float64, dev, optional=True)
+    m, pm = mask_arg(mask, n, dev)
     args = (C.byref(cfg), C.byref(params), C.c_void_p(d.data_ptr()), pm, n, pa, pd, C.c_void_p(mem.data.data_ptr()), pr, pt, pe)
     with torch.cuda.device(d.device):
         tail = (torch.cuda.current_device(), _native.stream(d.device))

@@ -16,7 +16,7 @@ import torch
 from . import _native
 from ._native import TERM_RULES, Termination
 from .config import ROBOT_SOLO12, InfoSoA, SoloConfig
-from .rows import StateBatch, mask_arg
+from .rows import known_keys, mask_arg, state_rows, tensor_arg
 
 RULES = ("height", "tilt", "contact", "joint")      # bit k of fired_out is RULES[k]: SOLORL_TERM_HEIGHT, _TILT, _CONTACT, _JOINT
 HEIGHT, TILT, CONTACT, JOINT = 1, 2, 4, 8
@@ -41,9 +41,7 @@ def make_termination(robot, **rules):
       ``joint_limits``: one ``[lo, hi]`` pair [rad] for every joint, or one pair per joint;
     and ``min_steps`` (default 0: no rule fires before an episode's step of that number), ``terminal_reward`` (default -10, the
     engine's own).  Unknown keys are refused by name; so is a call that enables no rule."""
-    unknown = sorted(set(rules) - set(KEYS))
-    if unknown:
-        raise ValueError("unknown termination key(s) %s (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(KEYS)))
+    known_keys("termination key", rules, KEYS)
     r, nq, nprims = _robot(robot)
     p = Termination()
     if rules.get("base_height") is not None:
@@ -107,19 +105,8 @@ def rules_from_dict(d):
     by name"""
     if not isinstance(d, dict):
         raise ValueError("a termination file holds a mapping with the keys %s" % ", ".join(KEYS))
-    unknown = sorted(set(d) - set(KEYS))
-    if unknown:
-        raise ValueError("unknown termination key(s) %s (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(KEYS)))
+    known_keys("termination key", d, KEYS)
     return dict(d)
-
-
-def _ptr(name, x, shapes, dtype, device):
-    if x is None:
-        return C.c_void_p(0)
-    if not (x.is_cuda and x.device == device and x.dtype == dtype and x.is_contiguous() and tuple(x.shape) in shapes):
-        raise AssertionError("%s must be a contiguous %s %s tensor on %s" % (name, str(dtype).replace("torch.", ""),
-                                                                            " or ".join(str(list(s)) for s in shapes), device))
-    return C.c_void_p(x.data_ptr())
 
 
 def terminate(cfg, params, states, done, reward, fired_out, info=None, term_stats=None, mask=None):
@@ -128,25 +115,18 @@ def terminate(cfg, params, states, done, reward, fired_out, info=None, term_stat
     ``info`` an InfoSoA of that step's arrays or None, ``term_stats`` float32 [5, N] or None (accumulated), ``mask`` a [N] torch.bool /
     torch.uint8 tensor (rows whose byte is 0 are neither read nor written).  -> ``fired_out``.  One launch on the current stream, no
     host synchronisation: capturable."""
-    if not isinstance(cfg, SoloConfig) or not isinstance(params, Termination):
-        raise AssertionError("cfg must be a SoloConfig and params a Termination (make_termination)")
-    if not isinstance(states, StateBatch):
-        raise AssertionError("states must be a StateBatch")
+    if not isinstance(params, Termination):
+        raise AssertionError("params must be a Termination (make_termination)")
     if info is not None and not isinstance(info, InfoSoA):
         raise AssertionError("info must be an InfoSoA or None")
-    d = states.data
-    n = d.shape[0]
-    if not d.is_cuda:
-        raise _native.SoloRLError("terminate() needs state rows on a GPU (there is no CPU fallback)")
-    if done is None or reward is None or fired_out is None:
-        raise AssertionError("done, reward and fired_out are required")
-    pd = _ptr("done", done, ((n,),), torch.uint8, d.device)
-    pr = _ptr("reward", reward, ((n,), (n, 1)), torch.float32, d.device)
-    pf = _ptr("fired_out", fired_out, ((n,),), torch.uint8, d.device)
-    ps = _ptr("term_stats", term_stats, ((STAT_FIELDS, n),), torch.float32, d.device)
-    m, pm = mask_arg(mask, n, d.device)
-    with torch.cuda.device(d.device):
+    d, n, dev = state_rows("terminate", cfg, states)
+    pd = tensor_arg("done", done, ((n,),), torch.uint8, dev)
+    pr = tensor_arg("reward", reward, ((n,), (n, 1)), torch.float32, dev)
+    pf = tensor_arg("fired_out", fired_out, ((n,),), torch.uint8, dev)
+    ps = tensor_arg("term_stats", term_stats, ((STAT_FIELDS, n),), torch.float32, dev, optional=True)
+    m, pm = mask_arg(mask, n, dev)
+    with torch.cuda.device(dev):
         _native.check(_native.lib().solorl_terminate(C.byref(cfg), C.byref(params), C.c_void_p(d.data_ptr()), pm, n, pd, pr, pf,
                                                      None if info is None else C.byref(info), ps, torch.cuda.current_device(),
-                                                     _native.stream(d.device)))
+                                                     _native.stream(dev)))
     return fired_out

@@ -43,10 +43,30 @@ import torch
 from . import _native
 from .config import SoloConfig, EnvState, InfoSoA, config_from_dict, EPSTAT_FIELDS, EPSTAT_NAMES
 from .normalize import RunningMeanStd, VecNormalizer
-from .rows import mask_arg
+from .rows import mask_arg, tensor_arg
 from .state import StateBatch, field_bits, SF_POSE, SF_VEL, SF_JOINT_POS, SF_JOINT_VEL, SF_CONTACT
 
 _RR_FIELDS = SF_POSE | SF_VEL | SF_JOINT_POS | SF_JOINT_VEL | SF_CONTACT      # what solorl_randomize_reset may change of a row
+
+# The optional stages of a control step, in the order their refusals are tried: (name of the stage's ``_no_<name>`` guard, is it set on
+# this env, the message's phrase, what K steps in one launch (step_n*, rollout_inplace) cannot take between the steps -- None: the stage
+# does not bar them -- with the call that switches it off, what the policy inside the step kernel (step_act_inplace, rollout_inplace)
+# would do wrong with it -- None: it does not bar the policy tail).  The guards, step_act_supported() and rollout_supported() read this
+# table and nothing else; _before_step / _after_step hold the order the stages run in.
+_STAGES = (
+    ("norm_obs", lambda e: e._norm_obs, "on an env with norm_obs", None, None, "read raw observations"),
+    ("kicks", lambda e: e.last_kick is not None, "with a perturbation set", "kicks", "set_perturbation(None)", None),
+    ("shaping", lambda e: e._shape_params is not None, "with reward shaping set", "the shaped terms", "set_reward_shaping(None)", None),
+    ("channel", lambda e: e._noise_scale is not None, "with observation noise set", "the noise launch", "set_obs_noise(None)",
+     "read clean observations"),
+    ("channel", lambda e: e._act is not None, "with actuation set", "the actuation launch", "set_actuation(None)", None),
+    ("commands", lambda e: e._cmd is not None, "with velocity commands", "the command launch", None,
+     "read the engine's rows without the command words"),
+    ("termination", lambda e: e._term is not None, "with a termination set", "the termination launch", "set_termination(None)",
+     "act on the observation of an env that is about to be reset"),
+    ("reset_randomization", lambda e: e._rr is not None, "with a reset randomization set", "its launches behind a reset",
+     "set_reset_randomization(None)", "act on the observation of the un-randomised reset"),
+)
 
 
 class Box:
@@ -258,29 +278,29 @@ class SoloVecEnv:
         x = obs.detach().to(device=self.device, dtype=torch.float32).contiguous()
         return self._norm.obs(x, 1, update, out=torch.empty_like(x))
 
-    def _normalize(self, o, r, d, rows):
-        """The wrapper's half of a step (running_mean_std.py:96-107) on the `rows` rows the engine has just written, in place."""
-        if self._norm_obs:
+    def _normalize(self, o, r, d, rows, obs=True):
+        """The wrapper's half of a step (running_mean_std.py:96-107) on the `rows` rows the engine has just written, in place
+        (``obs=False``: the rewards only)."""
+        if self._norm_obs and obs:
             self._norm.obs(o, rows, self.training)
         if self._norm_ret:
             self._norm.rewards(r, d, rows, self.training)
 
+    def _refuse(self, name, k_step=False, tail=False, guard=None):
+        """Raises for the first stage of _STAGES (of those with guard name ``guard``, if given) that is set on this env and bars ``name``:
+        a launch of K steps (``k_step``) or one with the policy inside the step kernel (``tail``)"""
+        for g, is_set, phrase, between, off, policy in _STAGES:
+            if guard not in (None, g) or not is_set(self):
+                continue
+            if tail and policy is not None:
+                raise _native.SoloRLError("%s %s: the policy inside the step kernel would %s (step_act_supported() / rollout_supported() "
+                                          "are False)" % (name, phrase, policy))
+            if k_step and between is not None:
+                raise _native.SoloRLError("%s %s: K steps in one launch cannot take %s between the steps (rollout_supported() is False; "
+                                          "step one at a time%s)" % (name, phrase, between, "" if off is None else ", or " + off))
+
     def _no_policy_tail(self, name):
-        if self._norm_obs:
-            raise _native.SoloRLError("%s on an env with norm_obs: the policy inside the step kernel would read raw observations "
-                                      "(step_act_supported() / rollout_supported() are False)" % name)
-        if self._noise_scale is not None:
-            raise _native.SoloRLError("%s with observation noise set: the policy inside the step kernel would read clean observations "
-                                      "(step_act_supported() / rollout_supported() are False)" % name)
-        if self._cmd is not None:
-            raise _native.SoloRLError("%s with velocity commands: the policy inside the step kernel would read the engine's rows without the "
-                                      "command words (step_act_supported() / rollout_supported() are False)" % name)
-        if self._term is not None:
-            raise _native.SoloRLError("%s with a termination set: the policy inside the step kernel would act on the observation of an env "
-                                      "that is about to be reset (step_act_supported() / rollout_supported() are False)" % name)
-        if self._rr is not None:
-            raise _native.SoloRLError("%s with a reset randomization set: the policy inside the step kernel would act on the observation of the "
-                                      "un-randomised reset (step_act_supported() / rollout_supported() are False)" % name)
+        self._refuse(name, tail=True)
 
     def _stream(self):
         return _native.stream(self.device)
@@ -339,11 +359,6 @@ class SoloVecEnv:
         if self.last_kick is not None:
             self.perturb()
 
-    def _no_kicks(self, name):
-        if self.last_kick is not None:
-            raise _native.SoloRLError("%s with a perturbation set: K steps in one launch cannot take kicks between the steps "
-                                      "(rollout_supported() is False; step one at a time, or set_perturbation(None))" % name)
-
     # ---- shaped reward terms (include/solorl.h solorl_shape_reward; shaping.py)
     def set_reward_shaping(self, weights, **params):
         """Adds the shaped terms named in ``weights`` (dict term name -> weight, shaping.TERMS; the table is in include/solorl.h) to every
@@ -384,11 +399,6 @@ class SoloVecEnv:
                 rows.tau[:, :self.act_dim].copy_(self._tau)
             shape_reward(self.cfg, self._shape_params, rows, actions, done, self._shape_mem, rew,
                          terms_out=self.last_shaping_terms, ep_out=self._shape_ep, commands=self._cmd_mem)
-
-    def _no_shaping(self, name):
-        if self._shape_params is not None:
-            raise _native.SoloRLError("%s with reward shaping set: K steps in one launch cannot take the shaped terms between the steps "
-                                      "(rollout_supported() is False; step one at a time, or set_reward_shaping(None))" % name)
 
     def shaping_stats(self, reset=True):
         """Means over the episodes finished since the last call of each term's weighted sum over the episode, ``sr/<name>``, and their
@@ -450,11 +460,6 @@ class SoloVecEnv:
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_reset_masked(self._h, C.c_void_p(self.last_termination.data_ptr()), C.c_void_p(e.data_ptr()), self._stream()))
         return rows
-
-    def _no_termination(self, name):
-        if self._term is not None:
-            raise _native.SoloRLError("%s with a termination set: K steps in one launch cannot take the termination launch between the steps "
-                                      "(rollout_supported() is False; step one at a time, or set_termination(None))" % name)
 
     def termination_stats(self, reset=True):
         """``term/episodes``: the episodes finished since the last call, by any cause; ``term/early``: the share of them that a rule
@@ -519,11 +524,6 @@ class SoloVecEnv:
         self.set_states(rows, mask, _RR_FIELDS)
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_restart_history(self._h, C.c_void_p(mask.data_ptr()), C.c_void_p(e.data_ptr()), self._stream()))
-
-    def _no_reset_randomization(self, name):
-        if self._rr is not None:
-            raise _native.SoloRLError("%s with a reset randomization set: K steps in one launch cannot take its launches behind a reset between "
-                                      "the steps (rollout_supported() is False; step one at a time, or set_reset_randomization(None))" % name)
 
     # ---- observation noise and actuation (include/solorl.h solorl_obs_noise / solorl_actuate; channel.py)
     def set_obs_noise(self, scales):
@@ -633,17 +633,6 @@ class SoloVecEnv:
         scale = torch.tensor(list(self._cmd.obs_scale), dtype=torch.float64, device=self.device)
         return (self._cmd_mem.cmd * scale).to(torch.float32)
 
-    def _no_commands(self, name):
-        if self._cmd is not None:
-            raise _native.SoloRLError("%s with velocity commands: K steps in one launch cannot take the command launch between the steps "
-                                      "(rollout_supported() is False; step one at a time)" % name)
-
-    def _no_channel(self, name):
-        if self._noise_scale is not None or self._act is not None:
-            raise _native.SoloRLError("%s with observation noise or actuation set: K steps in one launch cannot take their launches between "
-                                      "the steps (rollout_supported() is False; step one at a time, or set_obs_noise(None) / "
-                                      "set_actuation(None))" % name)
-
     def reset(self):
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_reset(self._h, C.c_void_p(self._obs_engine.data_ptr()), self._stream()))
@@ -666,31 +655,34 @@ class SoloVecEnv:
         if actions.shape != (self.nenvs, self.act_dim):
             raise AssertionError("actions must be [%d, %d]" % (self.nenvs, self.act_dim))   # solo.py:226
         a = actions.detach().to(device=self.device, dtype=torch.float32).contiguous()
-        self._steps_issued += 1
-        applied = self._actuate(a)
-        self._kick()
-        with torch.cuda.device(self.device):
-            _native.check(self.L.solorl_step(self._h, C.c_void_p(applied.data_ptr()), C.c_void_p(self._obs_engine.data_ptr()),
-                                             C.c_void_p(self._rew.data_ptr()), C.c_void_p(self._done.data_ptr()),
-                                             C.byref(self._info_c), self._stream()))
-        rows = self._terminate(self._obs_engine, self._rew, self._done)
-        self._restarts(self._done)
-        self._shape(a, self._rew, self._done, rows)     # (with commands: against the command the policy acted on, before it is redrawn)
-        self._randomize(self._obs_engine, self._done)
-        self._noise(self._obs_engine)
-        self._commands(self._obs, self._done)
-        if self._norm is not None:
-            self._normalize(self._obs, self._rew, self._done, 1)
+        self.step_inplace(a)                            # (on the engine-owned buffers)
         t = {k: v.clone() for k, v in self._info.items()}
         t["done"] = self._done.clone()
         return self._obs.clone(), self._rew.clone().unsqueeze(-1), t["done"].float(), LazyInfos(t, t["done"])
 
+    def _before_step(self, actions):
+        """in front of a step launch: the actuation, then the kick -> the actions the launch receives for the caller's raw ``actions``"""
+        applied = self._actuate(actions)
+        self._kick()
+        return applied
+
+    def _after_step(self, e, o, r, d, actions, tail=False):
+        """behind a step launch that wrote the engine's observation rows ``e``, rewards ``r`` and done flags ``d``: every stage that is
+        set, in the one order there is; ``o``: the caller's observation rows (``e`` without commands).  ``tail``: the subset of
+        step_act_inplace -- restarts, shaped terms, return normalisation -- whose policy has already read ``o``"""
+        rows = None if tail else self._terminate(e, r, d)
+        self._restarts(d)
+        self._shape(actions, r, d, rows)                # (with commands: against the command the policy acted on, before it is redrawn)
+        if not tail:
+            self._randomize(e, d)
+            self._noise(e)
+            self._commands(o, d)
+        if self._norm is not None:
+            self._normalize(o, r, d, 1, obs=not tail)
+
     def _raw(self, name, x, *shapes, dtype=torch.float32):
         """The C ABI takes raw pointers: `x` must already be `dtype`, contiguous, of one of `shapes`, on this env's device."""
-        if not (x.is_cuda and x.device == self.device and x.dtype == dtype and x.is_contiguous() and tuple(x.shape) in shapes):
-            raise AssertionError("%s must be a contiguous %s %s tensor on %s, got %s %s on %s" % (
-                name, str(dtype).replace("torch.", ""), " or ".join(str(list(sh)) for sh in shapes), self.device, x.dtype, tuple(x.shape), x.device))
-        return C.c_void_p(x.data_ptr())
+        return tensor_arg(name, x, shapes, dtype, self.device)
 
     def _per_env(self, name, x, lead):
         """one float per env and row (rewards, values, log-probs): [.., N] or [.., N, 1]"""
@@ -713,30 +705,19 @@ class SoloVecEnv:
         o, r, d, po, pr, pd = self._outputs((), (self._obs, self._rew, self._done), obs_out, rew_out, done_out)
         e = o if self._cmd is None else self._obs_engine
         self._steps_issued += 1
-        if self._act is not None:
-            a = C.c_void_p(self._actuate(actions).data_ptr())
-        self._kick()
+        applied = self._before_step(actions)
+        if applied is not actions:
+            a = C.c_void_p(applied.data_ptr())
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_step(self._h, a, C.c_void_p(e.data_ptr()), pr, pd, C.byref(self._info_c), self._stream()))
-        rows = self._terminate(e, r, d)
-        self._restarts(d)
-        self._shape(actions, r, d, rows)
-        self._randomize(e, d)
-        self._noise(e)
-        self._commands(o, d)
-        if self._norm is not None:
-            self._normalize(o, r, d, 1)
+        self._after_step(e, o, r, d, actions)
         return o, r, d, self._info
 
     def step_act_supported(self, params):
         """The policy tail's prerequisites (solorl_step_act, solorl_rollout; include/solorl.h), decided from the handle -- what the engine
         latched at solorl_create, whatever the environment says now: fp32, team mode, no sorting, and an observation size that is a
         multiple of 4 floats and at most 88 (zero or one history level) with the reference's hidden-64 MLP on it."""
-        return (not self._norm_obs                 # (the policy inside the step kernel would read the raw observations)
-                and self._noise_scale is None      # (... and the clean ones)
-                and self._cmd is None              # (... and rows without the command words)
-                and self._term is None             # (... and act on the observation of an env that is about to be reset)
-                and self._rr is None               # (... or on the observation of the un-randomised reset)
+        return (not any(policy is not None and is_set(self) for _, is_set, _, _, _, policy in _STAGES)
                 and self.get_property("step_n_one_launch") == 1 and self.get_property("f64") == 0 and self.obs_dim % 4 == 0 and self.obs_dim <= 88
                 and params.obs_dim == self.obs_dim and params.act_dim == self.act_dim and params.hidden == 64)
 
@@ -751,15 +732,12 @@ class SoloVecEnv:
         pl = self._per_env("logp_out", logp_out, ())
         pn = C.c_void_p(0) if noise is None else self._raw("noise", noise, (self.nenvs, self.act_dim))
         self._steps_issued += 1
-        if self._act is not None:
-            a = C.c_void_p(self._actuate(actions).data_ptr())
-        self._kick()
+        applied = self._before_step(actions)
+        if applied is not actions:
+            a = C.c_void_p(applied.data_ptr())
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_step_act(self._h, a, po, pr, pd, C.byref(self._info_c), C.byref(params), pn, pv, pa, pl, self._stream()))
-        self._restarts(d)
-        self._shape(actions, r, d)
-        if self._norm_ret:
-            self._normalize(o, r, d, 1)
+        self._after_step(o, o, r, d, actions, tail=True)
         return o, r, d, self._info
 
     def _k_rows(self, K):
@@ -801,12 +779,7 @@ class SoloVecEnv:
         """step_inplace for K steps: actions [K, N, A] (float32, contiguous, on this device); returns views of engine-owned rows
         (overwritten by the next call with the same K) -- or writes observations [K, N, O] / rewards [K, N] or [K, N, 1] / done flags
         (uint8 [K, N]) straight into caller-owned tensors such as rollout-storage rows.  Host-side checks only, capturable."""
-        self._no_kicks("step_n")
-        self._no_shaping("step_n")
-        self._no_channel("step_n")
-        self._no_commands("step_n")
-        self._no_termination("step_n")
-        self._no_reset_randomization("step_n")
+        self._refuse("step_n", k_step=True)
         K = int(actions.shape[0]) if actions.dim() == 3 else 0
         if K < 1:
             raise AssertionError("actions must be [K, %d, %d] with K >= 1" % (self.nenvs, self.act_dim))
@@ -824,20 +797,15 @@ class SoloVecEnv:
         """solorl_rollout (K closed-loop steps in one launch) on this handle: the prerequisites of solorl_step_act, and no perturbation
         set (kicks come between two step launches), no reward shaping set (its launch comes behind every step launch) and neither
         observation noise nor actuation set (their launches stand behind and in front of every step launch)."""
-        return self.last_kick is None and self._shape_params is None and self._act is None and self.step_act_supported(params)
+        return not any(between is not None and is_set(self) for _, is_set, _, between, _, _ in _STAGES) and self.step_act_supported(params)
 
     def rollout_inplace(self, actions, params, noise, value_out, logp_out, obs_out=None, rew_out=None, done_out=None, policy_after_last=False):
         """K closed-loop steps in one launch (solorl_rollout), in rollout-storage rows: actions [K (+1), N, A] -- row 0 drives the
         first step, rows 1.. are written by the policy on the observations the steps produce (row K too with policy_after_last: the
         first action of the next window); noise [K (+1), N, A] or None (actions = the mean); value_out / logp_out [K (+1), N] or
         [K (+1), N, 1], rows from 1 written; obs_out [K, N, O], rew_out [K, N] or [K, N, 1], done_out uint8 [K, N] as step_n_inplace."""
-        self._no_policy_tail("rollout_inplace")
-        self._no_kicks("rollout_inplace")
-        self._no_shaping("rollout_inplace")
-        self._no_channel("rollout_inplace")
-        self._no_commands("rollout_inplace")
-        self._no_termination("rollout_inplace")
-        self._no_reset_randomization("rollout_inplace")
+        self._refuse("rollout_inplace", tail=True)
+        self._refuse("rollout_inplace", k_step=True)
         pal = 1 if policy_after_last else 0
         R = int(actions.shape[0]) if actions.dim() == 3 else 0
         K = R - pal
@@ -1031,6 +999,10 @@ class SoloVecEnv:
             self.close()
         except Exception:
             pass
+
+
+for _guard in sorted({g for g, _, _, between, _, _ in _STAGES if between is not None}):       # _no_kicks(name), _no_shaping, _no_channel ...
+    setattr(SoloVecEnv, "_no_" + _guard, lambda self, name, _g=_guard: self._refuse(name, k_step=True, guard=_g))
 
 
 def make_vec_envs(config, num_envs, env_constructor=None, gamma=0.99, device=None, training=True, seed=1,

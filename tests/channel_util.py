@@ -8,27 +8,17 @@ own code -- and the host program tests/host/channel_main.cpp (solorl_amd/csrc/ch
   actuation: counter (gid_lo, gid_hi, 4 e, 6) word 0 -> latency = lo + word % (hi - lo + 1); (.., 4 e + 1 + j // 4, 6) word j % 4 ->
   gain = float32(1.0 + (2u - 1) * r); delayed = in if latency == 0 or fill == 0 else buf[min(latency, fill) - 1]; out = delayed (bits)
   if r == 0 else float32(double(gain) * double(delayed)); then the levels move up, buf[0] = in, fill = min(fill + 1, hi)."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 
-from oracle import oracle_py
+from tests import host_util
+from tests.host_util import M32, bits32, hex32 as _hex, hex64, philox_block as block, u24
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "tests", "host")
 NOISE_STREAM, ACTUATE_STREAM = 5, 6
 DELAY_MAX = 4
-M32 = 0xFFFFFFFF
-
-
-def block(seed, gid, b, stream):
-    return oracle_py.philox(seed & M32, (seed >> 32) & M32, gid & M32, (gid >> 32) & M32, b & M32, stream)
 
 
 def symmetric(word):
-    return 2.0 * (float(word >> 8) * (1.0 / 16777216.0)) - 1.0
+    return 2.0 * u24(word) - 1.0
 
 
 def noise_e(seed, gid, count, D, scale):
@@ -120,37 +110,14 @@ class Actuator:
         return w
 
 
-def bits32(x):
-    """float32 array -> its bit patterns (a bitwise comparison tells -0.0 from +0.0 and compares NaNs)"""
-    return np.ascontiguousarray(np.asarray(x, dtype=np.float32)).view(np.uint32)
-
-
-# ---- the host program
-def build_host(out_dir, flags=()):
-    """tests/host/channel_main.cpp -> an executable in out_dir (no -march=native, contraction off: every operation rounds on its own)"""
-    cxx = shutil.which("g++")
-    assert cxx is not None, "no g++"
-    exe = os.path.join(str(out_dir), "channel_main" + ("_san" if flags else ""))
-    cmd = [cxx, "-O1", "-g1", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off"] + list(flags) + ["-o", exe, os.path.join(HOST, "channel_main.cpp")]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    return exe
-
-
-def _hex(a):
-    return " ".join("%08x" % int(v) for v in np.asarray(a).reshape(-1))
-
-
+# ---- the host program (tests/host/channel_main.cpp: host_util.build_host("channel_main"))
 def run_host(exe, text):
-    r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
-    assert "runtime error" not in r.stderr and "ERROR: AddressSanitizer" not in r.stderr, r.stderr[-4000:]
-    return r.stdout.splitlines()
+    return host_util.run_host(exe, input=text).splitlines()
 
 
 def host_noise(exe, cases):
     """cases: [(seed, gid, count, scale float32 [D], x float32 [D], in_place)] -> [(noisy row as uint32 [D], count afterwards)]"""
-    text = "".join("N %d %d %d %d %d %s %s\n" % (s, g, c, len(x), int(ip), _hex(bits32(sc)), _hex(bits32(x))) for s, g, c, sc, x, ip in cases)
+    text = "".join("N %d %d %d %d %d %s %s\n" % (s, g, c, len(x), int(ip), _hex(sc), _hex(x)) for s, g, c, sc, x, ip in cases)
     out = []
     for line in run_host(exe, text):
         w = line.split()
@@ -162,10 +129,8 @@ def host_noise(exe, cases):
 def host_actuate_many(exe, seed, gids, A, lo, hi, r, actions, flags):
     """Every env's sequence of calls over zeroed memory, in one run: actions float32 [n, T, A], flags [n] strings of T characters ('1'
     restart, '0' none, '-' restart == NULL) -> (out uint32 [n, T, A], rows uint32 [n, T, 64] after each call)"""
-    import struct
     n, T = len(gids), len(flags[0])
-    rbits = struct.unpack("<Q", struct.pack("<d", float(r)))[0]
-    text = "".join("A %d %d %d %d %d %016x %d %s %s\n" % (seed, gids[i], A, lo, hi, rbits, T, flags[i], _hex(bits32(actions[i]))) for i in range(n))
+    text = "".join("A %d %d %d %d %d %s %d %s %s\n" % (seed, gids[i], A, lo, hi, hex64(r), T, flags[i], _hex(actions[i])) for i in range(n))
     lines = run_host(exe, text)
     assert len(lines) == n * T
     words = np.array([[int(v, 16) for v in l.split()] for l in lines], dtype=np.uint32).reshape(n, T, A + 64)

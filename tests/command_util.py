@@ -7,27 +7,15 @@ tests/host/command_main.cpp (solorl_amd/csrc/command.hpp compiled alone by g++) 
   u = (word >> 8) 2^-24, cmd_k = lo_k + u * (hi_k - lo_k) (Python floats are doubles: the same three operations, each rounded once);
   counter (.., 2 d + 1, 7) word 0: u < zero_prob -> (0, 0, 0); cmd_0^2 + cmd_1^2 < min_lin_norm^2 -> cmd_0 = cmd_1 = 0;
   draws = d + 1, countdown = interval.  Observation word k: float32(cmd_k * obs_scale_k)."""
-import os
-import shutil
-import struct
-import subprocess
-
 import numpy as np
 
-from oracle import oracle_py
+from tests.host_util import M32, bits32, hex32, hex64, philox_block, run_host, u24 as uniform  # noqa: F401  (bits32: for the tests)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "tests", "host")
 COMMAND_STREAM = 7
-M32 = 0xFFFFFFFF
 
 
 def block(seed, gid, b):
-    return oracle_py.philox(seed & M32, (seed >> 32) & M32, gid & M32, (gid >> 32) & M32, b & M32, COMMAND_STREAM)
-
-
-def uniform(word):
-    return float(word >> 8) * (1.0 / 16777216.0)
+    return philox_block(seed, gid, b, COMMAND_STREAM)
 
 
 class Params:
@@ -105,26 +93,7 @@ class Commands:
         return w
 
 
-def bits32(x):
-    return np.ascontiguousarray(np.asarray(x, dtype=np.float32)).view(np.uint32)
-
-
-def bits64(x):
-    return struct.unpack("<Q", struct.pack("<d", float(x)))[0]
-
-
-# ---- the host program
-def build_host(out_dir, flags=()):
-    """tests/host/command_main.cpp -> an executable in out_dir (no -march=native, contraction off: every operation rounds on its own)"""
-    cxx = shutil.which("g++")
-    assert cxx is not None, "no g++"
-    exe = os.path.join(str(out_dir), "command_main" + ("_san" if flags else ""))
-    cmd = [cxx, "-O1", "-g1", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", "-DSOLO_HOST_SHIM"] + list(flags) + ["-o", exe, os.path.join(HOST, "command_main.cpp")]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    return exe
-
-
+# ---- the host program (tests/host/command_main.cpp: host_util.build_host("command_main"))
 def host_commands(exe, seed, gid0, n, D, p, flags, masks, obs):
     """T calls on n zeroed rows in one run.  flags: [T] strings of n characters ('1' restart, '0' none) or '-' (restart == NULL);
     masks: [T] strings of n characters or '-' (mask == NULL); obs: float32 [T, n, D], or None with D == 0 (the no-observation form).
@@ -132,14 +101,11 @@ def host_commands(exe, seed, gid0, n, D, p, flags, masks, obs):
     what the program's buffers held before the call (rows: the last call's; cmd_out and obs_out: a fill pattern of 0xAA bytes)"""
     T = len(flags)
     head = "%d %d %d %d %d" % (seed, gid0, n, D, T)
-    pw = " ".join("%016x" % bits64(v) for v in list(p.lo) + list(p.hi) + list(p.obs_scale) + [p.zero_prob, p.min_lin_norm])
+    pw = hex64(list(p.lo) + list(p.hi) + list(p.obs_scale) + [p.zero_prob, p.min_lin_norm])
     text = ["%s %s %d %d\n" % (head, pw, p.interval[0], p.interval[1])]
     for t in range(T):
-        text.append("%s %s %s\n" % (flags[t], masks[t], " ".join("%08x" % int(v) for v in bits32(obs[t]).reshape(-1)) if D else ""))
-    r = subprocess.run([exe], input="".join(text), capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
-    assert "runtime error" not in r.stderr and "ERROR: AddressSanitizer" not in r.stderr, r.stderr[-4000:]
-    lines = r.stdout.splitlines()
+        text.append("%s %s %s\n" % (flags[t], masks[t], hex32(obs[t]) if D else ""))
+    lines = run_host(exe, input="".join(text)).splitlines()
     assert len(lines) == T * n
     rows = np.zeros((T, n, 8), dtype=np.uint32)
     cmd = np.zeros((T, n, 3), dtype=np.uint64)

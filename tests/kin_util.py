@@ -1,23 +1,18 @@
 """Shared by tests/test_kin_host.py and tests/test_kin_gpu.py: the seeded inputs of the solorl_kinematics checks, the stand-alone host
 program (tests/host/rows_main.cpp, which tests/dyn_util.py runs too) and the three references its rows are compared with -- the oracle's prim_points and
 energy_momentum, and a forward kinematics written here in numpy from solorl_amd/models/*.json (nothing of the engine's source)."""
-import atexit
 import ctypes as C
 import functools
 import json
 import os
-import shutil
-import subprocess
 import tempfile
 
 import numpy as np
 
 from solorl_amd.config import EnvState, SoloConfig, default_config, ROBOT_SOLO12, TASK_WALK
 from solorl_amd.kinematics import EnvKin, MEMBERS, ROW_WORDS
+from tests.host_util import ROOT, build_host, run_host, san_flags, sanitizers_link
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "tests", "host")
-SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
 TOL = 1e-10          # |err| <= TOL * max(1, |value|): both sides fp64, a chain of at most 5 frames, ~100 roundings on O(10) magnitudes
 TOL_FD = 1e-6        # central differences with h = 1e-6: truncation O(h^2) + rounding 1e-16 / h
 FD_H = 1e-6
@@ -33,30 +28,15 @@ def kin_cfg(robot, urdf):
 
 
 # ---------------------------------------------------------------- the host program
-_EXE = {}
+def host_main(program, sanitize=False):
+    """Path of tests/host/<program>.cpp built by g++ (once per process), or None if sanitize is asked for and the sanitizer runtimes do
+    not link here."""
+    if sanitize and not sanitizers_link():
+        return None
+    return build_host(program, san_flags(program) if sanitize else ())
 
 
-def rows_main(sanitize=False):
-    """Path of tests/host/rows_main.cpp built by g++ (once per process, in a temporary directory), or None if sanitize is asked for
-    and the sanitizer runtimes do not link here."""
-    if sanitize not in _EXE:
-        d = tempfile.mkdtemp(prefix="rows_main_")
-        atexit.register(shutil.rmtree, d, ignore_errors=True)
-        cxx = shutil.which("g++")
-        assert cxx, "g++ not found"
-        if sanitize:
-            probe = os.path.join(d, "probe.cpp")
-            open(probe, "w").write("int main() { return 0; }\n")
-            r = subprocess.run([cxx, *SAN, "-o", os.path.join(d, "probe"), probe], capture_output=True)
-            if r.returncode != 0 or subprocess.run([os.path.join(d, "probe")], capture_output=True).returncode != 0:
-                _EXE[sanitize] = None
-                return None
-        exe = os.path.join(d, "rows_main_san" if sanitize else "rows_main")
-        cmd = [cxx, "-O1", "-g1", "-std=c++17", "-DSOLO_HOST_SHIM", "-I" + HOST, *(SAN if sanitize else []), "-o", exe, os.path.join(HOST, "rows_main.cpp")]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-4000:]
-        _EXE[sanitize] = exe
-    return _EXE[sanitize]
+rows_main = functools.partial(host_main, "rows_main")
 
 
 def run_rows_main(query, row_words, cfg, states, sanitize=False):
@@ -68,9 +48,7 @@ def run_rows_main(query, row_words, cfg, states, sanitize=False):
             f.write(bytes(cfg)); f.write(np.array([len(states), 0], np.int32).tobytes())
             for s in states:
                 f.write(bytes(s))
-        r = subprocess.run([exe, query, fin, fout], capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
-        assert "runtime error" not in r.stderr and "ERROR: AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+        run_host(exe, (query, fin, fout), timeout=120)
         return np.fromfile(fout, np.float64).reshape(len(states), row_words)
 
 

@@ -6,13 +6,13 @@ oracle's Philox (oracle.oracle_py.philox) and the draw table of include/solorl.h
   doubles: the same two operations), exactly +0.0 for max == 0; countdown = lo + word % (hi - lo + 1)."""
 import numpy as np
 
-from oracle import oracle_py
+from tests.host_util import bits64 as bits, philox_block, u24  # noqa: F401  (bits: for the tests)
 
 STREAM = 4
 
 
 def block(seed, gid, b):
-    return oracle_py.philox(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, gid & 0xFFFFFFFF, (gid >> 32) & 0xFFFFFFFF, b & 0xFFFFFFFF, STREAM)
+    return philox_block(seed, gid, b, STREAM)
 
 
 def countdown(word, lo, hi):
@@ -22,8 +22,7 @@ def countdown(word, lo, hi):
 def component(word, m):
     if m == 0.0:
         return 0.0
-    u = float(word >> 8) * (1.0 / 16777216.0)
-    return (2.0 * u - 1.0) * m
+    return (2.0 * u24(word) - 1.0) * m
 
 
 def first_countdown(seed, gid, lo, hi):
@@ -54,8 +53,3 @@ class Schedule:
             out[i], self.countdown[i] = kick(self.seed, self.gid0 + int(i), int(self.kicks[i]), self.lo, self.hi, self.amps)
             self.kicks[i] += 1
         return out
-
-
-def bits(x):
-    """float64 array -> its bit patterns (a bitwise comparison tells -0.0 from +0.0 and compares NaNs)"""
-    return np.ascontiguousarray(np.asarray(x, dtype=np.float64)).view(np.uint64)

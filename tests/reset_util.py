@@ -8,22 +8,17 @@ and the contact words are compared bit for bit.  quat goes through sin and cos a
 to TOL_TRIG."""
 import ctypes as C
 import math
-import os
-import shutil
-import subprocess
 
 import numpy as np
 
 from oracle import oracle_py
 from solorl_amd._native import ResetRandomization
 from solorl_amd.config import EnvState, ROBOT_SOLO8, ROBOT_SOLO12, TASK_WALK, default_config
+from tests.host_util import bits64 as bits, hex64, philox_block, run_host, u24
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "tests", "host")
 ROW_WORDS = C.sizeof(EnvState) // 8
 STREAM = 8
 HEAD_WORDS = 37
-SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
 TOL_TRIG = 1e-12      # absolute, on quat (order 1) and pos.z (order 1 m): libm's sin / cos against numpy's differ by ulps, 1e-16
 TOL_PLACE = 1e-9      # [m] the lowest support point against the clearance: an fp64 chain of metre-sized terms, 1e-14
 POISON = 0xAAAAAAAAAAAAAAAA
@@ -101,12 +96,11 @@ def full(robot12, **kw):
 
 # ---------------------------------------------------------------- the reference: the draw table in Python floats
 def block(seed, gid, k, b):
-    return oracle_py.philox(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, gid & 0xFFFFFFFF, (gid >> 32) & 0xFFFFFFFF, (16 * k + b) & 0xFFFFFFFF, STREAM)
+    return philox_block(seed, gid, 16 * k + b, STREAM)
 
 
 def delta(word, a):
-    u = float(word >> 8) * (1.0 / 16777216.0)
-    return (2.0 * u - 1.0) * a
+    return (2.0 * u24(word) - 1.0) * a
 
 
 def quat_mul(a, b):
@@ -186,10 +180,6 @@ def reference(robot12, p, rows, count, mask=None, live=None):
 
 
 # ---------------------------------------------------------------- rows
-def bits(x):
-    return np.ascontiguousarray(x).view(np.uint64)
-
-
 def random_rows(robot12, n, seed):
     """n rows: every word poison, then the head members -- a base between 0.3 m below and 0.6 m above the ground, any orientation,
     joints within +-0.9 rad -- random impulses, random contact_mask bits (24.. among them) and counters"""
@@ -265,33 +255,19 @@ def check(got_rows, got_count, want_rows, want_count, rows_in, mask=None, live=N
     return float(err.max()) if err.size else 0.0
 
 
-# ---------------------------------------------------------------- the host program
-def build_host(out_dir, flags=()):
-    """tests/host/reset_random_main.cpp -> an executable in out_dir (no -march=native, contraction off: every operation rounds on its own)"""
-    cxx = shutil.which("g++")
-    assert cxx is not None, "no g++"
-    exe = os.path.join(str(out_dir), "reset_random_main" + ("_san" if flags else ""))
-    cmd = [cxx, "-O1", "-g1", "-std=c++17", "-DSOLO_HOST_SHIM", "-I" + HOST, "-ffp-contract=off"] + list(flags) + ["-o", exe, os.path.join(HOST, "reset_random_main.cpp")]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    return exe
-
-
+# ---------------------------------------------------------------- the host program (tests/host/reset_random_main.cpp)
 def host_reset(exe, robot12, p, rows, count, mask=None, check_params=False):
     """one call of the host program -> (rows [n, 255], count [n] uint32) after it, or None if ``check_params`` and the parameters are
     refused"""
     n = rows.shape[0]
-    hx64 = lambda v: " ".join("%016x" % int(w) for w in bits(np.asarray(v, dtype=np.float64)).reshape(-1))
+    hx64 = hex64
     text = ["%d %d %s %d %d" % (1 if robot12 else 0, n, hx64([p.joint_limit]), int(check_params), int(mask is not None)),
             "%d %d %d" % (p.seed, p.id0, p.place_on_ground), hx64(p.doubles())]
     if mask is not None:
         text.append(" ".join(str(int(b)) for b in np.asarray(mask, dtype=np.uint8)))
     text.append(" ".join(str(int(c)) for c in count))
     text += [hx64(rows[i]) for i in range(n)]
-    r = subprocess.run([exe], input="\n".join(text) + "\n", capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
-    assert "runtime error" not in r.stderr and "ERROR: AddressSanitizer" not in r.stderr, r.stderr[-4000:]
-    lines = r.stdout.strip().split("\n")
+    lines = run_host(exe, input="\n".join(text) + "\n").strip().split("\n")
     if lines[0] == "refused":
         return None
     assert len(lines) == 1 + n, len(lines)

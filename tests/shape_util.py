@@ -2,11 +2,9 @@
 host program (tests/host/shape_main.cpp) and the reference its outputs are compared with -- a numpy restatement of the term table of
 include/solorl.h, which takes the feet's points, velocities and forces from the solorl_kinematics host rows (tests/kin_util.py) and
 nothing from the engine's source."""
-import atexit
 import ctypes as C
+import functools
 import os
-import shutil
-import subprocess
 import tempfile
 import types
 
@@ -15,6 +13,7 @@ import numpy as np
 from solorl_amd.config import EnvState
 from solorl_amd.shaping import EnvShape, ShapeParams, TERMS, ROW_WORDS, SHAPE_TERMS, EP_FIELDS, make_params
 from tests import kin_util as ku
+from tests.host_util import run_host
 
 SEED = 20250307      # gives the coverage tests/test_shape_host.py asserts (every term, first contact, collision, foot force)
 FOOT_PRIMS = (13, 15, 17, 19)
@@ -26,26 +25,7 @@ F_ALL = F_DONE | F_REWARD | F_TERMS | F_EP
 
 
 # ---------------------------------------------------------------- the host program
-_EXE = {}
-
-
-def shape_main(sanitize=False):
-    """Path of tests/host/shape_main.cpp built by g++ (once per process, in a temporary directory), or None if sanitize is asked for
-    and the sanitizer runtimes do not link here."""
-    if sanitize not in _EXE:
-        if sanitize and ku.rows_main(sanitize=True) is None:          # (its probe: g++ cannot link the runtimes)
-            _EXE[sanitize] = None
-            return None
-        d = tempfile.mkdtemp(prefix="shape_main_")
-        atexit.register(shutil.rmtree, d, ignore_errors=True)
-        cxx = shutil.which("g++")
-        assert cxx, "g++ not found"
-        exe = os.path.join(d, "shape_main_san" if sanitize else "shape_main")
-        cmd = [cxx, "-O1", "-g1", "-std=c++17", "-DSOLO_HOST_SHIM", "-I" + ku.HOST, *(ku.SAN if sanitize else []), "-o", exe, os.path.join(ku.HOST, "shape_main.cpp")]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-4000:]
-        _EXE[sanitize] = exe
-    return _EXE[sanitize]
+shape_main = functools.partial(ku.host_main, "shape_main")
 
 
 def run_shape_main(c, flags=F_ALL, mask=None, states=None, sanitize=False):
@@ -62,9 +42,7 @@ def run_shape_main(c, flags=F_ALL, mask=None, states=None, sanitize=False):
             for a in (c.states if states is None else states, c.actions, c.mem, c.reward, c.terms, c.ep,
                       np.ones(n, np.uint8) if mask is None else np.asarray(mask, np.uint8), c.done):
                 f.write(np.ascontiguousarray(a).tobytes())
-        r = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
-        assert "runtime error" not in r.stderr and "ERROR: AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+        run_host(exe, (fin, fout), timeout=120)
         raw = open(fout, "rb").read()
     o = 0
     out = []

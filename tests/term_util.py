@@ -3,17 +3,13 @@ rounds every product, sum and quotient on its own -- and float32 sums where the 
 GPU tests share; and the helper that builds and runs tests/host/terminate_main.cpp (solorl_amd/csrc/termination.hpp compiled alone
 by g++)."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 
 from solorl_amd._native import Termination
 from solorl_amd.config import EnvState
+from tests.host_util import hex32, hex64, run_host
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "tests", "host")
 ROW_WORDS = C.sizeof(EnvState) // 8
 HEIGHT, TILT, CONTACT, JOINT = 1, 2, 4, 8
 ALL = HEIGHT | TILT | CONTACT | JOINT
@@ -272,28 +268,12 @@ def batch(robot12, n, seed=1):
     return rows, done, reward, [cs[i % len(cs)][0] for i in range(n)]
 
 
-# ---- the host program
-def bits64(x):
-    return np.ascontiguousarray(np.asarray(x, dtype=np.float64)).view(np.uint64)
-
-
-def build_host(out_dir, flags=()):
-    """tests/host/terminate_main.cpp -> an executable in out_dir (no -march=native, contraction off: every operation rounds on its own)"""
-    cxx = shutil.which("g++")
-    assert cxx is not None, "no g++"
-    exe = os.path.join(str(out_dir), "terminate_main" + ("_san" if flags else ""))
-    cmd = [cxx, "-O1", "-g1", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off"] + list(flags) + ["-o", exe, os.path.join(HOST, "terminate_main.cpp")]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    return exe
-
-
+# ---- the host program (tests/host/terminate_main.cpp: host_util.build_host("terminate_main"))
 def host_terminate(exe, robot12, p, sim_dt, rows, arrays, mask=None, info=True, stats=True, check=False):
     """one call of the host program on ``arrays`` -> the arrays after it (a new Arrays; members the call was not given stay as they
     were), or None if ``check`` and the parameters are refused"""
     n = rows.shape[0]
-    hx64 = lambda v: " ".join("%016x" % int(w) for w in bits64(v).reshape(-1))
-    hx32 = lambda v: " ".join("%08x" % int(w) for w in np.ascontiguousarray(v).view(np.uint32).reshape(-1))
+    hx64, hx32 = hex64, hex32
     dec = lambda v: " ".join(str(int(b)) for b in v)
     text = ["%d %d %s %d %d %d %d" % (1 if robot12 else 0, n, hx64([sim_dt]), int(check), int(mask is not None), int(info), int(stats)),
             "%d %d %d %s" % (p.rules, p.min_steps, p.contact_prims,
@@ -306,9 +286,7 @@ def host_terminate(exe, robot12, p, sim_dt, rows, arrays, mask=None, info=True, 
     if stats:
         text.append(hx32(arrays.stats))
     text += [hx64(rows[i]) for i in range(n)]
-    r = subprocess.run([exe], input="\n".join(text) + "\n", capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
-    lines = r.stdout.strip().split("\n")
+    lines = run_host(exe, input="\n".join(text) + "\n").strip().split("\n")
     if lines[0] == "refused":
         return None
     out = arrays.copy()

@@ -13,6 +13,7 @@ import torch
 from solorl_amd import _native, channel
 from solorl_amd.config import default_config, ROBOT_SOLO12, TASK_WALK
 from tests import channel_util as cu
+from tests.host_util import build_host
 from tests.test_channel_host import ACT_CASES, RESTARTS
 
 pytestmark = pytest.mark.gpu
@@ -24,8 +25,8 @@ SEED, OFF = 2301, 2 ** 32 + 3      # (global env ids above 2^32)
 
 
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    return cu.build_host(tmp_path_factory.mktemp("channel_gpu"))
+def exe():
+    return build_host("channel_main")
 
 
 def _rows(n, D, offset_words, seed):

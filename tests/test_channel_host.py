@@ -12,15 +12,15 @@ import pytest
 from solorl_amd import channel
 from solorl_amd.config import default_config, ROBOT_SOLO8, ROBOT_SOLO12, TASK_WALK, TASK_POINTGOAL
 from tests import channel_util as cu
+from tests.host_util import build_host, san_flags
 
-SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
 DIMS = (30, 38, 42, 76, 210)
 COUNTS = (0, 1, 2, 2 ** 32 - 1)
 
 
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    return cu.build_host(tmp_path_factory.mktemp("channel_host"))
+def exe():
+    return build_host("channel_main")
 
 
 def pairs():
@@ -105,7 +105,7 @@ def test_host_actuator_rows_equal_the_python_prediction(exe, A, lo, hi, r):
 def test_boundary_shapes_under_the_sanitizers(tmp_path):
     """The same stand-alone program with AddressSanitizer and UBSan, on D = 210 and delay_max = 4 (its buffers are heap blocks of exactly
     D and 64 words: an access past either ends the run)"""
-    san = cu.build_host(tmp_path, SAN)
+    san = build_host("channel_main", san_flags("channel_main"), tmp_path)
     rng = np.random.default_rng(9)
     cases = []
     for k, count in enumerate(COUNTS):

@@ -14,6 +14,7 @@ import torch
 from solorl_amd import _native, command
 from solorl_amd.config import default_config, ROBOT_SOLO12, TASK_WALK
 from tests import command_util as cu
+from tests.host_util import build_host
 from tests.test_command_host import FIXED, WALK, obs_rows
 
 pytestmark = pytest.mark.gpu
@@ -27,8 +28,8 @@ WALK_DICT = dict(lin_vel_x=(WALK.lo[0], WALK.hi[0]), lin_vel_y=(WALK.lo[1], WALK
 
 
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    return cu.build_host(tmp_path_factory.mktemp("command_gpu"))
+def exe():
+    return build_host("command_main")
 
 
 def _params(D, p=WALK, seed=SEED, off=OFF):

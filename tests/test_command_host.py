@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 
 from tests import command_util as cu
+from tests.host_util import build_host, san_flags
 
-SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
 SEED = 2301
 INTERVAL = (2, 5)
 # the ranges of the host and the GPU tests: a walk task's (both signs, a zero command now and then, a deadband), and a joystick's
@@ -42,8 +42,8 @@ def obs_rows(calls, n, D, seed=3):
 
 
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    return cu.build_host(tmp_path_factory.mktemp("command_host"))
+def exe():
+    return build_host("command_main")
 
 
 def check_run(exe, name, n, D, calls=CALLS):
@@ -79,7 +79,7 @@ def test_host_rows_equal_the_python_prediction(exe, name):
 def test_boundary_shapes_under_the_sanitizers(tmp_path):
     """The same stand-alone program with AddressSanitizer and UBSan on n = 1 and D in {1, 42, 210} (its observation buffers are heap
     blocks of exactly D and D + 3 floats: an access past either ends the run)"""
-    san = cu.build_host(tmp_path, SAN)
+    san = build_host("command_main", san_flags("command_main"), tmp_path)
     for D in (1, 42, 210):
         p = WALK
         obs = obs_rows(12, 1, D)

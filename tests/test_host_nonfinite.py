@@ -6,53 +6,31 @@ kernels instantiate, compiled for one lane -- into a stand-alone program with Ad
 included), runs it as a child process and requires: no report (exit 0: -fno-sanitize-recover=all aborts at the first one), and the
 guard's sum non-finite or beyond its threshold on every line whose state is.  tests/test_nan_guard_gpu.py runs the same poisons on
 the device."""
-import os
 import shutil
-import subprocess
+from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
 from solorl_amd.config import default_config, ROBOT_SOLO8, ROBOT_SOLO12, TASK_WALK
+from tests.host_util import build_host, run_host, san_flags, sanitizers_link
 
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host")
-SAN = ["-fsanitize=address,undefined,float-cast-overflow", "-fno-sanitize-recover=all"]
 POISONS = ("action_nan", "lin_vel_z_inf", "q_nan", "quat_x_nan", "pos_x_1e31", "pos_z_nan", "pos_y_nan", "ang_vel_neg_inf")
 
 
-def _sanitizers_link(cxx, tmp):
-    src = os.path.join(tmp, "probe.cpp")
-    with open(src, "w") as f:
-        f.write("int main() { return 0; }\n")
-    exe = os.path.join(tmp, "probe")
-    r = subprocess.run([cxx, *SAN, "-o", exe, src], capture_output=True)
-    return r.returncode == 0 and subprocess.run([exe], capture_output=True).returncode == 0
-
-
 def test_nonfinite_states_under_the_sanitizers(tmp_path):
-    # (-g1: file and line in a sanitizer report; full -g more than doubles the four builds' time and adds nothing to the check)
-    cxx = shutil.which("g++")
-    if cxx is None or not _sanitizers_link(cxx, str(tmp_path)):
+    if shutil.which("g++") is None or not sanitizers_link():
         pytest.skip("g++ cannot link the sanitizer runtimes here")
     # the four instantiations (robot x arithmetic type) as four programs, compiled side by side
-    builds = []
-    for robot in (ROBOT_SOLO12, ROBOT_SOLO8):
+    variants = [(robot, use_float) for robot in (ROBOT_SOLO12, ROBOT_SOLO8) for use_float in (1, 0)]
+    with ThreadPoolExecutor(len(variants)) as pool:
+        exes = list(pool.map(lambda v: build_host("nonfinite_main", san_flags("nonfinite_main") + ["-DHARNESS_ONLY_ROBOT=%d" % v[0], "-DHARNESS_ONLY_FLOAT=%d" % v[1]],
+                                                  tmp_path), variants))
+    lines = []
+    for (robot, _), exe in zip(variants, exes):
         cfg = str(tmp_path / ("cfg%d.bin" % robot))
         with open(cfg, "wb") as f:
             f.write(bytes(default_config(robot, TASK_WALK)))
-        for use_float in (1, 0):
-            exe = str(tmp_path / ("nonfinite_r%d_f%d" % (robot, use_float)))
-            cmd = [cxx, "-O1", "-g1", "-std=c++17", *SAN, "-DHARNESS_ONLY_ROBOT=%d" % robot, "-DHARNESS_ONLY_FLOAT=%d" % use_float, "-I" + HERE,
-                   "-o", exe, os.path.join(HERE, "nonfinite_main.cpp")]
-            builds.append((subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True), exe, cfg))
-    lines = []
-    for proc, exe, cfg in builds:
-        out, _ = proc.communicate()
-        assert proc.returncode == 0, out[-4000:]
-    for proc, exe, cfg in builds:
-        r = subprocess.run([exe, cfg], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-        assert "runtime error" not in r.stderr and "ERROR: AddressSanitizer" not in r.stderr, r.stderr[-4000:]
-        lines += [l.split() for l in r.stdout.splitlines() if l.startswith("robot ")]
+        lines += [l.split() for l in run_host(exe, (cfg,)).splitlines() if l.startswith("robot ")]
     # robot x {float, double} x treadmill {0, 1} x the poisons (pos_y_nan: with the treadmill only)
     assert len(lines) == 2 * 2 * (2 * len(POISONS) - 1), len(lines)
     seen = set()

@@ -10,7 +10,6 @@ import ctypes as C
 import os
 import re
 import shutil
-import struct
 import subprocess
 
 import numpy as np
@@ -18,20 +17,13 @@ import pytest
 
 from solorl_amd import _native, build
 from tests import perturb_util as pu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "tests", "host")
-SAN = ["-fsanitize=address,undefined,float-cast-overflow", "-fno-sanitize-recover=all"]
+from tests.host_util import ROOT, build_host, hex64 as _hex, run_host, san_flags, sanitizers_link
 
 
 @pytest.fixture(scope="module")
 def lib():
     build.build()
     return _native.lib()
-
-
-def _hex(x):
-    return "%016x" % struct.unpack("<Q", struct.pack("<d", x))[0]
 
 
 def _cases():
@@ -49,21 +41,13 @@ def _cases():
 
 
 def test_host_program_draws_equal_the_python_prediction(tmp_path):
-    cxx = shutil.which("g++")
-    if cxx is None:
+    if shutil.which("g++") is None:
         pytest.skip("no g++")
-    exe = str(tmp_path / "perturb_main")
-    base = [cxx, "-O1", "-g1", "-std=c++17", "-Wall", "-Werror", "-o", exe, os.path.join(HOST, "perturb_main.cpp")]
-    r = subprocess.run(base[:-3] + SAN + base[-3:], capture_output=True, text=True)
-    if r.returncode != 0:                      # g++ cannot link the sanitizer runtimes here: the plain program checks the same draws
-        r = subprocess.run(base, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
+    # (where g++ cannot link the sanitizer runtimes, the plain program checks the same draws)
+    exe = build_host("perturb_main", san_flags("perturb_main") if sanitizers_link() else (), tmp_path)
     cases = _cases()
-    text = "".join("%d %d %d %d %s\n" % (s, g, lo, hi, " ".join(_hex(a) for a in amp)) for s, g, (lo, hi), amp in cases)
-    r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
-    assert "runtime error" not in r.stderr and "ERROR: AddressSanitizer" not in r.stderr, r.stderr[-4000:]
-    lines = r.stdout.splitlines()
+    text = "".join("%d %d %d %d %s\n" % (s, g, lo, hi, _hex(amp)) for s, g, (lo, hi), amp in cases)
+    lines = run_host(exe, input=text, timeout=120).splitlines()
     assert len(lines) == len(cases) >= 200
     kicked = 0
     for (seed, gid, (lo, hi), amp), line in zip(cases, lines):

@@ -12,6 +12,7 @@ from solorl_amd import _native, reset_random
 from solorl_amd.config import EnvState, PRECISION_F64, ROBOT_SOLO8, ROBOT_SOLO12, TASK_STAND, TASK_WALK, default_config
 from solorl_amd.state import StateBatch
 from tests import reset_util as ru
+from tests.host_util import build_host
 from tests.reset_util import W
 
 pytestmark = pytest.mark.gpu
@@ -22,8 +23,8 @@ RANGES = dict(joint_pos=0.2, joint_vel=1.0, lin_vel=0.3, ang_vel=0.3, yaw=3.14, 
 
 
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    return ru.build_host(tmp_path_factory.mktemp("reset_gpu"))
+def exe():
+    return build_host("reset_random_main")
 
 
 # ---- 1: the kernel against the host program

@@ -9,12 +9,13 @@ import numpy as np
 import pytest
 
 from tests import reset_util as ru
+from tests.host_util import build_host, san_flags
 from tests.reset_util import W
 
 
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    return ru.build_host(tmp_path_factory.mktemp("reset_host"))
+def exe():
+    return build_host("reset_random_main")
 
 
 def run(exe, robot12, p, rows, count=None, mask=None, live=None, what=""):
@@ -195,7 +196,7 @@ def test_refusals(exe):
 
 def test_sanitized_run(tmp_path):
     """the same program once under AddressSanitizer and UBSan, as a child process: every row and array is a heap block of its exact size"""
-    exe = ru.build_host(tmp_path, ru.SAN)
+    exe = build_host("reset_random_main", san_flags("reset_random_main"), tmp_path)
     for robot12 in (0, 1):
         rows = ru.batch(robot12, 14)
         rows[3, W("q")] = float("nan")

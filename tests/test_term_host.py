@@ -10,13 +10,13 @@ import numpy as np
 import pytest
 
 from tests import term_util as tu
+from tests.host_util import build_host, san_flags
 
-SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
 
 
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    return tu.build_host(tmp_path_factory.mktemp("term_host"))
+def exe():
+    return build_host("terminate_main")
 
 
 def run_cases(exe, robot12, p, mask=None, info=True, stats=True, n=None):
@@ -82,7 +82,7 @@ def test_a_solo8_ignores_joints_8_to_11_and_primitives_20_to_23(exe):
 def test_boundary_shapes_under_the_sanitizers(tmp_path):
     """The same stand-alone program with AddressSanitizer and UBSan on n = 1 and on every crafted row of both robots (every array and
     every state row is a heap block of exactly its size: an access past one ends the run)"""
-    san = tu.build_host(tmp_path, SAN)
+    san = build_host("terminate_main", san_flags("terminate_main"), tmp_path)
     for robot12 in (True, False):
         p = tu.params(robot12)
         run_cases(san, robot12, p, n=1)

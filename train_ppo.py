@@ -66,50 +66,50 @@ def add_channel_flags(p):
                    help="each joint's action is scaled by 1 + U(-G, G), drawn per env and episode (default: 0, exact)")
 
 
-def load_obs_noise(path, config):
-    """--obs-noise FILE.yaml -> its dict, with unknown groups and keys refused by name before anything is built"""
-    from solorl_amd.channel import scales_from_dict
-    from solorl_amd.config import config_from_dict, load_yaml
-    noise = load_yaml(path)
+def load_option(flag, path, validate):
+    """--flag FILE.yaml -> validate(the file's dict), with unknown keys and bad values refused by name before anything is built"""
+    from solorl_amd.config import load_yaml
     try:
-        scales_from_dict(config_from_dict(config), noise)
+        return validate(load_yaml(path))
     except (ValueError, AttributeError, TypeError) as e:
-        raise SystemExit("--obs-noise %s: %s" % (path, e))
-    return noise
+        raise SystemExit("%s %s: %s" % (flag, path, e))
+
+
+def _checked(check):
+    """validate for load_option: the file's dict itself, once ``check`` has taken it"""
+    def validate(d):
+        check(d)
+        return d
+    return validate
+
+
+def load_reward_shaping(path):
+    from solorl_amd.shaping import params_from_dict
+    return load_option("--reward-shaping", path, _checked(params_from_dict))
+
+
+def load_obs_noise(path, config):
+    from solorl_amd.channel import scales_from_dict
+    from solorl_amd.config import config_from_dict
+    return load_option("--obs-noise", path, _checked(lambda d: scales_from_dict(config_from_dict(config), d)))
 
 
 def load_commands(path):
-    """--commands FILE.yaml -> its dict, with unknown keys and bad values refused by name before anything is built"""
     from solorl_amd.command import ranges_from_dict
-    from solorl_amd.config import load_yaml
-    try:
-        return ranges_from_dict(load_yaml(path))
-    except (ValueError, AttributeError, TypeError) as e:
-        raise SystemExit("--commands %s: %s" % (path, e))
+    return load_option("--commands", path, ranges_from_dict)
 
 
 def load_termination(path, config):
-    """--termination FILE.yaml -> its dict, with unknown keys and bad values refused by name before anything is built"""
-    from solorl_amd.config import config_from_dict, load_yaml
+    from solorl_amd.config import config_from_dict
     from solorl_amd.termination import make_termination, rules_from_dict
-    try:
-        rules = rules_from_dict(load_yaml(path))
-        make_termination(config_from_dict(config), **rules)
-        return rules
-    except (ValueError, AttributeError, TypeError) as e:
-        raise SystemExit("--termination %s: %s" % (path, e))
+    return load_option("--termination", path, _checked(lambda d: make_termination(config_from_dict(config), **rules_from_dict(d))))
 
 
 def load_reset_randomization(path, config):
-    """--reset-randomization FILE.yaml -> its dict, with unknown keys and bad values refused by name before anything is built"""
-    from solorl_amd.config import config_from_dict, load_yaml
+    from solorl_amd.config import config_from_dict
     from solorl_amd.reset_random import make_reset_randomization, ranges_from_dict
-    try:
-        ranges = ranges_from_dict(load_yaml(path))
-        make_reset_randomization(config_from_dict(config), 0, 0, **ranges)
-        return ranges
-    except (ValueError, AttributeError, TypeError) as e:
-        raise SystemExit("--reset-randomization %s: %s" % (path, e))
+    return load_option("--reset-randomization", path,
+                       _checked(lambda d: make_reset_randomization(config_from_dict(config), 0, 0, **ranges_from_dict(d))))
 
 
 def get_ppo_args(argv=None):
@@ -173,13 +173,7 @@ def main(argv=None):
     if args.num_steps is None:
         args.num_steps = config["episode_length"]
     if args.reward_shaping is not None:
-        from solorl_amd.shaping import params_from_dict
-        shaping = load_yaml(args.reward_shaping)
-        try:
-            params_from_dict(shaping)                 # unknown term and parameter names are refused by name, before anything is built
-        except ValueError as e:
-            raise SystemExit("--reward-shaping %s: %s" % (args.reward_shaping, e))
-        args.reward_shaping = shaping
+        args.reward_shaping = load_reward_shaping(args.reward_shaping)
     if args.obs_noise is not None:
         args.obs_noise = load_obs_noise(args.obs_noise, config)
     if args.commands is not None:
