@@ -124,7 +124,11 @@ def main(argv=None):
                              "with" if width == env.engine_obs_dim + 3 else "without", "given here" if commands is None else "left out"))
     env.ob_rms = ob_rms
     env.eval()
-    policy = Policy(env.observation_space.shape, env.action_space, None, {"hidden_size": a.hidden_size}).to(dev)
+    # a checkpoint trained with --privileged-critic: its critic reads rows of another width (the names are the same).  Evaluation runs
+    # the actor alone, which needs no critic rows: the env is made without them
+    critic_width = ckpt["state_dict"]["base.critic.0.weight"].shape[1]
+    policy = Policy(env.observation_space.shape, env.action_space, None, {"hidden_size": a.hidden_size},
+                    critic_obs_dim=None if critic_width == width else critic_width).to(dev)
     policy.load_state_dict(ckpt["state_dict"])
     policy.eval()
     torch.manual_seed(a.seed)
@@ -148,7 +152,10 @@ def main(argv=None):
             obs = env.normalize_obs(env.get_observation())          # the policy sees the kicked velocities
         steps += 1
         with torch.no_grad():
-            _, action, _ = policy.act(obs, deterministic=a.deterministic)
+            if policy.critic_obs_dim is None:
+                _, action, _ = policy.act(obs, deterministic=a.deterministic)
+            else:                                        # an asymmetric checkpoint: the actor alone (there are no critic rows here)
+                action = policy.act_actor(obs, deterministic=a.deterministic)
         if gait is not None or a.dump:
             rows = env.get_states(out=rows)              # the state the policy has just seen, every env: two launches
             kin = env.get_kinematics(states=rows, out=kin)

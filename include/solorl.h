@@ -692,6 +692,45 @@ int solorl_randomize_reset(const solorl_config* cfg, const solorl_reset_randomiz
 int solorl_restart_history(solorl_env* env, const uint8_t* mask /* [N] device, not NULL */,
                            float* obs_out /* [N*O] or NULL */, void* stream);
 
+/* Privileged critic rows (no reference counterpart; the "asymmetric actor-critic" of domain-randomised legged-robot training): the actor
+ * keeps the observation row a robot could measure, the critic gets that row WITHOUT its sensor noise plus SOLORL_CRITIC_PRIV words of the
+ * simulator's truth -- contact forces, foot heights and speeds, the command, the episode's progress, collisions, and what the actuation
+ * and the kicks drew.  A sixth handle-free row query beside solorl_kinematics, solorl_dynamics, solorl_shape_reward, solorl_terminate
+ * and solorl_randomize_reset: a pure function of its arguments, ONE kernel launch on `stream`, no allocation, no host synchronisation
+ * (capturable).  E = p->obs_dim, A = the robot's 8 or 12 joints.  For every live row i:
+ *   critic_out[i][0 .. E-1]  the bits of obs_in[i][0 .. E-1] (NaN payloads and -0.0 survive)
+ *   critic_out[i][E + k]     (float)(raw_k * p->scale[k]), the product rounded in double first; raw_k in fp64:
+ *    k       raw_k
+ *    0..3    F_f: the normal force of foot f = FL, FR, HL, HR in the last sub-step [N] -- solorl_env_kin's prim_force of the foot
+ *            primitive 13 + 2 f (the same functions compute it, and p_f and u_f below, from states[i])
+ *    4..7    p_f.z: the height of that primitive's support point [m] (prim_point)
+ *    8..11   sqrt(u_f.x * u_f.x + u_f.y * u_f.y): the horizontal speed of that point (prim_vel), each product rounded, then the sum
+ *    12..14  cmd[i].cmd[0..2] (0 if cmd is NULL)
+ *    15      states[i].timestep
+ *    16      the number of set contact_mask bits among the robot's primitives other than the four foot primitives (term 13 of the
+ *            shaped reward)
+ *    17      act[i].latency (0 if act is NULL)
+ *    18      ((g_0 + g_1) + ... + g_{A-1}) / A - 1 over act[i].gain[0 .. A-1], each widened to double, summed left to right (0 if act is NULL)
+ *    19      sqrt(kick[i][0] * kick[i][0] + kick[i][1] * kick[i][1]), each product rounded, then the sum (0 if kick is NULL)
+ *   Nothing is done about non-finite values: they propagate into the words they feed and into no other.
+ * masked (mask byte 0): nothing of the row is read or written, in any array.  critic_out must not overlap obs_in.
+ * Null cfg, p, states, obs_in or critic_out, n < 1, a robot that is neither SOLORL_ROBOT_*, obs_dim < 1 or > 210, a scale that is not
+ * finite: SOLORL_ERR_INVALID, the message starts with "solorl_critic_obs:" (checked before any HIP call). */
+#define SOLORL_CRITIC_PRIV 20
+typedef struct solorl_critic_params {
+  double scale[SOLORL_CRITIC_PRIV];   /* finite; 0 = that word reads 0 (or NaN where raw_k is not finite) */
+  int32_t obs_dim;                    /* E: width of obs_in's rows; 1 <= E <= 210 */
+  int32_t reserved;
+} solorl_critic_params;
+int solorl_critic_obs(const solorl_config* cfg, const solorl_critic_params* p,
+                      const solorl_env_state* states /* [n] DEVICE rows: the state the observation describes */,
+                      const uint8_t* mask /* [n] or NULL */, int n,
+                      const float* obs_in /* [n][E]: the engine's clean observation rows */,
+                      const solorl_env_command* cmd /* [n] rows or NULL */,
+                      const solorl_env_actuator* act /* [n] rows or NULL */,
+                      const double* kick /* [n][6] as solorl_perturb writes kick_out, or NULL */,
+                      float* critic_out /* [n][E + SOLORL_CRITIC_PRIV] */, int device_id, void* stream);
+
 /* Fused return computation over a rollout of T steps x N envs (device arrays, time-major [t][n]).
  * use_gae != 0:  value_preds[T][:] = next_value;  delta_t = r_t + gamma V_{t+1} m_{t+1} - V_t;
  *                A_t = delta_t + gamma lambda m_{t+1} A_{t+1};  returns[t] = A_t + V_t      (storage.py:41-50)
@@ -748,7 +787,9 @@ int solorl_ppo_loss(const float* mean, const float* logstd, const float* values,
  * mean_w -- and, when obs_dim % 4 == 0, critic_w0, actor_w0 and every `obs` array handed to solorl_policy_act /
  * solorl_ppo_batch -- are read as float4 rows and must start on a 16-byte boundary (checked: SOLORL_ERR_INVALID otherwise). */
 typedef struct solorl_policy_params {
-  int obs_dim, act_dim, hidden, reserved0;
+  int obs_dim, act_dim, hidden;
+  int critic_obs_dim;   /* 0: the critic reads the actor's rows (symmetric); OC != 0: critic_w0 is [64][OC] and the critic reads rows of OC
+                         * words of its own (the slot was reserved0: size and layout are unchanged) */
   const float *critic_w0, *critic_b0, *critic_w1, *critic_b1, *critic_w2, *critic_b2;
   const float *actor_w0, *actor_b0, *actor_w1, *actor_b1, *mean_w, *mean_b, *logstd;
 } solorl_policy_params;
@@ -851,6 +892,28 @@ int solorl_step_n(solorl_env* env, int K, const float* actions, float* obs_out, 
 int solorl_rollout(solorl_env* env, int K, float* actions, float* obs_out, float* reward_out, uint8_t* done_out,
                    const solorl_info_soa* info_out, const solorl_policy_params* p, const float* noise,
                    float* value_out, float* logp_out, int policy_after_last, void* stream);
+
+/* The asymmetric actor-critic (privileged critic): a policy whose solorl_policy_params.critic_obs_dim = OC != 0 -- the critic's first layer
+ * is [64][OC] and reads rows of its own, e.g. solorl_critic_obs' -- goes through the three entry points below, which are the ones above
+ * with the critic's rows beside the actor's; the ones above refuse such a policy (SOLORL_ERR_INVALID).  Built for (obs_dim, OC, act_dim) =
+ * (38, 58, 12), (41, 58, 12), (76, 96, 12), (30, 50, 8), (33, 50, 8), (60, 80, 8): walk and stand at zero and one history level and the
+ * commanded zero-history widths, OC = the engine's width + SOLORL_CRITIC_PRIV; other shapes return SOLORL_ERR_INVALID and the caller
+ * keeps its framework path.  solorl_ppo_clip_adam reads both widths from p and serves both forms.
+ *   solorl_policy_act_critic       value_out from critic_obs [n][OC], action_out and logp_out from obs [n][obs_dim]
+ *   solorl_ppo_grad_stage1_critic  critic_obs [rows][OC]: the rollout's critic rows, gathered through batch->perm like batch->obs;
+ *                                  work->xt0 receives the ACTOR's gathered rows (obs_dim units), critic_xt0 (OC x m floats, tiled like
+ *                                  xt0) the critic's
+ *   solorl_ppo_grad_stage2_critic  the critic's first layer from critic_xt0 with K = OC; out->scratch holds
+ *                                  solorl_ppo_scratch_count2 floats, the moments of solorl_adam_state solorl_ppo_grad_count2 + act_dim
+ * Rows of a width that is a multiple of 4 (and critic_w0 when OC is) must start on a 16-byte boundary. */
+int solorl_policy_act_critic(const solorl_policy_params* p, const float* obs /* [n][obs_dim] */, const float* critic_obs /* [n][OC] */,
+                             const float* noise, int n, float* value_out, float* action_out, float* logp_out, int device_id, void* stream);
+int solorl_ppo_grad_stage1_critic(const solorl_policy_params* p, const solorl_ppo_batch* batch, const float* critic_obs,
+                                  const solorl_ppo_stage1* work, float* critic_xt0, int device_id, void* stream);
+int solorl_ppo_grad_stage2_critic(const solorl_policy_params* p, const solorl_ppo_stage1* work, const float* critic_xt0, int m,
+                                  const solorl_ppo_grads* out, int device_id, void* stream);
+int solorl_ppo_grad_count2(int obs_dim, int critic_obs_dim, int act_dim);
+int solorl_ppo_scratch_count2(int obs_dim, int critic_obs_dim, int act_dim, int m);
 
 const char* solorl_last_error(void);
 const char* solorl_version(void);

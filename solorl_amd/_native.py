@@ -21,11 +21,12 @@ SYMBOLS = ("solorl_default_config", "solorl_create", "solorl_destroy", "solorl_d
            "solorl_set_perturbation", "solorl_perturb", "solorl_get_perturbation",
            "solorl_norm_scratch_count", "solorl_normalize_obs", "solorl_normalize_rewards", "solorl_kinematics", "solorl_dynamics",
            "solorl_shape_reward", "solorl_obs_noise", "solorl_actuate", "solorl_commands", "solorl_shape_reward_cmd",
-           "solorl_terminate", "solorl_randomize_reset", "solorl_restart_history")
+           "solorl_terminate", "solorl_randomize_reset", "solorl_restart_history", "solorl_critic_obs",
+           "solorl_policy_act_critic", "solorl_ppo_grad_stage1_critic", "solorl_ppo_grad_stage2_critic", "solorl_ppo_grad_count2", "solorl_ppo_scratch_count2")
 
 
 class PolicyParams(C.Structure):            # solorl_policy_params
-    _fields_ = [("obs_dim", C.c_int), ("act_dim", C.c_int), ("hidden", C.c_int), ("reserved0", C.c_int)] + [
+    _fields_ = [("obs_dim", C.c_int), ("act_dim", C.c_int), ("hidden", C.c_int), ("critic_obs_dim", C.c_int)] + [
         (n, C.c_void_p) for n in ("critic_w0", "critic_b0", "critic_w1", "critic_b1", "critic_w2", "critic_b2", "actor_w0", "actor_b0",
                                   "actor_w1", "actor_b1", "mean_w", "mean_b", "logstd")]
 
@@ -93,6 +94,13 @@ class ResetRandomization(C.Structure):      # solorl_reset_randomization
                 ("clearance", C.c_double), ("place_on_ground", C.c_int32), ("reserved", C.c_int32)]
 
 
+CRITIC_PRIV = 20                            # SOLORL_CRITIC_PRIV
+
+
+class CriticParams(C.Structure):            # solorl_critic_params
+    _fields_ = [("scale", C.c_double * CRITIC_PRIV), ("obs_dim", C.c_int32), ("reserved", C.c_int32)]
+
+
 class SoloRLError(RuntimeError):
     pass
 
@@ -144,6 +152,12 @@ def lib():
         L.solorl_ppo_grad_count.argtypes = [C.c_int, C.c_int]
         L.solorl_ppo_scratch_count.argtypes = [C.c_int, C.c_int, C.c_int]
         L.solorl_ppo_scratch_count.restype = C.c_int
+        # the asymmetric policy (critic_obs_dim != 0): the critic's rows beside the actor's
+        L.solorl_policy_act_critic.argtypes = [C.POINTER(PolicyParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.solorl_ppo_grad_stage1_critic.argtypes = [C.POINTER(PolicyParams), C.POINTER(PpoBatch), C.c_void_p, C.POINTER(PpoStage1), C.c_void_p, C.c_int, C.c_void_p]
+        L.solorl_ppo_grad_stage2_critic.argtypes = [C.POINTER(PolicyParams), C.POINTER(PpoStage1), C.c_void_p, C.c_int, C.POINTER(PpoGrads), C.c_int, C.c_void_p]
+        L.solorl_ppo_grad_count2.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.solorl_ppo_scratch_count2.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
         L.solorl_ppo_clip_adam.argtypes = [C.POINTER(PolicyParams), C.POINTER(PpoGrads), C.POINTER(AdamState), C.c_int, C.c_void_p]
         # running normalisation: stats / ret / scratch are device pointers to doubles
         L.solorl_norm_scratch_count.argtypes = [C.c_int, C.c_int, C.c_int]
@@ -182,6 +196,10 @@ def lib():
                                              C.c_int, C.c_void_p]
         L.solorl_restart_history.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.solorl_randomize_reset.restype = L.solorl_restart_history.restype = C.c_int
+        # privileged critic rows (critic_obs.py): handle-free; cfg and params are host structs, every array a device pointer
+        L.solorl_critic_obs.argtypes = [C.POINTER(SoloConfig), C.POINTER(CriticParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.solorl_critic_obs.restype = C.c_int
         for s in SYMBOLS:
             getattr(L, s)
         # the ctypes mirrors in config.py / this file are written against one layout of include/solorl.h's structs

@@ -20,13 +20,14 @@ UNITS = {
     "solorl_command.hip": [os.path.join(HERE, "csrc", f) for f in ("solorl_command.hip", "command.hpp", "channel.hpp", "perturb.hpp", "row_batch.hpp")] + INC[:1],
     "solorl_term.hip": [os.path.join(HERE, "csrc", f) for f in ("solorl_term.hip", "termination.hpp", "row_batch.hpp")] + INC[:1],
     "solorl_reset.hip": [os.path.join(HERE, "csrc", f) for f in ("solorl_reset.hip", "row_batch.hpp", "reset_random.hpp", "perturb.hpp", "kinematics.hpp", "state_row.hpp", "dynamics.hpp", "spatial.hpp")] + INC,
+    "solorl_critic.hip": [os.path.join(HERE, "csrc", f) for f in ("solorl_critic.hip", "row_batch.hpp", "critic_obs.hpp", "reward_shape.hpp", "kinematics.hpp", "state_row.hpp", "dynamics.hpp", "spatial.hpp")] + INC,
 }
 SRC = UNITS["solorl_hip.hip"][:3]
 # units whose object goes into a directory of its own under OBJ.  tests/test_build_cpu.py pins what lies directly in OBJ -- the five
 # engine parts, PPO, normalisation -- and existing tests are not rewritten for a new unit, so a new unit's object is kept beside them,
 # not among them; it is built, re-flagged and linked like every other (needs_build and build go by _jobs, not by the directory listing).
 UNIT_SUBDIR = {"solorl_kin.hip": "kin", "solorl_dyn.hip": "dyn", "solorl_shape.hip": "shape", "solorl_channel.hip": "channel",
-               "solorl_command.hip": "command", "solorl_term.hip": "term", "solorl_reset.hip": "reset"}
+               "solorl_command.hip": "command", "solorl_term.hip": "term", "solorl_reset.hip": "reset", "solorl_critic.hip": "critic"}
 LIB = os.path.join(HERE, "_lib", "libsolorl_hip.so")
 OBJ = os.path.join(HERE, "_lib", "obj")
 

@@ -1564,7 +1564,7 @@ Outputs make_outputs(float* obs_out, float* reward_out, uint8_t* done_out, const
 int check_policy_tail(const solorl_env* h, const solorl_policy_params* p, const char* who) {
   const std::string w(who);
   if (h->f64 || !h->team || h->sort) return fail(SOLORL_ERR_INVALID, w + " needs the fp32 team-mode engine without contact-count sorting (the defaults)");
-  if (p->hidden != 64 || p->obs_dim != h->O || p->act_dim != h->n || (h->O & 3) || h->O > 88 || h->L.H > 1)     // (step_team copies history levels 0 and 1 to LDS)
+  if (p->hidden != 64 || p->critic_obs_dim != 0 || p->obs_dim != h->O || p->act_dim != h->n || (h->O & 3) || h->O > 88 || h->L.H > 1)     // (step_team copies history levels 0 and 1 to LDS)
     return fail(SOLORL_ERR_INVALID, w + ": the policy must be the MLP of hidden size 64 on this env's observation / action sizes, obs_dim a multiple of 4 "
                                         "and at most 88 (zero or one history level)");
   const void* ptrs[] = {p->critic_w0, p->critic_b0, p->critic_w1, p->critic_b1, p->critic_w2, p->critic_b2, p->actor_w0, p->actor_b0, p->actor_w1, p->actor_b1,

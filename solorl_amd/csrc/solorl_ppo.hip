@@ -372,10 +372,22 @@ policy_act_mfma_kernel(CRITIC_ARGS, ACTOR_ARGS, const float* __restrict__ obs, c
   else act_net_mfma<O, A, true>(aw0, ab0, aw1, ab1, awh, abh, logstd, obs, noise, n, value_out, action_out, logp_out);
 }
 
+// The asymmetric actor-critic (solorl_policy_params.critic_obs_dim = OC != 0): the critic's workgroups run the same net at its own
+// width on rows of their own.  NetRegs<96, 1> holds 96 + 64 + 32 weight registers (the symmetric 84-wide net: 84 + 64 + 32).
+template <int O, int OC, int A>
+__global__ void __launch_bounds__(64)
+policy_act_critic_mfma_kernel(CRITIC_ARGS, ACTOR_ARGS, const float* __restrict__ obs, const float* __restrict__ cobs, const float* __restrict__ noise, int n,
+                              float* value_out, float* action_out, float* logp_out) {
+  if (blockIdx.y == 0) act_net_mfma<OC, A, false>(cw0, cb0, cw1, cb1, cwh, cbh, nullptr, cobs, noise, n, value_out, action_out, logp_out);
+  else act_net_mfma<O, A, true>(aw0, ab0, aw1, ab1, awh, abh, logstd, obs, noise, n, value_out, action_out, logp_out);
+}
+
 // ---------------------------------------------------------------- stage 1 on MFMA: grid (ceil(m / 128), 2), workgroups of four wavefronts,
 // one net per workgroup with its operand image in LDS (NetLds), one 32-row tile per wavefront (= one row of partials per 32 samples)
-template <int O, int A, bool ACTOR>
-__device__ __forceinline__ void grad_net_mfma(NET_ARGS, const float* __restrict__ logstd, const solorl_ppo_batch& B, float* xt0, float* xt1,
+// WX: this net writes its gathered input rows to xt0 (symmetric: the critic writes the shared ones; asymmetric: each net its own);
+// rows: the [n][O] rollout rows this net reads (symmetric: B.obs)
+template <int O, int A, bool ACTOR, bool WX = !ACTOR>
+__device__ __forceinline__ void grad_net_mfma(NET_ARGS, const float* __restrict__ logstd, const float* __restrict__ rows, const solorl_ppo_batch& B, float* xt0, float* xt1,
                                               float* xt2, float* g1, float* g2, float* gh, float* partials, float4* image) {
   constexpr int NOUT = ACTOR ? A : 1;
   using NR = NetLds<O, NOUT>;
@@ -393,7 +405,7 @@ __device__ __forceinline__ void grad_net_mfma(NET_ARGS, const float* __restrict_
 #endif
   const long long s = B.perm[*B.offset + r];
   ObsRow<O> X;
-  X.load(B.obs + (size_t)s * O, h);
+  X.load(rows + (size_t)s * O, h);
   const float sc_ret = B.ret[s], sc_vp = B.vpred[s], sc_adv = B.adv[s], sc_olp = B.old_logp[s];
   float sc_act[ACTOR ? 16 : 1] = {};           // the row's actions, in the head's D layout
   if constexpr (ACTOR) {
@@ -433,7 +445,7 @@ __device__ __forceinline__ void grad_net_mfma(NET_ARGS, const float* __restrict_
     };
     mfma_forward<O, NOUT>(R, b0, b1, bh, X, h, h1, h2, dh,
         [&](int i0, const float (&x)[4]) {
-          if (!ACTOR && st) {
+          if (WX && st) {
 #pragma unroll
             for (int t = 0; t < 4; ++t) if (i0 + t < O) xt0[(unsigned)((tile * O + i0 + t) * 32 + c)] = x[t];
           }
@@ -550,8 +562,17 @@ template <int O, int A>
 __global__ void __launch_bounds__(256, 2)
 ppo_grad_stage1_mfma_kernel(CRITIC_ARGS, ACTOR_ARGS, const solorl_ppo_batch B, const solorl_ppo_stage1 W) {
   extern __shared__ float4 stage1_image[];         // stage1_lds_bytes<O, A>() of dynamic LDS: 64-68 KB, two workgroups per CU
-  if (blockIdx.y == 0) grad_net_mfma<O, A, false>(cw0, cb0, cw1, cb1, cwh, cbh, nullptr, B, W.xt0, W.c_xt1, W.c_xt2, W.c_g1, W.c_g2, W.c_gh, W.partials, stage1_image);
-  else grad_net_mfma<O, A, true>(aw0, ab0, aw1, ab1, awh, abh, logstd, B, W.xt0, W.a_xt1, W.a_xt2, W.a_g1, W.a_g2, W.a_gh, W.partials, stage1_image);
+  if (blockIdx.y == 0) grad_net_mfma<O, A, false>(cw0, cb0, cw1, cb1, cwh, cbh, nullptr, B.obs, B, W.xt0, W.c_xt1, W.c_xt2, W.c_g1, W.c_g2, W.c_gh, W.partials, stage1_image);
+  else grad_net_mfma<O, A, true>(aw0, ab0, aw1, ab1, awh, abh, logstd, B.obs, B, W.xt0, W.a_xt1, W.a_xt2, W.a_g1, W.a_g2, W.a_gh, W.partials, stage1_image);
+}
+// asymmetric: the critic half at OC on the critic rows writes the critic xt0, the actor half writes the actor's xt0 (W.xt0)
+template <int O, int OC, int A> constexpr int stage1_critic_lds_bytes() { return NetLds<O, A>::BYTES > NetLds<OC, 1>::BYTES ? NetLds<O, A>::BYTES : NetLds<OC, 1>::BYTES; }
+template <int O, int OC, int A>
+__global__ void __launch_bounds__(256, 2)
+ppo_grad_stage1_critic_mfma_kernel(CRITIC_ARGS, ACTOR_ARGS, const solorl_ppo_batch B, const solorl_ppo_stage1 W, const float* __restrict__ cobs, float* cxt0) {
+  extern __shared__ float4 stage1_image[];         // stage1_critic_lds_bytes<O, OC, A>(): at most 66 KB (OC = 96), two workgroups per CU
+  if (blockIdx.y == 0) grad_net_mfma<OC, A, false, true>(cw0, cb0, cw1, cb1, cwh, cbh, nullptr, cobs, B, cxt0, W.c_xt1, W.c_xt2, W.c_g1, W.c_g2, W.c_gh, W.partials, stage1_image);
+  else grad_net_mfma<O, A, true, true>(aw0, ab0, aw1, ab1, awh, abh, logstd, B.obs, B, W.xt0, W.a_xt1, W.a_xt2, W.a_g1, W.a_g2, W.a_gh, W.partials, stage1_image);
 }
 
 // ---------------------------------------------------------------- stage 2 on MFMA: d W = G . X^T with the ROW index as K
@@ -686,8 +707,8 @@ __global__ void __launch_bounds__(64) ppo_grad_stage2_mfma_kernel(const Stage2Ar
 // The chunking of a mini-batch of m rows: every layer gets wavefronts in proportion to its tile count (6 : 4 : 2 for obs -> 64 -> 64 ->
 // head at 76 inputs), at most STAGE2_WAVES in all, so that all wavefronts carry the same number of MFMAs.  Chunks are multiples of 32 rows.
 struct Stage2Plan { int nchunks[6], mchunk[6], wave0[6], sbase[6], off[6], nwaves, total, scratch; };
-inline Stage2Plan stage2_plan(int O, int A, int m) {
-  const int U[6] = {H, H, 1, H, H, A}, K1[6] = {O + 1, H + 1, H + 1, O + 1, H + 1, H + 1};
+inline Stage2Plan stage2_plan(int O, int OC, int A, int m) {      // OC: the critic's input width (= O for the symmetric policy)
+  const int U[6] = {H, H, 1, H, H, A}, K1[6] = {OC + 1, H + 1, H + 1, O + 1, H + 1, H + 1};
   Stage2Plan P{};
   int tiles[6], all = 0;
   for (int i = 0; i < 6; ++i) { tiles[i] = ((U[i] + 31) / 32) * ((K1[i] - 1 + 31) / 32); all += tiles[i]; }
@@ -715,8 +736,8 @@ struct AdamArgs { AdamSeg seg[13]; int total; float* m; float* v; float* step; c
 // fell back to waited for one L2 round trip per tensor and pass: 22 us).  A thread owns element tid + 1024 j of tensor s for every
 // (s, j) -- 27-29 slots: every gradient is loaded ONCE, all loads of a phase are in flight together, the gradients stay in
 // registers between the norm and the update.
-template <int O, int A> struct AdamDims {
-  static constexpr int n(int s) { constexpr int N[13] = {H * O, H, H * H, H, H, 1, H * O, H, H * H, H, A * H, A, A}; return N[s]; }
+template <int O, int A, int OC = O> struct AdamDims {
+  static constexpr int n(int s) { constexpr int N[13] = {H * OC, H, H * H, H, H, 1, H * O, H, H * H, H, A * H, A, A}; return N[s]; }
   static constexpr int cnt(int s) { return (n(s) + 1023) / 1024; }
   static constexpr int base(int s) { int b = 0; for (int i = 0; i < s; ++i) b += cnt(i); return b; }
   static constexpr int SLOTS = base(13);
@@ -725,9 +746,7 @@ template <int O, int A> struct AdamDims {
   static constexpr int GROUP = 3, NGROUPS = (SLOTS + GROUP - 1) / GROUP, AHEAD = 2;     // update phase: groups of three slots, two groups in flight ahead of the
                                                                                         // one being updated (128 registers at 1024 threads; ONE group ahead: a memory round trip per group, 12 us)
 };
-template <int O, int A>
-__global__ void __launch_bounds__(1024) ppo_clip_adam_kernel(const AdamArgs K) {
-  using D = AdamDims<O, A>;
+template <typename D> __device__ __forceinline__ void clip_adam_body(const AdamArgs& K) {
   __shared__ float red[16];
   __shared__ float coef_s, step_size_s, inv_sqrt_bc2_s;
   const unsigned tid = threadIdx.x;        // (unsigned element offsets: scalar base + 32-bit vector offset addressing, no 64-bit address registers)
@@ -803,6 +822,10 @@ __global__ void __launch_bounds__(1024) ppo_clip_adam_kernel(const AdamArgs K) {
   // (every thread read *K.step before the first barrier)
   if (tid == 0) { *K.step = step; if (K.offset) *K.offset += K.inc; }
 }
+template <int O, int A>
+__global__ void __launch_bounds__(1024) ppo_clip_adam_kernel(const AdamArgs K) { clip_adam_body<AdamDims<O, A>>(K); }
+template <int O, int OC, int A>
+__global__ void __launch_bounds__(1024) ppo_clip_adam_critic_kernel(const AdamArgs K) { clip_adam_body<AdamDims<O, A, OC>>(K); }
 
 // observation widths of zero or one history level (14 + 2 n (+ 4 pointGoal), x 1 or x 2), action widths n = 8 / 12; and the
 // zero-history widths with the three velocity-command words of solorl_commands behind them (odd: every access goes word by word)
@@ -818,6 +841,31 @@ int fail_dims() {
                                           "(38, 42, 76 or 84 x 12; 30, 34, 60 or 68 x 8) and for zero history levels with velocity commands "
                                           "(41 or 45 x 12; 33 or 37 x 8); use the PyTorch path for other shapes");
 }
+// (actor width, critic width, action width) of the asymmetric policy: walk and stand at zero and one history level, and the commanded
+// zero-history widths; the critic's rows are the engine's observation + SOLORL_CRITIC_PRIV words
+#define SOLO_DIMS3_LIST(X) X(38, 58, 12) X(41, 58, 12) X(76, 96, 12) X(30, 50, 8) X(33, 50, 8) X(60, 80, 8)
+bool dims3_supported(int O, int OC, int A) {
+#define SOLO_DIMS3(O_, C_, A_) if (O == O_ && OC == C_ && A == A_) return true;
+  SOLO_DIMS3_LIST(SOLO_DIMS3)
+#undef SOLO_DIMS3
+  return false;
+}
+int fail_dims3() {
+  return solorl_fail_(SOLORL_ERR_INVALID, "policy kernels with a critic width are built for (obs, critic, act) = (38, 58, 12), (41, 58, 12), (76, 96, 12), "
+                                          "(30, 50, 8), (33, 50, 8), (60, 80, 8); the symmetric ones for 38, 42, 76 or 84 x 12; 30, 34, 60 or 68 x 8; "
+                                          "use the PyTorch path for other shapes");
+}
+int fail_critic_width() {
+  return solorl_fail_(SOLORL_ERR_INVALID, "this entry point takes the symmetric policy (38, 42, 76 or 84 x 12; 30, 34, 60 or 68 x 8 ...): critic_obs_dim must be 0 "
+                                          "-- a policy with a critic width goes through solorl_policy_act_critic / solorl_ppo_grad_stage1_critic / "
+                                          "solorl_ppo_grad_stage2_critic");
+}
+template <typename F> int dispatch_dims3(int O, int OC, int A, F&& f) {
+#define SOLO_DIMS3(O_, C_, A_) if (O == O_ && OC == C_ && A == A_) return f(std::integral_constant<int, O_>(), std::integral_constant<int, C_>(), std::integral_constant<int, A_>());
+  SOLO_DIMS3_LIST(SOLO_DIMS3)
+#undef SOLO_DIMS3
+  return fail_dims3();
+}
 template <typename F> int dispatch_dims(int O, int A, F&& f) {
 #define SOLO_DIMS(O_, A_) if (O == O_ && A == A_) return f(std::integral_constant<int, O_>(), std::integral_constant<int, A_>());
   SOLO_DIMS_LIST(SOLO_DIMS)
@@ -827,7 +875,8 @@ template <typename F> int dispatch_dims(int O, int A, F&& f) {
 
 // every policy entry point: the parameters, the shape (stage 2's kernel is not reached through dispatch_dims and computes only the tile
 // counts it instantiates), then the device -- so an unsupported shape is refused on a machine without a GPU too
-int check_policy(const solorl_policy_params* p, int device_id) {
+// critic: 0 = an entry point of the symmetric policy (refuses a critic width), 1 = one of the asymmetric policy (needs one), 2 = either
+int check_policy(const solorl_policy_params* p, int device_id, int critic = 0) {
   if (!p) return solorl_fail_(SOLORL_ERR_INVALID, "null policy parameters");
   if (p->hidden != H) return solorl_fail_(SOLORL_ERR_INVALID, "policy kernels are built for hidden size 64");
   const void* ptrs[] = {p->critic_w0, p->critic_b0, p->critic_w1, p->critic_b1, p->critic_w2, p->critic_b2, p->actor_w0, p->actor_b0,
@@ -835,9 +884,13 @@ int check_policy(const solorl_policy_params* p, int device_id) {
   for (const void* q : ptrs) if (!q) return solorl_fail_(SOLORL_ERR_INVALID, "null policy parameter pointer");
   // the kernels read weight rows as float4 (16 consecutive bytes per lane): every parameter tensor must start on a 16-byte
   // boundary (torch allocations do; an offset view passed by another C-ABI caller would fault on the GPU instead)
-  const void* vec[] = {p->critic_w1, p->actor_w1, p->critic_w2, p->mean_w, p->obs_dim % 4 == 0 ? p->critic_w0 : nullptr, p->obs_dim % 4 == 0 ? p->actor_w0 : nullptr};
+  const int cw = p->critic_obs_dim != 0 ? p->critic_obs_dim : p->obs_dim;       // the width of the critic's first layer
+  const void* vec[] = {p->critic_w1, p->actor_w1, p->critic_w2, p->mean_w, cw % 4 == 0 ? p->critic_w0 : nullptr, p->obs_dim % 4 == 0 ? p->actor_w0 : nullptr};
   for (const void* q : vec) if (reinterpret_cast<uintptr_t>(q) & 15u) return solorl_fail_(SOLORL_ERR_INVALID, "policy weight matrices must be 16-byte aligned (rows are read as float4)");
-  if (!dims_supported(p->obs_dim, p->act_dim)) return fail_dims();
+  if (p->critic_obs_dim != 0 && critic == 0) return fail_critic_width();
+  if (p->critic_obs_dim == 0 && critic == 1) return fail_dims3();
+  if (p->critic_obs_dim != 0 ? !dims3_supported(p->obs_dim, p->critic_obs_dim, p->act_dim) : !dims_supported(p->obs_dim, p->act_dim))
+    return p->critic_obs_dim != 0 ? fail_dims3() : fail_dims();
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return solorl_fail_(SOLORL_ERR_NODEVICE, "no HIP device available (no CPU fallback)");
   if (device_id < 0 || device_id >= ndev) return solorl_fail_(SOLORL_ERR_NODEVICE, "device_id out of range");
@@ -856,6 +909,50 @@ template <int O, int A> int stage1_raise_lds_limit(int device_id) {
                           stage1_lds_bytes<O, A>()) != hipSuccess)
     return solorl_fail_(SOLORL_ERR_HIP, "ppo_grad_stage1_mfma_kernel: cannot raise the dynamic LDS limit");
   raised[device_id] = true;
+  return 0;
+}
+
+template <int O, int OC, int A> int stage1_critic_raise_lds_limit(int device_id) {
+  static std::mutex mu;
+  static bool raised[64] = {};
+  if (device_id < 0 || device_id >= 64) return solorl_fail_(SOLORL_ERR_NODEVICE, "ppo_grad_stage1_critic_mfma_kernel: device_id beyond the 64 the library tracks");
+  std::lock_guard<std::mutex> lock(mu);
+  if (raised[device_id]) return 0;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_grad_stage1_critic_mfma_kernel<O, OC, A>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          stage1_critic_lds_bytes<O, OC, A>()) != hipSuccess)
+    return solorl_fail_(SOLORL_ERR_HIP, "ppo_grad_stage1_critic_mfma_kernel: cannot raise the dynamic LDS limit");
+  raised[device_id] = true;
+  return 0;
+}
+
+// stage 2 and 3 of both forms: xt0c = the critic's gathered rows (the shared xt0 for the symmetric policy), OC its width
+int grad_stage2_launch(const solorl_policy_params* p, const solorl_ppo_stage1* work, const float* xt0c, int OC, int m, const solorl_ppo_grads* out, void* stream) {
+  const int O = p->obs_dim, A = p->act_dim;
+  Stage3Args T;
+  Stage2Args& S = T.S;
+  const LayerDesc L[6] = {
+      {work->c_g1, xt0c, out->critic_w0, out->critic_b0, H, OC + 1, 0, 0}, {work->c_g2, work->c_xt1, out->critic_w1, out->critic_b1, H, H + 1, 0, 0},
+      {work->c_gh, work->c_xt2, out->critic_w2, out->critic_b2, 1, H + 1, 0, 0}, {work->a_g1, work->xt0, out->actor_w0, out->actor_b0, H, O + 1, 0, 0},
+      {work->a_g2, work->a_xt1, out->actor_w1, out->actor_b1, H, H + 1, 0, 0}, {work->a_gh, work->a_xt2, out->mean_w, out->mean_b, A, H + 1, 0, 0}};
+  if (m % 64 != 0) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage2: m must be a multiple of 64 rows");
+  const Stage2Plan plan = stage2_plan(O, OC, A, m);
+  S.m = m; S.scratch = out->scratch; S.total = plan.total; S.nwaves = plan.nwaves; S.reserved = 0;
+  for (int i = 0; i < 6; ++i) {
+    S.L[i] = L[i]; S.L[i].off = plan.off[i]; S.L[i].nchunks = plan.nchunks[i]; S.L[i].mchunk = plan.mchunk[i]; S.L[i].wave0 = plan.wave0[i];
+    S.L[i].sbase = plan.sbase[i];
+  }
+  T.partials = work->partials; T.nwaves = (m + 31) / 32; T.A = A; T.logstd = p->logstd; T.logstd_grad = out->logstd;
+  T.loss_sums = out->loss_sums; T.logstd_sum = out->logstd_sum; T.entropy_coef = out->entropy_coef;
+  hipLaunchKernelGGL(ppo_grad_stage2_mfma_kernel, dim3(S.nwaves), dim3(64), 0, (hipStream_t)stream, S);
+  hipLaunchKernelGGL(ppo_grad_stage3_kernel, dim3((S.total + 15) / 16 + 3 + A), dim3(256), 0, (hipStream_t)stream, T);
+  return hipGetLastError() == hipSuccess ? 0 : solorl_fail_(SOLORL_ERR_HIP, "ppo_grad_stage2/3 launch");
+}
+int grad_stage2_check(const solorl_ppo_stage1* work, int m, const solorl_ppo_grads* out) {
+  if (!work || !out || m < 1) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage2: null argument or m < 1");
+  const void* ptrs[] = {out->critic_w0, out->critic_b0, out->critic_w1, out->critic_b1, out->critic_w2, out->critic_b2, out->actor_w0,
+                        out->actor_b0, out->actor_w1, out->actor_b1, out->mean_w, out->mean_b, out->logstd, out->loss_sums, out->logstd_sum,
+                        out->scratch, work->xt0, work->partials};
+  for (const void* q : ptrs) if (!q) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage2: null array");
   return 0;
 }
 
@@ -902,47 +999,79 @@ int solorl_ppo_grad_stage1(const solorl_policy_params* p, const solorl_ppo_batch
 }
 
 int solorl_ppo_grad_count(int obs_dim, int act_dim) { return 2 * H * (obs_dim + 1) + 2 * H * (H + 1) + (H + 1) + act_dim * (H + 1); }
+int solorl_ppo_grad_count2(int obs_dim, int critic_obs_dim, int act_dim) {
+  return H * (critic_obs_dim + 1) + H * (obs_dim + 1) + 2 * H * (H + 1) + (H + 1) + act_dim * (H + 1);
+}
 
-int solorl_ppo_scratch_count(int obs_dim, int act_dim, int m) { return m < 1 ? 0 : stage2_plan(obs_dim, act_dim, m).scratch; }
+int solorl_ppo_scratch_count(int obs_dim, int act_dim, int m) { return m < 1 ? 0 : stage2_plan(obs_dim, obs_dim, act_dim, m).scratch; }
+int solorl_ppo_scratch_count2(int obs_dim, int critic_obs_dim, int act_dim, int m) { return m < 1 ? 0 : stage2_plan(obs_dim, critic_obs_dim, act_dim, m).scratch; }
 
 int solorl_ppo_grad_stage2(const solorl_policy_params* p, const solorl_ppo_stage1* work, int m, const solorl_ppo_grads* out, int device_id,
                            void* stream) {
   if (int rc = check_policy(p, device_id)) return rc;
-  if (!work || !out || m < 1) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage2: null argument or m < 1");
-  const void* ptrs[] = {out->critic_w0, out->critic_b0, out->critic_w1, out->critic_b1, out->critic_w2, out->critic_b2, out->actor_w0,
-                        out->actor_b0, out->actor_w1, out->actor_b1, out->mean_w, out->mean_b, out->logstd, out->loss_sums, out->logstd_sum,
-                        out->scratch, work->xt0, work->partials};
-  for (const void* q : ptrs) if (!q) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage2: null array");
-  const int O = p->obs_dim, A = p->act_dim;
-  Stage3Args T;
-  Stage2Args& S = T.S;
-  const LayerDesc L[6] = {
-      {work->c_g1, work->xt0, out->critic_w0, out->critic_b0, H, O + 1, 0, 0}, {work->c_g2, work->c_xt1, out->critic_w1, out->critic_b1, H, H + 1, 0, 0},
-      {work->c_gh, work->c_xt2, out->critic_w2, out->critic_b2, 1, H + 1, 0, 0}, {work->a_g1, work->xt0, out->actor_w0, out->actor_b0, H, O + 1, 0, 0},
-      {work->a_g2, work->a_xt1, out->actor_w1, out->actor_b1, H, H + 1, 0, 0}, {work->a_gh, work->a_xt2, out->mean_w, out->mean_b, A, H + 1, 0, 0}};
-  if (m % 64 != 0) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage2: m must be a multiple of 64 rows");
-  const Stage2Plan plan = stage2_plan(O, A, m);
-  S.m = m; S.scratch = out->scratch; S.total = plan.total; S.nwaves = plan.nwaves; S.reserved = 0;
-  for (int i = 0; i < 6; ++i) {
-    S.L[i] = L[i]; S.L[i].off = plan.off[i]; S.L[i].nchunks = plan.nchunks[i]; S.L[i].mchunk = plan.mchunk[i]; S.L[i].wave0 = plan.wave0[i];
-    S.L[i].sbase = plan.sbase[i];
-  }
-  T.partials = work->partials; T.nwaves = (m + 31) / 32; T.A = A; T.logstd = p->logstd; T.logstd_grad = out->logstd;
-  T.loss_sums = out->loss_sums; T.logstd_sum = out->logstd_sum; T.entropy_coef = out->entropy_coef;
-  hipLaunchKernelGGL(ppo_grad_stage2_mfma_kernel, dim3(S.nwaves), dim3(64), 0, (hipStream_t)stream, S);
-  hipLaunchKernelGGL(ppo_grad_stage3_kernel, dim3((S.total + 15) / 16 + 3 + A), dim3(256), 0, (hipStream_t)stream, T);
-  return hipGetLastError() == hipSuccess ? 0 : solorl_fail_(SOLORL_ERR_HIP, "ppo_grad_stage2/3 launch");
+  if (int rc = grad_stage2_check(work, m, out)) return rc;
+  return grad_stage2_launch(p, work, work->xt0, p->obs_dim, m, out, stream);
+}
+
+int solorl_policy_act_critic(const solorl_policy_params* p, const float* obs, const float* critic_obs, const float* noise, int n, float* value_out,
+                             float* action_out, float* logp_out, int device_id, void* stream) {
+  if (int rc = check_policy(p, device_id, 1)) return rc;
+  if (!obs || !critic_obs || !value_out || !action_out || !logp_out || n < 1) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_policy_act_critic: null array or n < 1");
+  if ((p->obs_dim % 4 == 0 && (reinterpret_cast<uintptr_t>(obs) & 15u)) || (p->critic_obs_dim % 4 == 0 && (reinterpret_cast<uintptr_t>(critic_obs) & 15u)))
+    return solorl_fail_(SOLORL_ERR_INVALID, "solorl_policy_act_critic: rows of a width that is a multiple of 4 must be 16-byte aligned (they are read as float4)");
+  const solorl_policy_params P = *p;
+  return dispatch_dims3(P.obs_dim, P.critic_obs_dim, P.act_dim, [&](auto oc, auto cc, auto ac) {
+    constexpr int O = decltype(oc)::value, OC = decltype(cc)::value, A = decltype(ac)::value;
+    hipLaunchKernelGGL((policy_act_critic_mfma_kernel<O, OC, A>), dim3((n + 31) / 32, 2), dim3(64), 0, (hipStream_t)stream, CRITIC_PASS, ACTOR_PASS, obs,
+                       critic_obs, noise, n, value_out, action_out, logp_out);
+    return hipGetLastError() == hipSuccess ? 0 : solorl_fail_(SOLORL_ERR_HIP, "policy_act_critic_mfma_kernel launch");
+  });
+}
+
+int solorl_ppo_grad_stage1_critic(const solorl_policy_params* p, const solorl_ppo_batch* batch, const float* critic_obs, const solorl_ppo_stage1* work,
+                                  float* critic_xt0, int device_id, void* stream) {
+  if (int rc = check_policy(p, device_id, 1)) return rc;
+  if (!batch || !work || !critic_obs || !critic_xt0 || batch->m < 1) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage1_critic: null argument or m < 1");
+  if (batch->m % 32 != 0) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage1_critic: m must be a multiple of 32 rows (the work arrays are written in tiles of 32)");
+  const int widest = p->critic_obs_dim > H ? (p->critic_obs_dim > p->obs_dim ? p->critic_obs_dim : p->obs_dim) : (p->obs_dim > H ? p->obs_dim : H);
+  if ((long long)batch->m * widest >= (1LL << 31))
+    return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage1_critic: mini-batch too large (the [unit][row] arrays are indexed with 32 bits)");
+  const void* ptrs[] = {batch->obs, batch->actions, batch->old_logp, batch->adv, batch->vpred, batch->ret, batch->perm, batch->offset,
+                        work->xt0, work->c_xt1, work->c_xt2, work->c_g1, work->c_g2, work->c_gh, work->a_xt1, work->a_xt2, work->a_g1,
+                        work->a_g2, work->a_gh, work->partials};
+  for (const void* q : ptrs) if (!q) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage1_critic: null array");
+  if ((p->obs_dim % 4 == 0 && (reinterpret_cast<uintptr_t>(batch->obs) & 15u)) || (p->critic_obs_dim % 4 == 0 && (reinterpret_cast<uintptr_t>(critic_obs) & 15u)))
+    return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage1_critic: rows of a width that is a multiple of 4 must be 16-byte aligned (they are read as float4)");
+  const solorl_policy_params P = *p;
+  const solorl_ppo_batch B = *batch;
+  const solorl_ppo_stage1 W = *work;
+  return dispatch_dims3(P.obs_dim, P.critic_obs_dim, P.act_dim, [&](auto oc, auto cc, auto ac) {
+    constexpr int O = decltype(oc)::value, OC = decltype(cc)::value, A = decltype(ac)::value;
+    constexpr int LDS = stage1_critic_lds_bytes<O, OC, A>();
+    if (int rc = stage1_critic_raise_lds_limit<O, OC, A>(device_id)) return rc;
+    hipLaunchKernelGGL((ppo_grad_stage1_critic_mfma_kernel<O, OC, A>), dim3((B.m + 127) / 128, 2), dim3(256), LDS, (hipStream_t)stream, CRITIC_PASS, ACTOR_PASS, B, W,
+                       critic_obs, critic_xt0);
+    return hipGetLastError() == hipSuccess ? 0 : solorl_fail_(SOLORL_ERR_HIP, "ppo_grad_stage1_critic_mfma_kernel launch");
+  });
+}
+
+int solorl_ppo_grad_stage2_critic(const solorl_policy_params* p, const solorl_ppo_stage1* work, const float* critic_xt0, int m, const solorl_ppo_grads* out,
+                                  int device_id, void* stream) {
+  if (int rc = check_policy(p, device_id, 1)) return rc;
+  if (int rc = grad_stage2_check(work, m, out)) return rc;
+  if (!critic_xt0) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage2_critic: null critic_xt0");
+  return grad_stage2_launch(p, work, critic_xt0, p->critic_obs_dim, m, out, stream);
 }
 
 int solorl_ppo_clip_adam(const solorl_policy_params* p, const solorl_ppo_grads* g, const solorl_adam_state* a, int device_id, void* stream) {
-  if (int rc = check_policy(p, device_id)) return rc;
+  if (int rc = check_policy(p, device_id, 2)) return rc;
   if (!g || !a || !a->exp_avg || !a->exp_avg_sq || !a->step || !a->lr) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_clip_adam: null argument");
-  const int O = p->obs_dim, A = p->act_dim;
+  const int O = p->obs_dim, A = p->act_dim, OC = p->critic_obs_dim != 0 ? p->critic_obs_dim : O;
   const float* ps[13] = {p->critic_w0, p->critic_b0, p->critic_w1, p->critic_b1, p->critic_w2, p->critic_b2, p->actor_w0, p->actor_b0,
                          p->actor_w1, p->actor_b1, p->mean_w, p->mean_b, p->logstd};
   const float* gs[13] = {g->critic_w0, g->critic_b0, g->critic_w1, g->critic_b1, g->critic_w2, g->critic_b2, g->actor_w0, g->actor_b0,
                          g->actor_w1, g->actor_b1, g->mean_w, g->mean_b, g->logstd};
-  const int ns[13] = {H * O, H, H * H, H, H, 1, H * O, H, H * H, H, A * H, A, A};
+  const int ns[13] = {H * OC, H, H * H, H, H, 1, H * O, H, H * H, H, A * H, A, A};
   AdamArgs K;
   int off = 0;
   for (int i = 0; i < 13; ++i) {
@@ -954,6 +1083,11 @@ int solorl_ppo_clip_adam(const solorl_policy_params* p, const solorl_ppo_grads* 
   K.b1 = a->beta1; K.b2 = a->beta2; K.eps = a->eps; K.wd = a->weight_decay; K.max_norm = a->max_grad_norm;
   K.gscale = a->grad_scale > 0.f ? a->grad_scale : 1.0f;
   K.offset = reinterpret_cast<long long*>(a->offset); K.inc = a->offset_increment;
+  if (p->critic_obs_dim != 0)
+    return dispatch_dims3(O, OC, A, [&](auto oc, auto cc, auto ac) {
+      hipLaunchKernelGGL((ppo_clip_adam_critic_kernel<decltype(oc)::value, decltype(cc)::value, decltype(ac)::value>), dim3(1), dim3(1024), 0, (hipStream_t)stream, K);
+      return hipGetLastError() == hipSuccess ? 0 : solorl_fail_(SOLORL_ERR_HIP, "ppo_clip_adam_critic_kernel launch");
+    });
   return dispatch_dims(O, A, [&](auto oc, auto ac) {
     hipLaunchKernelGGL((ppo_clip_adam_kernel<decltype(oc)::value, decltype(ac)::value>), dim3(1), dim3(1024), 0, (hipStream_t)stream, K);
     return hipGetLastError() == hipSuccess ? 0 : solorl_fail_(SOLORL_ERR_HIP, "ppo_clip_adam_kernel launch");

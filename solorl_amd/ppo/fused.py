@@ -54,6 +54,7 @@ def fused_ppo_loss(mean, logstd, values, action, old_logp, adv, vpred, ret, clip
 # Hand-written policy kernels (csrc/solorl_ppo.hip): the whole forward of Policy.act in one launch, and one PPO mini-batch's
 # gather + forward + losses + back-propagation in one launch (the weight gradients stay GEMMs).
 
+_SUPPORTED_CRITIC = {(38, 58, 12), (41, 58, 12), (76, 96, 12), (30, 50, 8), (33, 50, 8), (60, 80, 8)}     # (obs, critic rows, act): csrc SOLO_DIMS3_LIST
 _SUPPORTED = {(76, 12), (84, 12), (38, 12), (42, 12), (60, 8), (68, 8), (30, 8), (34, 8),
               (41, 12), (45, 12), (33, 8), (37, 8)}          # (... and zero history levels + the three command words of solorl_commands)
 
@@ -66,6 +67,9 @@ def policy_kernels_supported(actor_critic):
     except AttributeError:
         return False
     p = next(actor_critic.parameters())
+    oc = getattr(actor_critic, "critic_obs_dim", None)
+    if oc is not None:                    # an asymmetric policy: the shapes built with a critic width; any other keeps the PyTorch path
+        return h == 64 and (o, oc, a) in _SUPPORTED_CRITIC and b.critic[0].in_features == oc and p.is_cuda and p.dtype == torch.float32
     return h == 64 and (o, a) in _SUPPORTED and p.is_cuda and p.dtype == torch.float32
 
 
@@ -84,6 +88,7 @@ def policy_params(actor_critic):
     b, d = actor_critic.base, actor_critic.pi_dist
     P = _native.PolicyParams()
     P.obs_dim, P.hidden, P.act_dim = b.features[0].in_features, b.features[0].out_features, d.mean.out_features
+    P.critic_obs_dim = getattr(actor_critic, "critic_obs_dim", None) or 0       # 0: symmetric
     named = _named_parameters(actor_critic)
     for k, t in named.items():
         assert t.is_contiguous() and t.dtype == torch.float32 and t.is_cuda
@@ -101,15 +106,24 @@ def check_params(P):
             raise RuntimeError("policy parameter %s moved since solorl_policy_params was built; rebuild it (and any HIP graph)" % k)
 
 
-def policy_act(params, obs, noise, value_out, action_out, logp_out):
+def policy_act(params, obs, noise, value_out, action_out, logp_out, critic_obs=None):
     """Policy.act (agents/ppo/policy.py:33-49) in one launch: value_out [N,1], action_out [N,A] = mean + exp(logstd) * noise
-    (noise [N,A] standard normal, or None for the deterministic action), logp_out [N,1]."""
+    (noise [N,A] standard normal, or None for the deterministic action), logp_out [N,1].  ``critic_obs`` [N, OC]: the critic's rows
+    of an asymmetric policy (params.critic_obs_dim = OC), required by one and refused by a symmetric one (solorl_policy_act_critic)."""
     check_params(params)
     n = obs.shape[0]
     dev = obs.device
-    for t in (obs, value_out, action_out, logp_out) + (() if noise is None else (noise,)):
+    for t in (obs, value_out, action_out, logp_out) + (() if noise is None else (noise,)) + (() if critic_obs is None else (critic_obs,)):
         assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
     assert obs.shape == (n, params.obs_dim) and action_out.shape == (n, params.act_dim) and value_out.numel() == n and logp_out.numel() == n
+    assert (critic_obs is None) == (params.critic_obs_dim == 0), "critic_obs goes with a policy made with critic_obs_dim, and only with one"
+    if critic_obs is not None:
+        assert critic_obs.shape == (n, params.critic_obs_dim)
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().solorl_policy_act_critic(C.byref(params), C.c_void_p(obs.data_ptr()), C.c_void_p(critic_obs.data_ptr()),
+                                                                 C.c_void_p(0 if noise is None else noise.data_ptr()), n, C.c_void_p(value_out.data_ptr()),
+                                                                 C.c_void_p(action_out.data_ptr()), C.c_void_p(logp_out.data_ptr()), dev.index or 0, _native.stream(dev)))
+        return
     with torch.cuda.device(dev):
         _native.check(_native.lib().solorl_policy_act(C.byref(params), C.c_void_p(obs.data_ptr()),
                                                       C.c_void_p(0 if noise is None else noise.data_ptr()), n, C.c_void_p(value_out.data_ptr()),
@@ -131,6 +145,7 @@ class MiniBatchGrad:
         self.ac, self.m = actor_critic, m
         self.P = policy_params(actor_critic)
         O, A, H = self.P.obs_dim, self.P.act_dim, 64
+        OC = self.OC = self.P.critic_obs_dim          # 0: symmetric
         self.A = A
         flat = lambda x: x.reshape(n, *x.shape[2:])
         B = self.B = _native.PpoBatch()
@@ -141,6 +156,12 @@ class MiniBatchGrad:
             setattr(B, k, t.data_ptr())
         assert self._keep[0].data_ptr() == storage.obs.data_ptr() and perm.dtype == torch.long and offset.dtype == torch.long
         B.m, B.clipped_value, B.clip, B.value_coef = m, int(bool(clipped_value)), float(clip), float(value_coef)
+        # an asymmetric policy: the rollout's critic rows, gathered like obs, and the critic's own xt0 (stage 1 then writes the actor's rows to xt0)
+        self.cobs = self.cxt0 = None
+        if OC:
+            self.cobs = flat(storage.critic_obs[:-1])
+            assert self.cobs.is_contiguous() and self.cobs.data_ptr() == storage.critic_obs.data_ptr() and self.cobs.shape[1] == OC
+            self.cxt0 = torch.zeros(OC, m, device=dev)
 
         z = lambda u: torch.zeros(u, m, device=dev)
         xt = z                                # (activations [units][m]; the bias gradients are row sums of g, no row of ones)
@@ -152,7 +173,7 @@ class MiniBatchGrad:
         self.psum = torch.zeros(3 + A, device=dev)          # running sums of the partials over the steps of an update
         self.ent = torch.zeros(1, device=dev)               # running sum of sum_a logstd_a
         L = _native.lib()
-        self.scratch = torch.zeros(L.solorl_ppo_scratch_count(O, A, m), device=dev)
+        self.scratch = torch.zeros(L.solorl_ppo_scratch_count2(O, OC, A, m) if OC else L.solorl_ppo_scratch_count(O, A, m), device=dev)
         G = self.G = _native.PpoGrads()
         for k, prm in _named_parameters(actor_critic).items():
             g = prm.grad
@@ -166,6 +187,12 @@ class MiniBatchGrad:
         L = _native.lib()
         with torch.cuda.device(dev):
             st = _native.stream(dev)
+            if self.OC:
+                _native.check(L.solorl_ppo_grad_stage1_critic(C.byref(self.P), C.byref(self.B), C.c_void_p(self.cobs.data_ptr()), C.byref(self.W),
+                                                              C.c_void_p(self.cxt0.data_ptr()), dev.index or 0, st))
+                _native.check(L.solorl_ppo_grad_stage2_critic(C.byref(self.P), C.byref(self.W), C.c_void_p(self.cxt0.data_ptr()), self.m, C.byref(self.G),
+                                                              dev.index or 0, st))
+                return
             _native.check(L.solorl_ppo_grad_stage1(C.byref(self.P), C.byref(self.B), C.byref(self.W), dev.index or 0, st))
             _native.check(L.solorl_ppo_grad_stage2(C.byref(self.P), C.byref(self.W), self.m, C.byref(self.G), dev.index or 0, st))
 
@@ -187,7 +214,9 @@ class ClipAdam:
     def __init__(self, mini_batch_grad, lr, max_grad_norm, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, offset=None, offset_increment=0, grad_scale=1.0):
         mb = mini_batch_grad
         dev = mb.psum.device
-        n = _native.lib().solorl_ppo_grad_count(mb.P.obs_dim, mb.P.act_dim) + mb.P.act_dim
+        L = _native.lib()
+        n = (L.solorl_ppo_grad_count2(mb.P.obs_dim, mb.P.critic_obs_dim, mb.P.act_dim) if mb.P.critic_obs_dim
+             else L.solorl_ppo_grad_count(mb.P.obs_dim, mb.P.act_dim)) + mb.P.act_dim
         assert n == sum(p.numel() for p in mb.ac.parameters())
         self.P, self.G, self.dev = mb.P, mb.G, dev
         self.exp_avg, self.exp_avg_sq = torch.zeros(n, device=dev), torch.zeros(n, device=dev)

@@ -113,6 +113,9 @@ class GraphedRollout:
         # the arithmetic of train.rollout() with every result written where it is stored: the policy's outputs and the engine's
         # observations / rewards / done flags go straight into storage-side rows (the C ABI takes caller-owned pointers) -- two
         # launches per step (act, env step) instead of 35, and launches are what a step costs besides the env kernel
+        # an asymmetric policy (storage with critic rows): the critic reads st.critic_obs[t], which the env writes beside st.obs[t + 1]:
+        # one policy launch per step (solorl_policy_act_critic where the shape is built, else act_into) plus the env's launches
+        asym = getattr(st, "critic_obs", None) is not None
         fused = _kernels_enabled() and policy_kernels_supported(self.ac)
         if fused:                            # one launch for the whole of Policy.act (csrc/solorl_ppo.hip)
             self._pp = policy_params(self.ac)
@@ -149,9 +152,15 @@ class GraphedRollout:
                     self.envs.step_inplace(st.actions[t], obs_out=st.obs[t + 1], rew_out=st.rewards[t], done_out=done[t])
                 continue
             if fused:
-                policy_act(self._pp, st.obs[t], noise[t], st.value_preds[t], st.actions[t], st.action_log_probs[t])
+                policy_act(self._pp, st.obs[t], noise[t], st.value_preds[t], st.actions[t], st.action_log_probs[t],
+                           critic_obs=st.critic_obs[t] if asym else None)
+            elif asym:
+                self.ac.act_into(st.obs[t], st.value_preds[t], st.actions[t], st.action_log_probs[t], critic_inputs=st.critic_obs[t])
             else:
                 self.ac.act_into(st.obs[t], st.value_preds[t], st.actions[t], st.action_log_probs[t])
+            if asym:
+                self.envs.step_inplace(st.actions[t], obs_out=st.obs[t + 1], rew_out=st.rewards[t], done_out=done[t], critic_obs_out=st.critic_obs[t + 1])
+                continue
             self.envs.step_inplace(st.actions[t], obs_out=st.obs[t + 1], rew_out=st.rewards[t], done_out=done[t])
         torch.sub(torch.ones((), device=st.device), done, out=st.masks[1:].view(self.T, st.num_agents))
 
@@ -204,6 +213,8 @@ class GraphedPPO(PPO):
                      flat(storage.action_log_probs))
         assert all(s.data_ptr() == b.data_ptr() for s, b in zip(self._src, (storage.obs, storage.actions, storage.value_preds,
                                                                             storage.returns, storage.action_log_probs)))
+        # the critic's rows of an asymmetric policy, gathered like the actor's
+        self._csrc = flat(storage.critic_obs[:-1]) if getattr(storage, "critic_obs", None) is not None else None
         self._adv = torch.zeros(n, 1, device=dev)
         self._perm = torch.zeros(n, dtype=torch.long, device=dev)
         self._off = torch.zeros((), dtype=torch.long, device=dev)
@@ -229,12 +240,13 @@ class GraphedPPO(PPO):
             self._off += m
             obs_b, act_b, vpred_b, ret_b, old_lp_b = (s.index_select(0, idx) for s in self._src)
             adv_b = self._adv.index_select(0, idx)
+            critic = {} if self._csrc is None else {"critic_inputs": self._csrc.index_select(0, idx)}
             if self.fused_loss:       # one HIP launch for log-prob, both losses and their head gradients (ppo/fused.py)
-                values, mean, logstd = self.actor_critic.heads(obs_b)
+                values, mean, logstd = self.actor_critic.heads(obs_b, **critic)
                 loss, value_loss, action_loss, entropy = fused_ppo_loss(mean, logstd, values, act_b, old_lp_b, adv_b, vpred_b, ret_b, clip,
                                                                         self.value_loss_coef, self.entropy_coef, self.use_clipped_value_loss)
             else:
-                values, logp, entropy = self.actor_critic.evaluate_actions(obs_b, act_b)
+                values, logp, entropy = self.actor_critic.evaluate_actions(obs_b, act_b, **critic)
                 ratio = torch.exp(logp - old_lp_b)
                 action_loss = -torch.min(ratio * adv_b, torch.clamp(ratio, 1.0 - clip, 1.0 + clip) * adv_b).mean()
                 if self.use_clipped_value_loss:

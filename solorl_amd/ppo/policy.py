@@ -6,6 +6,10 @@ get_value / evaluate_actions, :33-58) with parameter names kept identical so `so
     base.critic.{0,2,4}.{weight,bias}   separate tanh MLP critic             (policy.py:70-73)
     pi_dist.mean.{weight,bias}, pi_dist.logstd   state-independent diagonal Gaussian (:138-148)
 
+``Policy(..., critic_obs_dim=OC)`` is the asymmetric actor-critic: ``base.critic.0`` takes rows of OC words of their own (the
+privileged critic rows of SoloVecEnv(critic_obs=...), include/solorl.h solorl_critic_obs) and every method takes them as
+``critic_inputs``; the parameter names are unchanged, so a checkpoint tells the two apart by the shape of ``base.critic.0.weight``.
+
 Only Box action spaces exist on the hot path (baseEnv.py:23-25); the reference's Discrete /
 MultiDiscrete heads cannot even be constructed at that commit.
 """
@@ -64,16 +68,17 @@ def ortho_(linear, gain=math.sqrt(2.0)):
 
 
 class MLPBase(nn.Module):
-    def __init__(self, num_inputs, hidden_size=64):
+    def __init__(self, num_inputs, hidden_size=64, critic_inputs=None):
         super().__init__()
         self.output_size = hidden_size
         h = hidden_size
         self.features = nn.Sequential(ortho_(Linear(num_inputs, h)), nn.Tanh(), ortho_(Linear(h, h)), nn.Tanh())
-        self.critic = nn.Sequential(ortho_(Linear(num_inputs, h)), nn.Tanh(), ortho_(Linear(h, h)), nn.Tanh(),
-                                    ortho_(Linear(h, 1)))
+        # (built in this order whatever the critic's width: the random draws of the initialisation are the symmetric policy's)
+        self.critic = nn.Sequential(ortho_(Linear(num_inputs if critic_inputs is None else critic_inputs, h)), nn.Tanh(), ortho_(Linear(h, h)),
+                                    nn.Tanh(), ortho_(Linear(h, 1)))
 
-    def forward(self, x):
-        return self.critic(x), self.features(x)
+    def forward(self, x, critic_x=None):
+        return self.critic(x if critic_x is None else critic_x), self.features(x)
 
 
 class DiagGaussianHead(nn.Module):
@@ -101,32 +106,47 @@ def gaussian_entropy_mean(mean, logstd):
 
 
 class Policy(nn.Module):
-    def __init__(self, obs_shape, action_space, base=None, base_kwargs=None):
+    def __init__(self, obs_shape, action_space, base=None, base_kwargs=None, critic_obs_dim=None):
         super().__init__()
         if len(obs_shape) != 1:
             raise NotImplementedError("only flat observations (the TransformerBase of policy.py:83-120 serves the "
                                       "out-of-scope Timings envs)")
         if action_space.__class__.__name__ != "Box":
             raise NotImplementedError("only Box action spaces (baseEnv.py:23-25)")
-        self.base = MLPBase(obs_shape[0], **(base_kwargs or {}))
+        # None: the critic reads the actor's rows (the reference's policy); an int: rows of that many words of its own
+        self.critic_obs_dim = None if critic_obs_dim is None else int(critic_obs_dim)
+        self.base = MLPBase(obs_shape[0], critic_inputs=self.critic_obs_dim, **(base_kwargs or {}))
         if base is not None:                       # --base-checkpoint (agents/ppo/train.py:44-45)
             self.base.load_state_dict(base)
         self.pi_dist = DiagGaussianHead(self.base.output_size, action_space.shape[0])
 
-    def act(self, inputs, deterministic=False):
-        value, feat = self.base(inputs)
+    def _critic_rows(self, critic_inputs):
+        """the rows the critic reads beside the actor's ``inputs``: None for a symmetric policy, which must not be given any"""
+        if (critic_inputs is None) != (self.critic_obs_dim is None):
+            raise ValueError("critic_inputs [.., %d] are required by a policy made with critic_obs_dim" % self.critic_obs_dim
+                             if critic_inputs is None else "critic_inputs given to a policy made without critic_obs_dim")
+        return critic_inputs
+
+    def act(self, inputs, deterministic=False, critic_inputs=None):
+        value, feat = self.base(inputs, self._critic_rows(critic_inputs))
         mean, logstd = self.pi_dist(feat)
         action = mean if deterministic else mean + torch.exp(logstd) * torch.randn_like(mean)
         return value, action, gaussian_log_prob(action, mean, logstd)
 
+    def act_actor(self, inputs, deterministic=False):
+        """the action alone, from the actor's rows alone (evaluation: an asymmetric policy needs no critic rows for it)"""
+        mean, logstd = self.pi_dist(self.base.features(inputs))
+        return mean if deterministic else mean + torch.exp(logstd) * torch.randn_like(mean)
+
     @torch.no_grad()
-    def act_into(self, inputs, value_out, action_out, logp_out, noise=None):
+    def act_into(self, inputs, value_out, action_out, logp_out, noise=None, critic_inputs=None):
         """`act` for rollout loops that own their buffers (ppo/storage.py): the same arithmetic written straight into
         value_out [N,1], action_out [N,A] and logp_out [N,1] -- about half the launches of act() + three copies, which is what
         a captured rollout step costs besides the env kernel.  `noise` (optional, [N,A]) replaces the standard-normal draw."""
         c, f = self.base.critic, self.base.features
         lin = lambda l, x, out=None: torch.addmm(l.bias, x, l.weight.t(), out=out)
-        lin(c[4], torch.tanh_(lin(c[2], torch.tanh_(lin(c[0], inputs)))), out=value_out)
+        cin = self._critic_rows(critic_inputs)
+        lin(c[4], torch.tanh_(lin(c[2], torch.tanh_(lin(c[0], inputs if cin is None else cin)))), out=value_out)
         mean = lin(self.pi_dist.mean, torch.tanh_(lin(f[2], torch.tanh_(lin(f[0], inputs)))))
         logstd = self.pi_dist.logstd
         if noise is None:
@@ -135,16 +155,18 @@ class Policy(nn.Module):
         z = (action_out - mean).mul_(torch.exp(-logstd))
         torch.sum(z.mul_(z).mul_(-0.5).sub_(logstd).sub_(_HALF_LOG_2PI), -1, keepdim=True, out=logp_out)
 
-    def heads(self, inputs):
+    def heads(self, inputs, critic_inputs=None):
         """(value, mean, logstd): what the fused loss kernel (ppo/fused.py) consumes."""
-        value, feat = self.base(inputs)
+        value, feat = self.base(inputs, self._critic_rows(critic_inputs))
         mean, logstd = self.pi_dist(feat)
         return value, mean, logstd
 
-    def get_value(self, inputs):
-        return self.base.critic(inputs)
+    def get_value(self, inputs, critic_inputs=None):
+        """the critic alone; an asymmetric policy reads ``critic_inputs`` and nothing of ``inputs`` (which may be None)"""
+        cin = self._critic_rows(critic_inputs)
+        return self.base.critic(inputs if cin is None else cin)
 
-    def evaluate_actions(self, inputs, action):
-        value, feat = self.base(inputs)
+    def evaluate_actions(self, inputs, action, critic_inputs=None):
+        value, feat = self.base(inputs, self._critic_rows(critic_inputs))
         mean, logstd = self.pi_dist(feat)
         return value, gaussian_log_prob(action, mean, logstd), gaussian_entropy_mean(mean, logstd)

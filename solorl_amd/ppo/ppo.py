@@ -31,8 +31,10 @@ class PPO:
         n_updates = 0
         clip = self.clip_param
         for _ in range(self.ppo_epoch):
-            for obs_b, act_b, vpred_b, ret_b, _mask_b, old_lp_b, adv_b in storage.batch_generator(adv, self.mini_batch_size):
-                values, logp, entropy = self.actor_critic.evaluate_actions(obs_b, act_b)
+            for batch in storage.batch_generator(adv, self.mini_batch_size):
+                obs_b, act_b, vpred_b, ret_b, _mask_b, old_lp_b, adv_b = batch[:7]
+                critic = {"critic_inputs": batch[7]} if len(batch) > 7 else {}       # (a storage with critic rows: an asymmetric policy)
+                values, logp, entropy = self.actor_critic.evaluate_actions(obs_b, act_b, **critic)
                 ratio = torch.exp(logp - old_lp_b)
                 action_loss = -torch.min(ratio * adv_b, torch.clamp(ratio, 1.0 - clip, 1.0 + clip) * adv_b).mean()
                 if self.use_clipped_value_loss:

@@ -1,6 +1,7 @@
 """On-device rollout storage -- surface of the reference's OPBuffer (agents/ppo/storage.py:5-71):
 tensors obs[T+1,N,O], rewards/value_preds/returns/action_log_probs[.,N,1], actions[T,N,A],
 masks[T+1,N,1]; append / reset / compute_returns (GAE and plain discounted) / batch_generator.
+With ``critic_obs_dim=OC`` also critic_obs[T+1,N,OC], the rows an asymmetric policy's critic reads (policy.py), carried like obs.
 
 Everything lives on the rollout device, so a 4096-env x 400-step buffer (~0.55 GB for Solo12
 pointGoal) never crosses PCIe; mini-batches are gathered with one index_select per tensor."""
@@ -8,9 +9,10 @@ import torch
 
 
 class RolloutStorage:
-    def __init__(self, num_steps, num_agents, obs_shape, action_dim, device):
+    def __init__(self, num_steps, num_agents, obs_shape, action_dim, device, critic_obs_dim=None):
         z = lambda *s: torch.zeros(*s, device=device)
         self.obs = z(num_steps + 1, num_agents, *obs_shape)
+        self.critic_obs = None if critic_obs_dim is None else z(num_steps + 1, num_agents, int(critic_obs_dim))
         self.rewards = z(num_steps, num_agents, 1)
         self.value_preds = z(num_steps + 1, num_agents, 1)
         self.returns = z(num_steps + 1, num_agents, 1)
@@ -22,9 +24,13 @@ class RolloutStorage:
         self.device = device
         self.step = 0
 
-    def append(self, obs, actions, action_log_probs, value_preds, rewards, masks):
+    def append(self, obs, actions, action_log_probs, value_preds, rewards, masks, critic_obs=None):
         t = self.step
+        if (critic_obs is None) != (self.critic_obs is None):
+            raise ValueError("critic_obs goes with a storage made with critic_obs_dim, and only with one")
         self.obs[t + 1].copy_(obs)
+        if critic_obs is not None:
+            self.critic_obs[t + 1].copy_(critic_obs)
         self.actions[t].copy_(actions)
         self.action_log_probs[t].copy_(action_log_probs)
         self.value_preds[t].copy_(value_preds)
@@ -34,6 +40,8 @@ class RolloutStorage:
 
     def reset(self):
         self.obs[0].copy_(self.obs[-1])
+        if self.critic_obs is not None:
+            self.critic_obs[0].copy_(self.critic_obs[-1])
         self.masks[0].copy_(self.masks[-1])
 
     @torch.no_grad()
@@ -69,7 +77,8 @@ class RolloutStorage:
                 self.returns[t] = torch.addcmul(self.rewards[t], gm[t], self.returns[t + 1])
 
     def batch_generator(self, advantages, mini_batch_size, generator=None):
-        """storage.py:57-71: random mini-batches without replacement, incomplete last batch dropped."""
+        """storage.py:57-71: random mini-batches without replacement, incomplete last batch dropped.  A storage with critic rows yields
+        them as an eighth element; one without yields the reference's seven."""
         n = self.num_samples
         perm = torch.randperm(n, device=self.device, generator=generator)
         flat = lambda x: x.reshape(n, *x.shape[2:])
@@ -77,7 +86,8 @@ class RolloutStorage:
         ret, msk, olp, adv = flat(self.returns[:-1]), flat(self.masks[:-1]), flat(self.action_log_probs), advantages.reshape(n, 1)
         for s in range(0, n - mini_batch_size + 1, mini_batch_size):
             idx = perm[s:s + mini_batch_size]
-            yield obs[idx], act[idx], val[idx], ret[idx], msk[idx], olp[idx], adv[idx]
+            batch = obs[idx], act[idx], val[idx], ret[idx], msk[idx], olp[idx], adv[idx]
+            yield batch if self.critic_obs is None else batch + (flat(self.critic_obs[:-1])[idx],)
 
 
 OPBuffer = RolloutStorage   # the reference's class name

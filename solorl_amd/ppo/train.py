@@ -35,6 +35,11 @@ Differences that come with the GPU engine (documented, not behavioural):
     ground -- by four launches behind every step launch of the eager and of the captured rollout alike
     (SoloVecEnv.set_reset_randomization), keyed by global env id, so ranks draw like one batch.  The policy cannot run inside the step
     kernel (it would act on the observation of the un-randomised reset): the rollout takes two launches per step;
+  * args.privileged_critic (train_ppo.py --privileged-critic [FILE.yaml]: True, or a dict of scales; no reference counterpart) gives the
+    value function rows of its own -- the observation before the sensor noise plus twenty words of the simulator's truth, written by
+    two launches behind every step launch of the eager and of the captured rollout alike (SoloVecEnv(critic_obs=)) -- while the actor
+    keeps the row a robot could measure: Policy(critic_obs_dim=), RolloutStorage(critic_obs_dim=).  No policy kernel is built at a
+    critic width, so the rollout's act and the mini-batch step take their PyTorch paths (inside the same HIP graphs);
   * multi-GPU: one process per GPU (`python -m torch.distributed.run --nproc-per-node W ...`), envs
     sharded by rank (global env id = rank*N + i), flat-bucket RCCL gradient all-reduce (ppo.py).
 """
@@ -81,11 +86,13 @@ def episode_stats(envs, device):
 def rollout(envs, actor_critic, storage, num_steps):
     """train.py:82-103: T steps of act -> env.step -> storage.append, entirely on the device (the episode statistics
     of train.py:90-100 are accumulated by the step kernel itself)."""
+    asym = storage.critic_obs is not None                 # an asymmetric policy: the critic reads the env's critic rows
     for step in range(num_steps):
         with torch.no_grad():
-            value, action, logp = actor_critic.act(storage.obs[step])
+            value, action, logp = actor_critic.act(storage.obs[step], **({"critic_inputs": storage.critic_obs[step]} if asym else {}))
         obs, reward, done, info = envs.step_inplace(action.contiguous())
-        storage.append(obs, action, logp, value, reward.unsqueeze(-1), (1.0 - done.float()).unsqueeze(-1))
+        storage.append(obs, action, logp, value, reward.unsqueeze(-1), (1.0 - done.float()).unsqueeze(-1),
+                       **({"critic_obs": envs.last_critic_obs} if asym else {}))
 
 
 def train(args, config, env_constructor=None, writer=None):
@@ -109,23 +116,29 @@ def train(args, config, env_constructor=None, writer=None):
                          reward_shaping=getattr(args, "reward_shaping", None), obs_noise=getattr(args, "obs_noise", None),
                          action_delay=getattr(args, "action_delay", None), motor_gain_range=getattr(args, "motor_gain_range", 0.0),
                          commands=getattr(args, "commands", None), termination=getattr(args, "termination", None),
-                         reset_randomization=getattr(args, "reset_randomization", None))
+                         reset_randomization=getattr(args, "reset_randomization", None),
+                         critic_obs=getattr(args, "privileged_critic", None) or None)
     shaping = getattr(args, "reward_shaping", None) is not None
     termination = getattr(args, "termination", None) is not None
     action_dim = envs.action_space.shape[0]
     base = torch.load(args.base_checkpoint) if getattr(args, "base_checkpoint", None) else None
-    actor_critic = Policy(envs.observation_space.shape, envs.action_space, base, {"hidden_size": args.hidden_size}).to(device)
+    critic_dim = getattr(envs, "critic_obs_dim", None)    # None: the critic reads the actor's rows
+    critic_of = (lambda t: {"critic_inputs": storage.critic_obs[t]}) if critic_dim is not None else (lambda t: {})
+    actor_critic = Policy(envs.observation_space.shape, envs.action_space, base, {"hidden_size": args.hidden_size},
+                          critic_obs_dim=critic_dim).to(device)
     D.broadcast_parameters(actor_critic)
     use_graphs = bool(args.cuda) and not getattr(args, "no_hip_graphs", False)
     agent = (GraphedPPO if use_graphs else PPO)(actor_critic, args.clip_param, args.ppo_epoch, args.mini_batch_size,
                                                  args.value_loss_coef, args.entropy_coef, lr=args.lr, l2_coef=args.l2_coef,
                                                  max_grad_norm=args.max_grad_norm)
-    storage = RolloutStorage(args.num_steps, N, envs.observation_space.shape, action_dim, device)
+    storage = RolloutStorage(args.num_steps, N, envs.observation_space.shape, action_dim, device, critic_obs_dim=critic_dim)
     storage.obs[0].copy_(envs.reset())
+    if critic_dim is not None:
+        storage.critic_obs[0].copy_(envs.last_critic_obs)
     torch.manual_seed(args.seed + 1000 * rank)        # but different action noise per rank
     if use_graphs:
         with torch.no_grad():
-            actor_critic.act(storage.obs[0]); actor_critic.get_value(storage.obs[0])    # library workspaces before capture
+            actor_critic.act(storage.obs[0], **critic_of(0)); actor_critic.get_value(storage.obs[0], **critic_of(0))    # library workspaces before capture
         torch.manual_seed(args.seed + 1000 * rank)
         graphed_rollout = GraphedRollout(envs, actor_critic, storage, args.num_steps)
     start = time.time()
@@ -139,7 +152,7 @@ def train(args, config, env_constructor=None, writer=None):
         else:
             rollout(envs, actor_critic, storage, args.num_steps)
         with torch.no_grad():
-            next_value = actor_critic.get_value(storage.obs[-1])
+            next_value = actor_critic.get_value(storage.obs[-1], **critic_of(-1))
         storage.compute_returns(next_value, args.use_gae, args.gamma, args.tau)
         value_loss, action_loss, entropy = agent.update(storage)
         storage.reset()

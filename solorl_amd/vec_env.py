@@ -31,6 +31,10 @@
   set_reset_randomization(**ranges), reset_randomization_count   (randomised initial states -- joint angles and velocities, base
       velocity, heading, roll and pitch drawn per env and episode on the device, the robot placed on the ground -- behind every reset:
       include/solorl.h solorl_randomize_reset / solorl_restart_history, reset_random.py)
+  SoloVecEnv(..., critic_obs=True | dict), critic_obs_dim, critic_observation_space, last_critic_obs   (privileged critic rows: the clean
+      observation row and twenty words of the simulator's truth -- contact forces, foot heights and speeds, the command, the episode's
+      progress, collisions, the drawn latency and gain error, the last kick -- written behind every step and reset for the value
+      function of an asymmetric actor-critic: include/solorl.h solorl_critic_obs, critic_obs.py)
 
 torch is plumbing only: it owns the device buffers and the stream; all arithmetic happens in
 ``libsolorl_hip.so`` on the caller's current HIP stream (no host synchronisation in step()).
@@ -66,6 +70,8 @@ _STAGES = (
      "act on the observation of an env that is about to be reset"),
     ("reset_randomization", lambda e: e._rr is not None, "with a reset randomization set", "its launches behind a reset",
      "set_reset_randomization(None)", "act on the observation of the un-randomised reset"),
+    ("critic_obs", lambda e: getattr(e, "_critic", None) is not None, "with critic_obs", "the critic rows' launches", None,
+     "compute the value from the actor's row"),
 )
 
 
@@ -138,7 +144,7 @@ class SoloVecEnv:
     or a ``SoloConfig``."""
 
     def __init__(self, config, num_envs, device=None, seed=1, env_id_offset=0, applied_torque=False, norm_obs=False, norm_ret=False,
-                 clipob=10.0, cliprew=10.0, gamma=0.99, epsilon=1e-8, commands=None, **overrides):
+                 clipob=10.0, cliprew=10.0, gamma=0.99, epsilon=1e-8, commands=None, critic_obs=None, **overrides):
         self.cfg = config.copy() if isinstance(config, SoloConfig) else config_from_dict(config, **overrides)
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
@@ -222,6 +228,23 @@ class SoloVecEnv:
         # nothing is allocated or launched unless a switch is on
         self._norm = VecNormalizer(N, self.obs_dim, device, norm_obs, norm_ret, clipob, cliprew, gamma, epsilon) if (norm_obs or norm_ret) else None
         self._norm_obs, self._norm_ret = bool(norm_obs), bool(norm_ret)
+        # privileged critic rows (``critic_obs``: True, or a dict of scale overrides, critic_obs.GROUPS): the engine's clean row plus
+        # twenty words.  The width is fixed here, as with commands -- a policy is built from critic_observation_space.  None or False:
+        # nothing is allocated or launched
+        self._critic = self._critic_states = self._critic_clean = self.last_critic_obs = None
+        self.critic_obs_dim = self.critic_observation_space = None
+        if critic_obs is not None and critic_obs is not False:
+            from .critic_obs import CRITIC_PRIV, make_params, scales_from_dict
+            if norm_obs:
+                raise _native.SoloRLError("critic_obs on an env with norm_obs: the critic rows would need running statistics of their own "
+                                          "(normalise the rows in the policy, or leave norm_obs off)")
+            self._critic = make_params(self.cfg, self.engine_obs_dim, **(scales_from_dict(critic_obs) if isinstance(critic_obs, dict) else {}))
+            self.critic_obs_dim = self.engine_obs_dim + CRITIC_PRIV
+            self.critic_observation_space = Box(-np.inf * np.ones(self.critic_obs_dim), np.inf * np.ones(self.critic_obs_dim))
+            self._critic_states = StateBatch(N, device)    # engine-owned: the state the new observation describes
+            # the engine's rows before the noise, while noise is set: the engine writes these and solorl_obs_noise the caller's, out of place
+            self._critic_clean = torch.zeros((N, self.engine_obs_dim), dtype=torch.float32, **kw)
+            self.last_critic_obs = torch.zeros((N, self.critic_obs_dim), dtype=torch.float32, **kw)
         self.training = True        # running_mean_std.py:94
         self.closed = False
 
@@ -390,7 +413,7 @@ class SoloVecEnv:
 
     def _shape(self, actions, rew, done, rows=None):
         """the shaped terms of a control step, behind its step launch: the state after the step (``rows``: the rows _terminate has
-        already read, taken before its reset), then one launch"""
+        already read, taken before its reset), then one launch -> the rows it read, or ``rows``"""
         if self._shape_params is not None:
             from .shaping import shape_reward
             if rows is None:
@@ -399,6 +422,7 @@ class SoloVecEnv:
                 rows.tau[:, :self.act_dim].copy_(self._tau)
             shape_reward(self.cfg, self._shape_params, rows, actions, done, self._shape_mem, rew,
                          terms_out=self.last_shaping_terms, ep_out=self._shape_ep, commands=self._cmd_mem)
+        return rows
 
     def shaping_stats(self, reset=True):
         """Means over the episodes finished since the last call of each term's weighted sum over the episode, ``sr/<name>``, and their
@@ -554,11 +578,11 @@ class SoloVecEnv:
         else:
             self._noise_count.zero_()
 
-    def _noise(self, o, mask=None):
-        """the sensor noise of the observation rows the engine has just written, in place"""
+    def _noise(self, o, mask=None, out=None):
+        """the sensor noise of the observation rows the engine has just written, in place (``out``: into these rows, ``o`` staying clean)"""
         if self._noise_scale is not None:
             from .channel import obs_noise
-            obs_noise(self._seed, self._id0, self._noise_scale, self._noise_count, o, mask=mask)
+            obs_noise(self._seed, self._id0, self._noise_scale, self._noise_count, o, out=None if out is o else out, mask=mask)
 
     def set_actuation(self, delay=None, gain_range=0.0):
         """Actuation latency and motor gain error between the caller's actions and the engine: every env applies the action it received
@@ -633,14 +657,34 @@ class SoloVecEnv:
         scale = torch.tensor(list(self._cmd.obs_scale), dtype=torch.float64, device=self.device)
         return (self._cmd_mem.cmd * scale).to(torch.float32)
 
+    # ---- privileged critic rows (include/solorl.h solorl_critic_obs; critic_obs.py)
+    def _clean_rows(self, e):
+        """the rows the engine writes for the caller's engine rows ``e``: ``e`` itself, or -- with critic rows and noise both set -- the
+        clean buffer, from which solorl_obs_noise writes ``e`` out of place"""
+        return self._critic_clean if self._critic is not None and self._noise_scale is not None else e
+
+    def _critic_rows(self, clean, out=None, rows=None):
+        """the critic rows of the observation just written, behind every other stage: the state that observation describes (``rows``:
+        rows already read in this step that are still current; else a get_states of its own), then one launch on the engine's clean
+        rows ``clean``, the command, actuator and kick rows the env holds now -> ``out`` (default: last_critic_obs)"""
+        if self._critic is None:
+            return None
+        from .critic_obs import critic_obs
+        if rows is None:
+            rows = self.get_states(out=self._critic_states)
+        return critic_obs(self.cfg, self._critic, rows, clean, out=self.last_critic_obs if out is None else out, commands=self._cmd_mem,
+                          actuators=self._act_mem, kick=self.last_kick)
+
     def reset(self):
+        c = self._clean_rows(self._obs_engine)
         with torch.cuda.device(self.device):
-            _native.check(self.L.solorl_reset(self._h, C.c_void_p(self._obs_engine.data_ptr()), self._stream()))
+            _native.check(self.L.solorl_reset(self._h, C.c_void_p(c.data_ptr()), self._stream()))
         if self._act is not None:                       # every env starts an episode
             self._act_restart.fill_(1)
-        self._randomize(self._obs_engine, self._rr_all)
-        self._noise(self._obs_engine)
+        self._randomize(c, self._rr_all)
+        self._noise(c, out=self._obs_engine)
         self._commands(self._obs, self._cmd_all)        # every env draws a command
+        self._critic_rows(c)
         if self._shape_mem is not None:                 # every env starts an episode
             self._shape_mem.data.zero_()
         if self.last_termination is not None:
@@ -666,17 +710,21 @@ class SoloVecEnv:
         self._kick()
         return applied
 
-    def _after_step(self, e, o, r, d, actions, tail=False):
+    def _after_step(self, e, o, r, d, actions, tail=False, clean=None, critic_out=None):
         """behind a step launch that wrote the engine's observation rows ``e``, rewards ``r`` and done flags ``d``: every stage that is
         set, in the one order there is; ``o``: the caller's observation rows (``e`` without commands).  ``tail``: the subset of
-        step_act_inplace -- restarts, shaped terms, return normalisation -- whose policy has already read ``o``"""
-        rows = None if tail else self._terminate(e, r, d)
+        step_act_inplace -- restarts, shaped terms, return normalisation -- whose policy has already read ``o``.  ``clean``: the rows
+        the launch wrote instead of ``e`` (_clean_rows: the noise then writes ``e`` from them); ``critic_out``: where the critic rows go"""
+        c = e if clean is None else clean
+        rows = None if tail else self._terminate(c, r, d)
         self._restarts(d)
-        self._shape(actions, r, d, rows)                # (with commands: against the command the policy acted on, before it is redrawn)
+        rows = self._shape(actions, r, d, rows)         # (with commands: against the command the policy acted on, before it is redrawn)
         if not tail:
-            self._randomize(e, d)
-            self._noise(e)
+            self._randomize(c, d)
+            self._noise(c, out=e)
             self._commands(o, d)
+            # (rows read behind the step are the state the observation describes unless a termination or a randomised start has reset envs since)
+            self._critic_rows(c, critic_out, rows if self._term is None and self._rr is None else None)
         if self._norm is not None:
             self._normalize(o, r, d, 1, obs=not tail)
 
@@ -696,21 +744,28 @@ class SoloVecEnv:
         return (o, r, d, self._raw("obs_out", o, lead + (self.nenvs, self.obs_dim)), self._per_env("rew_out", r, lead),
                 self._raw("done_out", d, lead + (self.nenvs,), dtype=torch.uint8))
 
-    def step_inplace(self, actions, obs_out=None, rew_out=None, done_out=None):
+    def step_inplace(self, actions, obs_out=None, rew_out=None, done_out=None, critic_obs_out=None):
         """Zero-copy variant for rollout loops: returns views of the engine-owned output buffers (overwritten by the next
         step) -- or writes observations [N, O] / rewards [N] or [N, 1] / done flags (uint8 [N]) straight into caller-owned tensors
         such as rollout-storage rows (the C ABI takes the caller's pointers anyway).  Host-side checks only, capturable in a HIP graph.
-        With velocity commands O is the wide width: the engine writes its own narrow buffer and solorl_commands the caller's rows."""
+        With velocity commands O is the wide width: the engine writes its own narrow buffer and solorl_commands the caller's rows.
+        ``critic_obs_out`` (an env made with critic_obs): where the critic rows [N, critic_obs_dim] go instead of last_critic_obs."""
         a = self._raw("actions", actions, (self.nenvs, self.act_dim))
         o, r, d, po, pr, pd = self._outputs((), (self._obs, self._rew, self._done), obs_out, rew_out, done_out)
+        if critic_obs_out is not None:
+            if self._critic is None:
+                raise _native.SoloRLError("critic_obs_out on an env made without critic_obs (the width is fixed at construction: "
+                                          "SoloVecEnv(..., critic_obs=True))")
+            self._raw("critic_obs_out", critic_obs_out, (self.nenvs, self.critic_obs_dim))
         e = o if self._cmd is None else self._obs_engine
+        c = self._clean_rows(e)
         self._steps_issued += 1
         applied = self._before_step(actions)
         if applied is not actions:
             a = C.c_void_p(applied.data_ptr())
         with torch.cuda.device(self.device):
-            _native.check(self.L.solorl_step(self._h, a, C.c_void_p(e.data_ptr()), pr, pd, C.byref(self._info_c), self._stream()))
-        self._after_step(e, o, r, d, actions)
+            _native.check(self.L.solorl_step(self._h, a, C.c_void_p(c.data_ptr()), pr, pd, C.byref(self._info_c), self._stream()))
+        self._after_step(e, o, r, d, actions, clean=c, critic_out=critic_obs_out)
         return o, r, d, self._info
 
     def step_act_supported(self, params):
@@ -962,8 +1017,12 @@ class SoloVecEnv:
             self._act_restart.bitwise_or_(m.ne(0).to(torch.uint8))
         if self._cmd is not None:                       # every row with the command it holds; the selected ones are rewritten below
             self._obs.copy_(torch.cat([self._obs_engine, self._command_words()], dim=1))
+        c = self._clean_rows(self._obs_engine)
+        if c is not self._obs_engine:                   # every row before the noise, for the critic rows
+            c.copy_(self._obs_engine)
         self._noise(self._obs_engine, m)                # the rows the engine has just written: the selected ones
         self._commands(self._obs, m, mask=m)            # the selected envs draw a command; no other row is touched
+        self._critic_rows(c)                            # every row: the unselected ones describe their current state too
         if self._shape_mem is not None:                 # the selected envs start an episode (its sums so far are dropped, not counted)
             self._shape_mem.data.masked_fill_(m.bool().unsqueeze(-1), 0.0)
         if self._norm is not None:
@@ -1008,7 +1067,8 @@ for _guard in sorted({g for g, _, _, between, _, _ in _STAGES if between is not 
 def make_vec_envs(config, num_envs, env_constructor=None, gamma=0.99, device=None, training=True, seed=1,
                   env_id_offset=0, norm_obs=False, norm_ret=False, clipob=10., cliprew=10., epsilon=1e-8,
                   push_interval=None, push_max_vel=0.0, push_max_yaw_rate=0.0, reward_shaping=None,
-                  obs_noise=None, action_delay=None, motor_gain_range=0.0, commands=None, termination=None, reset_randomization=None):
+                  obs_noise=None, action_delay=None, motor_gain_range=0.0, commands=None, termination=None, reset_randomization=None,
+                  critic_obs=None):
     """Signature of agents/ppo/envs.py:14.  ``env_constructor`` (the per-process gym env class of the
     reference) is accepted for call-site compatibility and ignored.  ``norm_obs`` / ``norm_ret`` are VecNormalize's ``ob`` /
     ``ret`` (agents/running_mean_std.py:79; the reference's launcher passes False, False, and so do the defaults here) with its
@@ -1032,9 +1092,11 @@ def make_vec_envs(config, num_envs, env_constructor=None, gamma=0.99, device=Non
     launched): early termination rules behind every step (SoloVecEnv.set_termination).
     ``reset_randomization`` (a dict with ``joint_pos``, ``joint_vel``, ``lin_vel``, ``ang_vel``, ``yaw``, ``roll``, ``pitch``, ``clearance``,
     ``place_on_ground``, as configs/reset_walk12.yaml holds it; None = the engine's own snapshots, and nothing is allocated or launched):
-    randomised initial states behind every reset (SoloVecEnv.set_reset_randomization)."""
+    randomised initial states behind every reset (SoloVecEnv.set_reset_randomization).
+    ``critic_obs`` (True, or a dict of scale overrides per group of privileged words as configs/critic_walk12.yaml holds it; None = no
+    critic rows, and nothing is allocated or launched): privileged critic rows behind every step and reset (SoloVecEnv.last_critic_obs)."""
     envs = SoloVecEnv(config, num_envs, device=device, seed=seed, env_id_offset=env_id_offset, norm_obs=norm_obs, norm_ret=norm_ret,
-                      clipob=clipob, cliprew=cliprew, gamma=gamma, epsilon=epsilon, commands=commands)
+                      clipob=clipob, cliprew=cliprew, gamma=gamma, epsilon=epsilon, commands=commands, critic_obs=critic_obs)
     if push_interval is not None:
         envs.set_perturbation(push_interval, (push_max_vel, push_max_vel, 0.0), (0.0, 0.0, push_max_yaw_rate))
     if reward_shaping is not None:

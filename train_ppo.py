@@ -112,6 +112,12 @@ def load_reset_randomization(path, config):
                        _checked(lambda d: make_reset_randomization(config_from_dict(config), 0, 0, **ranges_from_dict(d))))
 
 
+def load_privileged_critic(path, config):
+    from solorl_amd.config import config_from_dict
+    from solorl_amd.critic_obs import make_params, scales_from_dict
+    return load_option("--privileged-critic", path, _checked(lambda d: make_params(config_from_dict(config), 1, **scales_from_dict(d))))
+
+
 def get_ppo_args(argv=None):
     p = argparse.ArgumentParser("PPO args")
     p.add_argument("--num-agents", type=int, default=32)          # envs PER GPU
@@ -154,6 +160,11 @@ def get_ppo_args(argv=None):
                    help="add shaped reward terms to every step's reward: `weights:` (term name -> weight) and the terms' parameters, "
                         "e.g. configs/shaping_walk12.yaml (default: the reference's reward alone)")
     add_channel_flags(p)
+    p.add_argument("--privileged-critic", type=str, nargs="?", const=True, default=None, metavar="FILE.yaml",
+                   help="asymmetric actor-critic: the value function reads rows of its own -- the observation before --obs-noise plus twenty "
+                        "words of the simulator's truth (contact forces, foot heights and speeds, the command, the episode's progress, "
+                        "collisions, the drawn latency and gain error, the last kick); FILE.yaml holds scales per group of words, e.g. "
+                        "configs/critic_walk12.yaml (without a file: the defaults; default: the critic reads the actor's rows)")
     p.add_argument("--num-steps", type=int, default=None, help="rollout length (default: episode_length, train_ppo.py:62-63)")
     return p.parse_args(argv)
 
@@ -182,6 +193,11 @@ def main(argv=None):
         args.termination = load_termination(args.termination, config)
     if args.reset_randomization is not None:
         args.reset_randomization = load_reset_randomization(args.reset_randomization, config)
+    if args.privileged_critic is not None:
+        if args.normalize_obs:
+            raise SystemExit("--privileged-critic with --normalize-obs: the critic rows would need running statistics of their own")
+        if args.privileged_critic is not True:
+            args.privileged_critic = load_privileged_critic(args.privileged_critic, config)
     writer = None
     rank = int(os.environ.get("RANK", "0"))
     if args.logdir is not None:      # run directory named as training/train_ppo.py:64-72
