@@ -10,6 +10,13 @@
 //                                back-propagated pre-activation gradients of every layer, written [unit][row]
 //   ppo_grad_stage2_mfma_kernel  the weight gradients G X^T of the six layers over row chunks
 //   ppo_grad_stage3_kernel       their fixed-order sum into the parameters' gradients, log-std gradient, loss bookkeeping
+//   ppo_clip_adam_kernel         the gradient-norm clip and the Adam update of all 13 parameter tensors
+//
+// The kernels whose code depends on the policy's shape (act, stage 1, clip-Adam) are ONE family on <O, OC, A>: the actor's input
+// width, the critic's, the action width (SOLO_DIMS_LIST).  The critic reads rows of its own, [n][OC], and in stage 1 gathers them
+// into an xt0 of its own.  The symmetric policy (solorl_policy_params.critic_obs_dim = 0) is the instance OC = O, launched with the
+// actor's rows and the shared xt0 in the critic's places; a critic width of its own (the asymmetric actor-critic) goes through the
+// _critic entry points, which take the two extra arrays.  Stage 2 / 3 and the host code take OC at run time in the same way.
 //
 // The three product kernels run on the matrix cores (exact-f32 MFMA), see "MFMA formulation" below.  Two VALU formulations
 // (lane = row; weights through scalar loads, then through LDS broadcast reads) were built and measured first:
@@ -17,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdio>
 #include <mutex>
 #include <type_traits>
 #include <utility>
@@ -364,29 +372,21 @@ __device__ __forceinline__ void act_net_mfma(NET_ARGS, const float* __restrict__
   }
 }
 
-template <int O, int A>
-__global__ void __launch_bounds__(64)
-policy_act_mfma_kernel(CRITIC_ARGS, ACTOR_ARGS, const float* __restrict__ obs, const float* __restrict__ noise, int n, float* value_out,
-                       float* action_out, float* logp_out) {
-  if (blockIdx.y == 0) act_net_mfma<O, A, false>(cw0, cb0, cw1, cb1, cwh, cbh, nullptr, obs, noise, n, value_out, action_out, logp_out);
-  else act_net_mfma<O, A, true>(aw0, ab0, aw1, ab1, awh, abh, logstd, obs, noise, n, value_out, action_out, logp_out);
-}
-
-// The asymmetric actor-critic (solorl_policy_params.critic_obs_dim = OC != 0): the critic's workgroups run the same net at its own
-// width on rows of their own.  NetRegs<96, 1> holds 96 + 64 + 32 weight registers (the symmetric 84-wide net: 84 + 64 + 32).
+// The critic's workgroups run the net at the critic's width OC on the critic's rows cobs (the symmetric policy: OC = O, cobs = obs).
+// NetRegs<96, 1>, the widest built, holds 96 + 64 + 32 weight registers.
 template <int O, int OC, int A>
 __global__ void __launch_bounds__(64)
-policy_act_critic_mfma_kernel(CRITIC_ARGS, ACTOR_ARGS, const float* __restrict__ obs, const float* __restrict__ cobs, const float* __restrict__ noise, int n,
-                              float* value_out, float* action_out, float* logp_out) {
+policy_act_mfma_kernel(CRITIC_ARGS, ACTOR_ARGS, const float* __restrict__ obs, const float* __restrict__ cobs, const float* __restrict__ noise, int n,
+                       float* value_out, float* action_out, float* logp_out) {
   if (blockIdx.y == 0) act_net_mfma<OC, A, false>(cw0, cb0, cw1, cb1, cwh, cbh, nullptr, cobs, noise, n, value_out, action_out, logp_out);
   else act_net_mfma<O, A, true>(aw0, ab0, aw1, ab1, awh, abh, logstd, obs, noise, n, value_out, action_out, logp_out);
 }
 
 // ---------------------------------------------------------------- stage 1 on MFMA: grid (ceil(m / 128), 2), workgroups of four wavefronts,
 // one net per workgroup with its operand image in LDS (NetLds), one 32-row tile per wavefront (= one row of partials per 32 samples)
-// WX: this net writes its gathered input rows to xt0 (symmetric: the critic writes the shared ones; asymmetric: each net its own);
-// rows: the [n][O] rollout rows this net reads (symmetric: B.obs)
-template <int O, int A, bool ACTOR, bool WX = !ACTOR>
+// WX: this net writes its gathered input rows to xt0 (the critic always; the actor where its rows are not the critic's: OC != O);
+// rows: the [n][O] rollout rows this net reads
+template <int O, int A, bool ACTOR, bool WX>
 __device__ __forceinline__ void grad_net_mfma(NET_ARGS, const float* __restrict__ logstd, const float* __restrict__ rows, const solorl_ppo_batch& B, float* xt0, float* xt1,
                                               float* xt2, float* g1, float* g2, float* gh, float* partials, float4* image) {
   constexpr int NOUT = ACTOR ? A : 1;
@@ -557,22 +557,15 @@ __device__ __forceinline__ void grad_net_mfma(NET_ARGS, const float* __restrict_
   }
 }
 
-template <int O, int A> constexpr int stage1_lds_bytes() { return NetLds<O, A>::BYTES > NetLds<O, 1>::BYTES ? NetLds<O, A>::BYTES : NetLds<O, 1>::BYTES; }
-template <int O, int A>
-__global__ void __launch_bounds__(256, 2)
-ppo_grad_stage1_mfma_kernel(CRITIC_ARGS, ACTOR_ARGS, const solorl_ppo_batch B, const solorl_ppo_stage1 W) {
-  extern __shared__ float4 stage1_image[];         // stage1_lds_bytes<O, A>() of dynamic LDS: 64-68 KB, two workgroups per CU
-  if (blockIdx.y == 0) grad_net_mfma<O, A, false>(cw0, cb0, cw1, cb1, cwh, cbh, nullptr, B.obs, B, W.xt0, W.c_xt1, W.c_xt2, W.c_g1, W.c_g2, W.c_gh, W.partials, stage1_image);
-  else grad_net_mfma<O, A, true>(aw0, ab0, aw1, ab1, awh, abh, logstd, B.obs, B, W.xt0, W.a_xt1, W.a_xt2, W.a_g1, W.a_g2, W.a_gh, W.partials, stage1_image);
-}
-// asymmetric: the critic half at OC on the critic rows writes the critic xt0, the actor half writes the actor's xt0 (W.xt0)
-template <int O, int OC, int A> constexpr int stage1_critic_lds_bytes() { return NetLds<O, A>::BYTES > NetLds<OC, 1>::BYTES ? NetLds<O, A>::BYTES : NetLds<OC, 1>::BYTES; }
+// The critic half at OC gathers the critic's rows cobs into the critic's xt0 (cxt0).  The symmetric policy is launched with cobs = B.obs
+// and cxt0 = W.xt0: the critic half writes the one xt0 both first layers' gradients read, and the actor half leaves it alone.
+template <int O, int OC, int A> constexpr int stage1_lds_bytes() { return NetLds<O, A>::BYTES > NetLds<OC, 1>::BYTES ? NetLds<O, A>::BYTES : NetLds<OC, 1>::BYTES; }
 template <int O, int OC, int A>
 __global__ void __launch_bounds__(256, 2)
-ppo_grad_stage1_critic_mfma_kernel(CRITIC_ARGS, ACTOR_ARGS, const solorl_ppo_batch B, const solorl_ppo_stage1 W, const float* __restrict__ cobs, float* cxt0) {
-  extern __shared__ float4 stage1_image[];         // stage1_critic_lds_bytes<O, OC, A>(): at most 66 KB (OC = 96), two workgroups per CU
+ppo_grad_stage1_mfma_kernel(CRITIC_ARGS, ACTOR_ARGS, const solorl_ppo_batch B, const solorl_ppo_stage1 W, const float* __restrict__ cobs, float* cxt0) {
+  extern __shared__ float4 stage1_image[];         // stage1_lds_bytes<O, OC, A>() of dynamic LDS: 50-66 KB, two workgroups per CU
   if (blockIdx.y == 0) grad_net_mfma<OC, A, false, true>(cw0, cb0, cw1, cb1, cwh, cbh, nullptr, cobs, B, cxt0, W.c_xt1, W.c_xt2, W.c_g1, W.c_g2, W.c_gh, W.partials, stage1_image);
-  else grad_net_mfma<O, A, true, true>(aw0, ab0, aw1, ab1, awh, abh, logstd, B.obs, B, W.xt0, W.a_xt1, W.a_xt2, W.a_g1, W.a_g2, W.a_gh, W.partials, stage1_image);
+  else grad_net_mfma<O, A, true, OC != O>(aw0, ab0, aw1, ab1, awh, abh, logstd, B.obs, B, W.xt0, W.a_xt1, W.a_xt2, W.a_g1, W.a_g2, W.a_gh, W.partials, stage1_image);
 }
 
 // ---------------------------------------------------------------- stage 2 on MFMA: d W = G . X^T with the ROW index as K
@@ -736,7 +729,7 @@ struct AdamArgs { AdamSeg seg[13]; int total; float* m; float* v; float* step; c
 // fell back to waited for one L2 round trip per tensor and pass: 22 us).  A thread owns element tid + 1024 j of tensor s for every
 // (s, j) -- 27-29 slots: every gradient is loaded ONCE, all loads of a phase are in flight together, the gradients stay in
 // registers between the norm and the update.
-template <int O, int A, int OC = O> struct AdamDims {
+template <int O, int OC, int A> struct AdamDims {
   static constexpr int n(int s) { constexpr int N[13] = {H * OC, H, H * H, H, H, 1, H * O, H, H * H, H, A * H, A, A}; return N[s]; }
   static constexpr int cnt(int s) { return (n(s) + 1023) / 1024; }
   static constexpr int base(int s) { int b = 0; for (int i = 0; i < s; ++i) b += cnt(i); return b; }
@@ -822,55 +815,43 @@ template <typename D> __device__ __forceinline__ void clip_adam_body(const AdamA
   // (every thread read *K.step before the first barrier)
   if (tid == 0) { *K.step = step; if (K.offset) *K.offset += K.inc; }
 }
-template <int O, int A>
-__global__ void __launch_bounds__(1024) ppo_clip_adam_kernel(const AdamArgs K) { clip_adam_body<AdamDims<O, A>>(K); }
 template <int O, int OC, int A>
-__global__ void __launch_bounds__(1024) ppo_clip_adam_critic_kernel(const AdamArgs K) { clip_adam_body<AdamDims<O, A, OC>>(K); }
+__global__ void __launch_bounds__(1024) ppo_clip_adam_kernel(const AdamArgs K) { clip_adam_body<AdamDims<O, OC, A>>(K); }
 
-// observation widths of zero or one history level (14 + 2 n (+ 4 pointGoal), x 1 or x 2), action widths n = 8 / 12; and the
-// zero-history widths with the three velocity-command words of solorl_commands behind them (odd: every access goes word by word)
-#define SOLO_DIMS_LIST(X) X(76, 12) X(84, 12) X(38, 12) X(42, 12) X(60, 8) X(68, 8) X(30, 8) X(34, 8) X(41, 12) X(45, 12) X(33, 8) X(37, 8)
-bool dims_supported(int O, int A) {
-#define SOLO_DIMS(O_, A_) if (O == O_ && A == A_) return true;
+// (actor width, critic width, action width).  Symmetric, OC = O: the observation widths of zero or one history level (14 + 2 n
+// (+ 4 pointGoal), x 1 or x 2) at action widths n = 8 / 12, and the zero-history widths with the three velocity-command words of
+// solorl_commands behind them (odd: every access goes word by word).  With a critic width of its own: walk and stand at zero and one
+// history level and the commanded zero-history widths; the critic's rows are the engine's observation + SOLORL_CRITIC_PRIV words.
+#define SOLO_DIMS_LIST(X) X(76, 76, 12) X(84, 84, 12) X(38, 38, 12) X(42, 42, 12) X(60, 60, 8) X(68, 68, 8) X(30, 30, 8) X(34, 34, 8) \
+                          X(41, 41, 12) X(45, 45, 12) X(33, 33, 8) X(37, 37, 8) \
+                          X(38, 58, 12) X(41, 58, 12) X(76, 96, 12) X(30, 50, 8) X(33, 50, 8) X(60, 80, 8)
+#define SOLO_DIMS_TEXT "obs x act = 38, 42, 76 or 84 x 12; 30, 34, 60 or 68 x 8 (zero or one history level), 41 or 45 x 12; 33 or 37 x 8 (zero history " \
+                       "levels with velocity commands); with a critic width, (obs, critic, act) = (38, 58, 12), (41, 58, 12), (76, 96, 12), (30, 50, 8), " \
+                       "(33, 50, 8), (60, 80, 8)"
+bool dims_supported(int O, int OC, int A) {
+#define SOLO_DIMS(O_, C_, A_) if (O == O_ && OC == C_ && A == A_) return true;
   SOLO_DIMS_LIST(SOLO_DIMS)
 #undef SOLO_DIMS
   return false;
 }
-int fail_dims() {
-  return solorl_fail_(SOLORL_ERR_INVALID, "policy kernels are built for the observation / action sizes of zero or one history level "
-                                          "(38, 42, 76 or 84 x 12; 30, 34, 60 or 68 x 8) and for zero history levels with velocity commands "
-                                          "(41 or 45 x 12; 33 or 37 x 8); use the PyTorch path for other shapes");
-}
-// (actor width, critic width, action width) of the asymmetric policy: walk and stand at zero and one history level, and the commanded
-// zero-history widths; the critic's rows are the engine's observation + SOLORL_CRITIC_PRIV words
-#define SOLO_DIMS3_LIST(X) X(38, 58, 12) X(41, 58, 12) X(76, 96, 12) X(30, 50, 8) X(33, 50, 8) X(60, 80, 8)
-bool dims3_supported(int O, int OC, int A) {
-#define SOLO_DIMS3(O_, C_, A_) if (O == O_ && OC == C_ && A == A_) return true;
-  SOLO_DIMS3_LIST(SOLO_DIMS3)
-#undef SOLO_DIMS3
-  return false;
-}
-int fail_dims3() {
-  return solorl_fail_(SOLORL_ERR_INVALID, "policy kernels with a critic width are built for (obs, critic, act) = (38, 58, 12), (41, 58, 12), (76, 96, 12), "
-                                          "(30, 50, 8), (33, 50, 8), (60, 80, 8); the symmetric ones for 38, 42, 76 or 84 x 12; 30, 34, 60 or 68 x 8; "
-                                          "use the PyTorch path for other shapes");
-}
+int fail_dims() { return solorl_fail_(SOLORL_ERR_INVALID, "policy kernels are built for " SOLO_DIMS_TEXT "; use the PyTorch path for other shapes"); }
 int fail_critic_width() {
-  return solorl_fail_(SOLORL_ERR_INVALID, "this entry point takes the symmetric policy (38, 42, 76 or 84 x 12; 30, 34, 60 or 68 x 8 ...): critic_obs_dim must be 0 "
-                                          "-- a policy with a critic width goes through solorl_policy_act_critic / solorl_ppo_grad_stage1_critic / "
-                                          "solorl_ppo_grad_stage2_critic");
+  return solorl_fail_(SOLORL_ERR_INVALID, "this entry point takes the symmetric policy: critic_obs_dim must be 0 -- a policy with a critic width goes through "
+                                          "solorl_policy_act_critic / solorl_ppo_grad_stage1_critic / solorl_ppo_grad_stage2_critic (built: " SOLO_DIMS_TEXT ")");
 }
-template <typename F> int dispatch_dims3(int O, int OC, int A, F&& f) {
-#define SOLO_DIMS3(O_, C_, A_) if (O == O_ && OC == C_ && A == A_) return f(std::integral_constant<int, O_>(), std::integral_constant<int, C_>(), std::integral_constant<int, A_>());
-  SOLO_DIMS3_LIST(SOLO_DIMS3)
-#undef SOLO_DIMS3
-  return fail_dims3();
-}
-template <typename F> int dispatch_dims(int O, int A, F&& f) {
-#define SOLO_DIMS(O_, A_) if (O == O_ && A == A_) return f(std::integral_constant<int, O_>(), std::integral_constant<int, A_>());
+template <typename F> int dispatch_dims(int O, int OC, int A, F&& f) {
+#define SOLO_DIMS(O_, C_, A_) if (O == O_ && OC == C_ && A == A_) return f(std::integral_constant<int, O_>(), std::integral_constant<int, C_>(), std::integral_constant<int, A_>());
   SOLO_DIMS_LIST(SOLO_DIMS)
 #undef SOLO_DIMS
   return fail_dims();
+}
+// the width of the critic's first layer: critic_obs_dim = 0 says "the actor's"
+inline int critic_width(const solorl_policy_params* p) { return p->critic_obs_dim != 0 ? p->critic_obs_dim : p->obs_dim; }
+// "<entry point>: <what>", as rows_check_args (row_batch.hpp) reports
+int fail_in(const char* fn, int code, const char* what) {
+  char msg[192];
+  std::snprintf(msg, sizeof(msg), "%s: %s", fn, what);
+  return solorl_fail_(code, msg);
 }
 
 // every policy entry point: the parameters, the shape (stage 2's kernel is not reached through dispatch_dims and computes only the tile
@@ -884,13 +865,12 @@ int check_policy(const solorl_policy_params* p, int device_id, int critic = 0) {
   for (const void* q : ptrs) if (!q) return solorl_fail_(SOLORL_ERR_INVALID, "null policy parameter pointer");
   // the kernels read weight rows as float4 (16 consecutive bytes per lane): every parameter tensor must start on a 16-byte
   // boundary (torch allocations do; an offset view passed by another C-ABI caller would fault on the GPU instead)
-  const int cw = p->critic_obs_dim != 0 ? p->critic_obs_dim : p->obs_dim;       // the width of the critic's first layer
-  const void* vec[] = {p->critic_w1, p->actor_w1, p->critic_w2, p->mean_w, cw % 4 == 0 ? p->critic_w0 : nullptr, p->obs_dim % 4 == 0 ? p->actor_w0 : nullptr};
+  const void* vec[] = {p->critic_w1, p->actor_w1, p->critic_w2, p->mean_w, critic_width(p) % 4 == 0 ? p->critic_w0 : nullptr, p->obs_dim % 4 == 0 ? p->actor_w0 : nullptr};
   for (const void* q : vec) if (reinterpret_cast<uintptr_t>(q) & 15u) return solorl_fail_(SOLORL_ERR_INVALID, "policy weight matrices must be 16-byte aligned (rows are read as float4)");
   if (p->critic_obs_dim != 0 && critic == 0) return fail_critic_width();
-  if (p->critic_obs_dim == 0 && critic == 1) return fail_dims3();
-  if (p->critic_obs_dim != 0 ? !dims3_supported(p->obs_dim, p->critic_obs_dim, p->act_dim) : !dims_supported(p->obs_dim, p->act_dim))
-    return p->critic_obs_dim != 0 ? fail_dims3() : fail_dims();
+  if (p->critic_obs_dim == 0 && critic == 1) return fail_dims();
+  // (the actor's width is written critic_obs_dim = 0, never as a critic width of its own: those instances leave the actor's xt0 unwritten)
+  if (p->critic_obs_dim == p->obs_dim || !dims_supported(p->obs_dim, critic_width(p), p->act_dim)) return fail_dims();
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return solorl_fail_(SOLORL_ERR_NODEVICE, "no HIP device available (no CPU fallback)");
   if (device_id < 0 || device_id >= ndev) return solorl_fail_(SOLORL_ERR_NODEVICE, "device_id out of range");
@@ -899,35 +879,22 @@ int check_policy(const solorl_policy_params* p, int device_id, int critic = 0) {
 }
 
 // Stage 1 takes more than the 64 KB of dynamic LDS a kernel gets by default: the limit is raised once per (instantiation, device)
-template <int O, int A> int stage1_raise_lds_limit(int device_id) {
+template <int O, int OC, int A> int stage1_raise_lds_limit(int device_id) {
   static std::mutex mu;
   static bool raised[64] = {};
   if (device_id < 0 || device_id >= 64) return solorl_fail_(SOLORL_ERR_NODEVICE, "ppo_grad_stage1_mfma_kernel: device_id beyond the 64 the library tracks");
   std::lock_guard<std::mutex> lock(mu);
   if (raised[device_id]) return 0;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_grad_stage1_mfma_kernel<O, A>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          stage1_lds_bytes<O, A>()) != hipSuccess)
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_grad_stage1_mfma_kernel<O, OC, A>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          stage1_lds_bytes<O, OC, A>()) != hipSuccess)
     return solorl_fail_(SOLORL_ERR_HIP, "ppo_grad_stage1_mfma_kernel: cannot raise the dynamic LDS limit");
   raised[device_id] = true;
   return 0;
 }
 
-template <int O, int OC, int A> int stage1_critic_raise_lds_limit(int device_id) {
-  static std::mutex mu;
-  static bool raised[64] = {};
-  if (device_id < 0 || device_id >= 64) return solorl_fail_(SOLORL_ERR_NODEVICE, "ppo_grad_stage1_critic_mfma_kernel: device_id beyond the 64 the library tracks");
-  std::lock_guard<std::mutex> lock(mu);
-  if (raised[device_id]) return 0;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_grad_stage1_critic_mfma_kernel<O, OC, A>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          stage1_critic_lds_bytes<O, OC, A>()) != hipSuccess)
-    return solorl_fail_(SOLORL_ERR_HIP, "ppo_grad_stage1_critic_mfma_kernel: cannot raise the dynamic LDS limit");
-  raised[device_id] = true;
-  return 0;
-}
-
-// stage 2 and 3 of both forms: xt0c = the critic's gathered rows (the shared xt0 for the symmetric policy), OC its width
-int grad_stage2_launch(const solorl_policy_params* p, const solorl_ppo_stage1* work, const float* xt0c, int OC, int m, const solorl_ppo_grads* out, void* stream) {
-  const int O = p->obs_dim, A = p->act_dim;
+// stage 2 and 3 of both forms: xt0c = the critic's gathered rows (the shared xt0 for the symmetric policy)
+int grad_stage2_launch(const solorl_policy_params* p, const solorl_ppo_stage1* work, const float* xt0c, int m, const solorl_ppo_grads* out, void* stream) {
+  const int O = p->obs_dim, OC = critic_width(p), A = p->act_dim;
   Stage3Args T;
   Stage2Args& S = T.S;
   const LayerDesc L[6] = {
@@ -956,6 +923,51 @@ int grad_stage2_check(const solorl_ppo_stage1* work, int m, const solorl_ppo_gra
   return 0;
 }
 
+// a row array of width w is read as float4 where w is a multiple of 4
+bool rows_misaligned(const void* rows, int w) { return w % 4 == 0 && (reinterpret_cast<uintptr_t>(rows) & 15u); }
+
+// act of both forms, behind check_policy: cobs = the critic's rows [n][critic_width(p)] (obs for the symmetric policy)
+int policy_act_launch(const char* fn, const solorl_policy_params* p, const float* obs, const float* cobs, const float* noise, int n, float* value_out,
+                      float* action_out, float* logp_out, void* stream) {
+  if (!obs || !cobs || !value_out || !action_out || !logp_out || n < 1) return fail_in(fn, SOLORL_ERR_INVALID, "null array or n < 1");
+  if (rows_misaligned(obs, p->obs_dim) || rows_misaligned(cobs, critic_width(p)))
+    return fail_in(fn, SOLORL_ERR_INVALID, "rows of a width that is a multiple of 4 must be 16-byte aligned (they are read as float4)");
+  const solorl_policy_params P = *p;
+  return dispatch_dims(P.obs_dim, critic_width(p), P.act_dim, [&](auto oc, auto cc, auto ac) {
+    constexpr int O = decltype(oc)::value, OC = decltype(cc)::value, A = decltype(ac)::value;
+    hipLaunchKernelGGL((policy_act_mfma_kernel<O, OC, A>), dim3((n + 31) / 32, 2), dim3(64), 0, (hipStream_t)stream, CRITIC_PASS, ACTOR_PASS, obs, cobs, noise,
+                       n, value_out, action_out, logp_out);
+    return hipGetLastError() == hipSuccess ? 0 : fail_in(fn, SOLORL_ERR_HIP, "policy_act_mfma_kernel launch");
+  });
+}
+
+// stage 1 of both forms, behind check_policy: cobs = the critic's rollout rows, cxt0 = the critic's gathered rows; the symmetric policy's
+// are batch->obs and work->xt0 (null with a null batch / work, which is refused first)
+int grad_stage1_launch(const char* fn, const solorl_policy_params* p, const solorl_ppo_batch* batch, const float* cobs, const solorl_ppo_stage1* work,
+                       float* cxt0, int device_id, void* stream) {
+  if (!batch || !work || batch->m < 1) return fail_in(fn, SOLORL_ERR_INVALID, "null argument or m < 1");
+  if (batch->m % 32 != 0) return fail_in(fn, SOLORL_ERR_INVALID, "m must be a multiple of 32 rows (the work arrays are written in tiles of 32)");
+  const int OC = critic_width(p), widest = OC > p->obs_dim ? (OC > H ? OC : H) : (p->obs_dim > H ? p->obs_dim : H);
+  if ((long long)batch->m * widest >= (1LL << 31)) return fail_in(fn, SOLORL_ERR_INVALID, "mini-batch too large (the [unit][row] arrays are indexed with 32 bits)");
+  const void* ptrs[] = {batch->obs, batch->actions, batch->old_logp, batch->adv, batch->vpred, batch->ret, batch->perm, batch->offset,
+                        work->xt0, work->c_xt1, work->c_xt2, work->c_g1, work->c_g2, work->c_gh, work->a_xt1, work->a_xt2, work->a_g1,
+                        work->a_g2, work->a_gh, work->partials, cobs, cxt0};
+  for (const void* q : ptrs) if (!q) return fail_in(fn, SOLORL_ERR_INVALID, "null array");
+  if (rows_misaligned(batch->obs, p->obs_dim) || rows_misaligned(cobs, OC))
+    return fail_in(fn, SOLORL_ERR_INVALID, "rows of a width that is a multiple of 4 must be 16-byte aligned (they are read as float4)");
+  const solorl_policy_params P = *p;
+  const solorl_ppo_batch B = *batch;
+  const solorl_ppo_stage1 W = *work;
+  return dispatch_dims(P.obs_dim, OC, P.act_dim, [&](auto oc, auto cc, auto ac) {
+    constexpr int O = decltype(oc)::value, OC_ = decltype(cc)::value, A = decltype(ac)::value;
+    constexpr int LDS = stage1_lds_bytes<O, OC_, A>();
+    if (int rc = stage1_raise_lds_limit<O, OC_, A>(device_id)) return rc;
+    hipLaunchKernelGGL((ppo_grad_stage1_mfma_kernel<O, OC_, A>), dim3((B.m + 127) / 128, 2), dim3(256), LDS, (hipStream_t)stream, CRITIC_PASS, ACTOR_PASS, B, W,
+                       cobs, cxt0);
+    return hipGetLastError() == hipSuccess ? 0 : fail_in(fn, SOLORL_ERR_HIP, "ppo_grad_stage1_mfma_kernel launch");
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -963,39 +975,13 @@ extern "C" {
 int solorl_policy_act(const solorl_policy_params* p, const float* obs, const float* noise, int n, float* value_out, float* action_out,
                       float* logp_out, int device_id, void* stream) {
   if (int rc = check_policy(p, device_id)) return rc;
-  if (!obs || !value_out || !action_out || !logp_out || n < 1) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_policy_act: null array or n < 1");
-  if (p->obs_dim % 4 == 0 && (reinterpret_cast<uintptr_t>(obs) & 15u)) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_policy_act: obs must be 16-byte aligned (rows are read as float4)");
-  const solorl_policy_params P = *p;
-  return dispatch_dims(P.obs_dim, P.act_dim, [&](auto oc, auto ac) {
-    constexpr int O = decltype(oc)::value, A = decltype(ac)::value;
-    hipLaunchKernelGGL((policy_act_mfma_kernel<O, A>), dim3((n + 31) / 32, 2), dim3(64), 0, (hipStream_t)stream, CRITIC_PASS, ACTOR_PASS, obs, noise,
-                       n, value_out, action_out, logp_out);
-    return hipGetLastError() == hipSuccess ? 0 : solorl_fail_(SOLORL_ERR_HIP, "policy_act_mfma_kernel launch");
-  });
+  return policy_act_launch("solorl_policy_act", p, obs, obs, noise, n, value_out, action_out, logp_out, stream);
 }
 
 int solorl_ppo_grad_stage1(const solorl_policy_params* p, const solorl_ppo_batch* batch, const solorl_ppo_stage1* work, int device_id,
                            void* stream) {
   if (int rc = check_policy(p, device_id)) return rc;
-  if (!batch || !work || batch->m < 1) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage1: null argument or m < 1");
-  if (batch->m % 32 != 0) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage1: m must be a multiple of 32 rows (the work arrays are written in tiles of 32)");
-  if ((long long)batch->m * (p->obs_dim > H ? p->obs_dim : H) >= (1LL << 31))
-    return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage1: mini-batch too large (the [unit][row] arrays are indexed with 32 bits)");
-  const void* ptrs[] = {batch->obs, batch->actions, batch->old_logp, batch->adv, batch->vpred, batch->ret, batch->perm, batch->offset,
-                        work->xt0, work->c_xt1, work->c_xt2, work->c_g1, work->c_g2, work->c_gh, work->a_xt1, work->a_xt2, work->a_g1,
-                        work->a_g2, work->a_gh, work->partials};
-  for (const void* q : ptrs) if (!q) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage1: null array");
-  if (p->obs_dim % 4 == 0 && (reinterpret_cast<uintptr_t>(batch->obs) & 15u)) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage1: obs must be 16-byte aligned (rows are read as float4)");
-  const solorl_policy_params P = *p;
-  const solorl_ppo_batch B = *batch;
-  const solorl_ppo_stage1 W = *work;
-  return dispatch_dims(P.obs_dim, P.act_dim, [&](auto oc, auto ac) {
-    constexpr int O = decltype(oc)::value, A = decltype(ac)::value;
-    constexpr int LDS = stage1_lds_bytes<O, A>();
-    if (int rc = stage1_raise_lds_limit<O, A>(device_id)) return rc;
-    hipLaunchKernelGGL((ppo_grad_stage1_mfma_kernel<O, A>), dim3((B.m + 127) / 128, 2), dim3(256), LDS, (hipStream_t)stream, CRITIC_PASS, ACTOR_PASS, B, W);
-    return hipGetLastError() == hipSuccess ? 0 : solorl_fail_(SOLORL_ERR_HIP, "ppo_grad_stage1_mfma_kernel launch");
-  });
+  return grad_stage1_launch("solorl_ppo_grad_stage1", p, batch, batch ? batch->obs : nullptr, work, work ? work->xt0 : nullptr, device_id, stream);
 }
 
 int solorl_ppo_grad_count(int obs_dim, int act_dim) { return 2 * H * (obs_dim + 1) + 2 * H * (H + 1) + (H + 1) + act_dim * (H + 1); }
@@ -1010,49 +996,19 @@ int solorl_ppo_grad_stage2(const solorl_policy_params* p, const solorl_ppo_stage
                            void* stream) {
   if (int rc = check_policy(p, device_id)) return rc;
   if (int rc = grad_stage2_check(work, m, out)) return rc;
-  return grad_stage2_launch(p, work, work->xt0, p->obs_dim, m, out, stream);
+  return grad_stage2_launch(p, work, work->xt0, m, out, stream);
 }
 
 int solorl_policy_act_critic(const solorl_policy_params* p, const float* obs, const float* critic_obs, const float* noise, int n, float* value_out,
                              float* action_out, float* logp_out, int device_id, void* stream) {
   if (int rc = check_policy(p, device_id, 1)) return rc;
-  if (!obs || !critic_obs || !value_out || !action_out || !logp_out || n < 1) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_policy_act_critic: null array or n < 1");
-  if ((p->obs_dim % 4 == 0 && (reinterpret_cast<uintptr_t>(obs) & 15u)) || (p->critic_obs_dim % 4 == 0 && (reinterpret_cast<uintptr_t>(critic_obs) & 15u)))
-    return solorl_fail_(SOLORL_ERR_INVALID, "solorl_policy_act_critic: rows of a width that is a multiple of 4 must be 16-byte aligned (they are read as float4)");
-  const solorl_policy_params P = *p;
-  return dispatch_dims3(P.obs_dim, P.critic_obs_dim, P.act_dim, [&](auto oc, auto cc, auto ac) {
-    constexpr int O = decltype(oc)::value, OC = decltype(cc)::value, A = decltype(ac)::value;
-    hipLaunchKernelGGL((policy_act_critic_mfma_kernel<O, OC, A>), dim3((n + 31) / 32, 2), dim3(64), 0, (hipStream_t)stream, CRITIC_PASS, ACTOR_PASS, obs,
-                       critic_obs, noise, n, value_out, action_out, logp_out);
-    return hipGetLastError() == hipSuccess ? 0 : solorl_fail_(SOLORL_ERR_HIP, "policy_act_critic_mfma_kernel launch");
-  });
+  return policy_act_launch("solorl_policy_act_critic", p, obs, critic_obs, noise, n, value_out, action_out, logp_out, stream);
 }
 
 int solorl_ppo_grad_stage1_critic(const solorl_policy_params* p, const solorl_ppo_batch* batch, const float* critic_obs, const solorl_ppo_stage1* work,
                                   float* critic_xt0, int device_id, void* stream) {
   if (int rc = check_policy(p, device_id, 1)) return rc;
-  if (!batch || !work || !critic_obs || !critic_xt0 || batch->m < 1) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage1_critic: null argument or m < 1");
-  if (batch->m % 32 != 0) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage1_critic: m must be a multiple of 32 rows (the work arrays are written in tiles of 32)");
-  const int widest = p->critic_obs_dim > H ? (p->critic_obs_dim > p->obs_dim ? p->critic_obs_dim : p->obs_dim) : (p->obs_dim > H ? p->obs_dim : H);
-  if ((long long)batch->m * widest >= (1LL << 31))
-    return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage1_critic: mini-batch too large (the [unit][row] arrays are indexed with 32 bits)");
-  const void* ptrs[] = {batch->obs, batch->actions, batch->old_logp, batch->adv, batch->vpred, batch->ret, batch->perm, batch->offset,
-                        work->xt0, work->c_xt1, work->c_xt2, work->c_g1, work->c_g2, work->c_gh, work->a_xt1, work->a_xt2, work->a_g1,
-                        work->a_g2, work->a_gh, work->partials};
-  for (const void* q : ptrs) if (!q) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage1_critic: null array");
-  if ((p->obs_dim % 4 == 0 && (reinterpret_cast<uintptr_t>(batch->obs) & 15u)) || (p->critic_obs_dim % 4 == 0 && (reinterpret_cast<uintptr_t>(critic_obs) & 15u)))
-    return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage1_critic: rows of a width that is a multiple of 4 must be 16-byte aligned (they are read as float4)");
-  const solorl_policy_params P = *p;
-  const solorl_ppo_batch B = *batch;
-  const solorl_ppo_stage1 W = *work;
-  return dispatch_dims3(P.obs_dim, P.critic_obs_dim, P.act_dim, [&](auto oc, auto cc, auto ac) {
-    constexpr int O = decltype(oc)::value, OC = decltype(cc)::value, A = decltype(ac)::value;
-    constexpr int LDS = stage1_critic_lds_bytes<O, OC, A>();
-    if (int rc = stage1_critic_raise_lds_limit<O, OC, A>(device_id)) return rc;
-    hipLaunchKernelGGL((ppo_grad_stage1_critic_mfma_kernel<O, OC, A>), dim3((B.m + 127) / 128, 2), dim3(256), LDS, (hipStream_t)stream, CRITIC_PASS, ACTOR_PASS, B, W,
-                       critic_obs, critic_xt0);
-    return hipGetLastError() == hipSuccess ? 0 : solorl_fail_(SOLORL_ERR_HIP, "ppo_grad_stage1_critic_mfma_kernel launch");
-  });
+  return grad_stage1_launch("solorl_ppo_grad_stage1_critic", p, batch, critic_obs, work, critic_xt0, device_id, stream);
 }
 
 int solorl_ppo_grad_stage2_critic(const solorl_policy_params* p, const solorl_ppo_stage1* work, const float* critic_xt0, int m, const solorl_ppo_grads* out,
@@ -1060,13 +1016,13 @@ int solorl_ppo_grad_stage2_critic(const solorl_policy_params* p, const solorl_pp
   if (int rc = check_policy(p, device_id, 1)) return rc;
   if (int rc = grad_stage2_check(work, m, out)) return rc;
   if (!critic_xt0) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage2_critic: null critic_xt0");
-  return grad_stage2_launch(p, work, critic_xt0, p->critic_obs_dim, m, out, stream);
+  return grad_stage2_launch(p, work, critic_xt0, m, out, stream);
 }
 
 int solorl_ppo_clip_adam(const solorl_policy_params* p, const solorl_ppo_grads* g, const solorl_adam_state* a, int device_id, void* stream) {
   if (int rc = check_policy(p, device_id, 2)) return rc;
   if (!g || !a || !a->exp_avg || !a->exp_avg_sq || !a->step || !a->lr) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_clip_adam: null argument");
-  const int O = p->obs_dim, A = p->act_dim, OC = p->critic_obs_dim != 0 ? p->critic_obs_dim : O;
+  const int O = p->obs_dim, A = p->act_dim, OC = critic_width(p);
   const float* ps[13] = {p->critic_w0, p->critic_b0, p->critic_w1, p->critic_b1, p->critic_w2, p->critic_b2, p->actor_w0, p->actor_b0,
                          p->actor_w1, p->actor_b1, p->mean_w, p->mean_b, p->logstd};
   const float* gs[13] = {g->critic_w0, g->critic_b0, g->critic_w1, g->critic_b1, g->critic_w2, g->critic_b2, g->actor_w0, g->actor_b0,
@@ -1083,13 +1039,8 @@ int solorl_ppo_clip_adam(const solorl_policy_params* p, const solorl_ppo_grads* 
   K.b1 = a->beta1; K.b2 = a->beta2; K.eps = a->eps; K.wd = a->weight_decay; K.max_norm = a->max_grad_norm;
   K.gscale = a->grad_scale > 0.f ? a->grad_scale : 1.0f;
   K.offset = reinterpret_cast<long long*>(a->offset); K.inc = a->offset_increment;
-  if (p->critic_obs_dim != 0)
-    return dispatch_dims3(O, OC, A, [&](auto oc, auto cc, auto ac) {
-      hipLaunchKernelGGL((ppo_clip_adam_critic_kernel<decltype(oc)::value, decltype(cc)::value, decltype(ac)::value>), dim3(1), dim3(1024), 0, (hipStream_t)stream, K);
-      return hipGetLastError() == hipSuccess ? 0 : solorl_fail_(SOLORL_ERR_HIP, "ppo_clip_adam_critic_kernel launch");
-    });
-  return dispatch_dims(O, A, [&](auto oc, auto ac) {
-    hipLaunchKernelGGL((ppo_clip_adam_kernel<decltype(oc)::value, decltype(ac)::value>), dim3(1), dim3(1024), 0, (hipStream_t)stream, K);
+  return dispatch_dims(O, OC, A, [&](auto oc, auto cc, auto ac) {
+    hipLaunchKernelGGL((ppo_clip_adam_kernel<decltype(oc)::value, decltype(cc)::value, decltype(ac)::value>), dim3(1), dim3(1024), 0, (hipStream_t)stream, K);
     return hipGetLastError() == hipSuccess ? 0 : solorl_fail_(SOLORL_ERR_HIP, "ppo_clip_adam_kernel launch");
   });
 }

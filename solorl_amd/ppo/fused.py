@@ -54,9 +54,11 @@ def fused_ppo_loss(mean, logstd, values, action, old_logp, adv, vpred, ret, clip
 # Hand-written policy kernels (csrc/solorl_ppo.hip): the whole forward of Policy.act in one launch, and one PPO mini-batch's
 # gather + forward + losses + back-propagation in one launch (the weight gradients stay GEMMs).
 
-_SUPPORTED_CRITIC = {(38, 58, 12), (41, 58, 12), (76, 96, 12), (30, 50, 8), (33, 50, 8), (60, 80, 8)}     # (obs, critic rows, act): csrc SOLO_DIMS3_LIST
-_SUPPORTED = {(76, 12), (84, 12), (38, 12), (42, 12), (60, 8), (68, 8), (30, 8), (34, 8),
-              (41, 12), (45, 12), (33, 8), (37, 8)}          # (... and zero history levels + the three command words of solorl_commands)
+# (obs, critic rows, act): csrc SOLO_DIMS_LIST.  The symmetric policy is critic rows = obs (zero or one history level, and zero history
+# levels + the three command words of solorl_commands); then the shapes built with a critic width of its own
+_SUPPORTED = {(76, 76, 12), (84, 84, 12), (38, 38, 12), (42, 42, 12), (60, 60, 8), (68, 68, 8), (30, 30, 8), (34, 34, 8),
+              (41, 41, 12), (45, 45, 12), (33, 33, 8), (37, 37, 8),
+              (38, 58, 12), (41, 58, 12), (76, 96, 12), (30, 50, 8), (33, 50, 8), (60, 80, 8)}
 
 
 def policy_kernels_supported(actor_critic):
@@ -67,10 +69,10 @@ def policy_kernels_supported(actor_critic):
     except AttributeError:
         return False
     p = next(actor_critic.parameters())
-    oc = getattr(actor_critic, "critic_obs_dim", None)
-    if oc is not None:                    # an asymmetric policy: the shapes built with a critic width; any other keeps the PyTorch path
-        return h == 64 and (o, oc, a) in _SUPPORTED_CRITIC and b.critic[0].in_features == oc and p.is_cuda and p.dtype == torch.float32
-    return h == 64 and (o, a) in _SUPPORTED and p.is_cuda and p.dtype == torch.float32
+    oc = getattr(actor_critic, "critic_obs_dim", None)          # None: symmetric (a critic width that equals obs is not a built shape)
+    if oc is not None and (oc == o or b.critic[0].in_features != oc):
+        return False
+    return h == 64 and (o, oc or o, a) in _SUPPORTED and p.is_cuda and p.dtype == torch.float32
 
 
 def _named_parameters(actor_critic):
@@ -106,6 +108,16 @@ def check_params(P):
             raise RuntimeError("policy parameter %s moved since solorl_policy_params was built; rebuild it (and any HIP graph)" % k)
 
 
+def _call(params, name, args, critic):
+    """The entry point `name` of the symmetric policy on `args` (what follows the parameters), or, where params.critic_obs_dim is set,
+    `name`_critic with the critic's arrays put in: critic = {position in that argument list: tensor}"""
+    if params.critic_obs_dim:
+        name += "_critic"
+        for i in sorted(critic):
+            args.insert(i, C.c_void_p(critic[i].data_ptr()))
+    _native.check(getattr(_native.lib(), name)(C.byref(params), *args))
+
+
 def policy_act(params, obs, noise, value_out, action_out, logp_out, critic_obs=None):
     """Policy.act (agents/ppo/policy.py:33-49) in one launch: value_out [N,1], action_out [N,A] = mean + exp(logstd) * noise
     (noise [N,A] standard normal, or None for the deterministic action), logp_out [N,1].  ``critic_obs`` [N, OC]: the critic's rows
@@ -117,17 +129,11 @@ def policy_act(params, obs, noise, value_out, action_out, logp_out, critic_obs=N
         assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
     assert obs.shape == (n, params.obs_dim) and action_out.shape == (n, params.act_dim) and value_out.numel() == n and logp_out.numel() == n
     assert (critic_obs is None) == (params.critic_obs_dim == 0), "critic_obs goes with a policy made with critic_obs_dim, and only with one"
-    if critic_obs is not None:
-        assert critic_obs.shape == (n, params.critic_obs_dim)
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().solorl_policy_act_critic(C.byref(params), C.c_void_p(obs.data_ptr()), C.c_void_p(critic_obs.data_ptr()),
-                                                                 C.c_void_p(0 if noise is None else noise.data_ptr()), n, C.c_void_p(value_out.data_ptr()),
-                                                                 C.c_void_p(action_out.data_ptr()), C.c_void_p(logp_out.data_ptr()), dev.index or 0, _native.stream(dev)))
-        return
+    assert critic_obs is None or critic_obs.shape == (n, params.critic_obs_dim)
     with torch.cuda.device(dev):
-        _native.check(_native.lib().solorl_policy_act(C.byref(params), C.c_void_p(obs.data_ptr()),
-                                                      C.c_void_p(0 if noise is None else noise.data_ptr()), n, C.c_void_p(value_out.data_ptr()),
-                                                      C.c_void_p(action_out.data_ptr()), C.c_void_p(logp_out.data_ptr()), dev.index or 0, _native.stream(dev)))
+        _call(params, "solorl_policy_act", [C.c_void_p(obs.data_ptr()), C.c_void_p(0 if noise is None else noise.data_ptr()), n, C.c_void_p(value_out.data_ptr()),
+                                            C.c_void_p(action_out.data_ptr()), C.c_void_p(logp_out.data_ptr()), dev.index or 0, _native.stream(dev)],
+              {1: critic_obs})
 
 
 class MiniBatchGrad:
@@ -173,7 +179,7 @@ class MiniBatchGrad:
         self.psum = torch.zeros(3 + A, device=dev)          # running sums of the partials over the steps of an update
         self.ent = torch.zeros(1, device=dev)               # running sum of sum_a logstd_a
         L = _native.lib()
-        self.scratch = torch.zeros(L.solorl_ppo_scratch_count2(O, OC, A, m) if OC else L.solorl_ppo_scratch_count(O, A, m), device=dev)
+        self.scratch = torch.zeros(L.solorl_ppo_scratch_count2(O, OC or O, A, m), device=dev)
         G = self.G = _native.PpoGrads()
         for k, prm in _named_parameters(actor_critic).items():
             g = prm.grad
@@ -184,17 +190,10 @@ class MiniBatchGrad:
     def __call__(self):
         check_params(self.P)
         dev = self.psum.device
-        L = _native.lib()
         with torch.cuda.device(dev):
             st = _native.stream(dev)
-            if self.OC:
-                _native.check(L.solorl_ppo_grad_stage1_critic(C.byref(self.P), C.byref(self.B), C.c_void_p(self.cobs.data_ptr()), C.byref(self.W),
-                                                              C.c_void_p(self.cxt0.data_ptr()), dev.index or 0, st))
-                _native.check(L.solorl_ppo_grad_stage2_critic(C.byref(self.P), C.byref(self.W), C.c_void_p(self.cxt0.data_ptr()), self.m, C.byref(self.G),
-                                                              dev.index or 0, st))
-                return
-            _native.check(L.solorl_ppo_grad_stage1(C.byref(self.P), C.byref(self.B), C.byref(self.W), dev.index or 0, st))
-            _native.check(L.solorl_ppo_grad_stage2(C.byref(self.P), C.byref(self.W), self.m, C.byref(self.G), dev.index or 0, st))
+            _call(self.P, "solorl_ppo_grad_stage1", [C.byref(self.B), C.byref(self.W), dev.index or 0, st], {1: self.cobs, 3: self.cxt0})
+            _call(self.P, "solorl_ppo_grad_stage2", [C.byref(self.W), self.m, C.byref(self.G), dev.index or 0, st], {1: self.cxt0})
 
     def losses(self, steps):
         """(value loss, action loss, entropy) averaged over `steps` mini-batch steps since reset()."""
@@ -215,8 +214,7 @@ class ClipAdam:
         mb = mini_batch_grad
         dev = mb.psum.device
         L = _native.lib()
-        n = (L.solorl_ppo_grad_count2(mb.P.obs_dim, mb.P.critic_obs_dim, mb.P.act_dim) if mb.P.critic_obs_dim
-             else L.solorl_ppo_grad_count(mb.P.obs_dim, mb.P.act_dim)) + mb.P.act_dim
+        n = L.solorl_ppo_grad_count2(mb.P.obs_dim, mb.P.critic_obs_dim or mb.P.obs_dim, mb.P.act_dim) + mb.P.act_dim
         assert n == sum(p.numel() for p in mb.ac.parameters())
         self.P, self.G, self.dev = mb.P, mb.G, dev
         self.exp_avg, self.exp_avg_sq = torch.zeros(n, device=dev), torch.zeros(n, device=dev)

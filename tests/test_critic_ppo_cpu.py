@@ -140,7 +140,10 @@ def test_one_update_moves_the_wide_critic_layer():
 
 def test_policy_kernels_are_claimed_for_the_built_shapes_only():
     from solorl_amd.ppo import fused
-    assert fused._SUPPORTED_CRITIC == {(38, 58, 12), (41, 58, 12), (76, 96, 12), (30, 50, 8), (33, 50, 8), (60, 80, 8)}
+    assert {s for s in fused._SUPPORTED if s[1] != s[0]} == {(38, 58, 12), (41, 58, 12), (76, 96, 12), (30, 50, 8), (33, 50, 8), (60, 80, 8)}
+    assert {(o, a) for o, oc, a in fused._SUPPORTED if oc == o} == {(76, 12), (84, 12), (38, 12), (42, 12), (60, 8), (68, 8), (30, 8), (34, 8),
+                                                                    (41, 12), (45, 12), (33, 8), (37, 8)}
+    assert len(fused._SUPPORTED) == 18
     assert not fused.policy_kernels_supported(_policy())     # (parameters on the CPU: never)
 
 
