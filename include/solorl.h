@@ -14,6 +14,9 @@
  *   solorl_increment_curriculum <- agents/ppo/envs.py:125-127 (pointgoal: solo.py:332-334)
  *   solorl_compute_returns <- agents/ppo/storage.py:35-55 (OPBuffer.compute_returns: GAE / discounted returns;
  *                             400 sequential tiny torch ops per update in the reference)
+ *   solorl_compute_returns_tl : the same with time-limit bootstrapping (no reference counterpart: its returns treat an episode the
+ *                             time limit ended like a fall): a truncated step bootstraps from the value of the observation its
+ *                             action was taken from, read from the timeout flags the step kernels write
  *   solorl_ppo_loss        <- agents/ppo/ppo.py:52-74 (clipped surrogate + clipped value loss) with the Gaussian
  *                             log-prob of agents/ppo/policy.py:51-58,171-173: ~60 elementwise torch kernels per mini-batch
  *   solorl_policy_act      <- agents/ppo/policy.py:33-49 (Policy.act on the MLPBase of :62-81): value, sampled action, log-prob
@@ -170,7 +173,11 @@ typedef struct solorl_config {
 /* Struct-of-arrays info block (replaces the per-env dicts of baseEnv.py:62-66).  Every pointer is
  * a device array of num_envs elements, or NULL to skip that field. */
 typedef struct solorl_info_soa {
-  uint8_t* timeout;          /* info['timeout'] (valid where done) */
+  /* info['timeout'] (valid where done): 1 where the time limit ended the episode, and the time limit is tested first -- a fall on the
+   * very last step is a timeout (baseEnv.py:164-167).  0 for an env the non-finite-state guard, a reached pointgoal or a
+   * solorl_terminate rule ended.  The pointers are read per call: a caller that wants a step's flags in a row of its own (the
+   * rollout rows solorl_compute_returns_tl reads) passes that step a block with this pointer set to the row. */
+  uint8_t* timeout;
   uint8_t* success;          /* info['success'] (valid where done) */
   uint8_t* nan_reset;        /* env was force-reset because its state went non-finite */
   int32_t* episode_length;   /* info['episode_length'] = timestep */
@@ -739,6 +746,26 @@ int solorl_compute_returns(const float* rewards /* [T*N] */, float* value_preds 
                            const float* masks /* [(T+1)*N] */, const float* next_value /* [N] */,
                            float* returns /* [(T+1)*N] */, int T, int N, int use_gae, float gamma,
                            float gae_lambda, int device_id, void* stream);
+
+/* The same with time-limit bootstrapping: an episode the time limit ended is cut off, not finished, and its last return must not read
+ * as that of a fall.  `timeouts` [T*N] are the bytes the step kernels write to solorl_info_soa.timeout, row t = the step that filled
+ * rewards[t]; a byte is consulted only where masks[t+1] == 0 ("valid where done"), elsewhere its value does not matter.
+ * With m = masks[t+1], V_t = value_preds[t] and  tl = (m == 0 && timeouts[t] != 0):
+ * use_gae != 0:  value_preds[T][:] = next_value;  delta_t = r_t + gamma (tl ? V_t : V_{t+1} m) - V_t;
+ *                A_t = delta_t + gamma lambda m A_{t+1};  returns[t] = A_t + V_t
+ * use_gae == 0:  returns[T][:] = next_value;  returns[t] = r_t + gamma (tl ? V_t : returns[t+1] m)
+ * A truncated step bootstraps from the value of the observation its action was taken from: that value is in the rollout already,
+ * while the episode's true last observation was overwritten by the auto-reset inside the step kernel.  This is the rsl_rl /
+ * legged_gym form (reward += gamma * value * time_out), not the bootstrap from the successor state.  The advantage chain is cut at
+ * every episode end, truncated or not.
+ * Where tl is false the arithmetic is solorl_compute_returns', expression for expression: with no truncation in the rollout the two
+ * calls write the same bits (returns, and the row value_preds[T]).  One launch, one thread per env, 17 bytes per sample (16 without GAE).
+ * Null array (timeouts too: a caller without flags calls solorl_compute_returns), T < 1 or N < 1: SOLORL_ERR_INVALID, the message
+ * starts with "solorl_compute_returns_tl:" (checked before any HIP call). */
+int solorl_compute_returns_tl(const float* rewards /* [T*N] */, float* value_preds /* [(T+1)*N] */,
+                              const float* masks /* [(T+1)*N] */, const uint8_t* timeouts /* [T*N] */,
+                              const float* next_value /* [N] */, float* returns /* [(T+1)*N] */,
+                              int T, int N, int use_gae, float gamma, float gae_lambda, int device_id, void* stream);
 
 /* Running normalisation of observations and rewards (VecNormalize, agents/running_mean_std.py:73-127).  State is the caller's device
  * memory: `stats` = mean[D], var[D], count as 2 D + 1 doubles (initially 0, 1, 1e-4: running_mean_std.py:13-16; D = the observation size,

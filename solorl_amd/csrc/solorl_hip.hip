@@ -1271,6 +1271,53 @@ __global__ void returns_kernel(const float* __restrict__ rew, float* __restrict_
   }
 }
 
+// ---- the same walk with time-limit bootstrapping (include/solorl.h solorl_compute_returns_tl): where an episode ended (m == 0) at
+// the time limit (tout != 0) the successor's term is the value of the observation the action was taken from, V_t, with weight 1
+// instead of V_{t+1} m.  The two operands are selected, the expressions are returns_kernel's: a sample that is no truncation gets
+// its bits.  The flag is consulted only where m == 0.  17 B per (t, env) sample (GAE; 16 B without, where the plain walk reads no values).
+__global__ void returns_tl_kernel(const float* __restrict__ rew, float* __restrict__ val, const float* __restrict__ msk,
+                                  const unsigned char* __restrict__ tout, const float* __restrict__ nextv, float* __restrict__ ret,
+                                  int T, int N, int use_gae, float gamma, float lam) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  const size_t S = (size_t)N;
+  if (use_gae) {
+    float vnext = nextv[n];
+    val[(size_t)T * S + n] = vnext;
+    float gae = 0.f;
+#pragma unroll 8
+    for (int t = T - 1; t >= 0; t--) {
+      const float m = msk[(size_t)(t + 1) * S + n], v = val[(size_t)t * S + n];
+      const bool tl = (m == 0.f) & (tout[(size_t)t * S + n] != 0);
+      const float boot = tl ? v : vnext, w = tl ? 1.f : m;
+      const float delta = rew[(size_t)t * S + n] + gamma * boot * w - v;
+      gae = delta + gamma * lam * m * gae;
+      ret[(size_t)t * S + n] = gae + v;
+      vnext = v;
+    }
+  } else {
+    float r = nextv[n];
+    ret[(size_t)T * S + n] = r;
+#pragma unroll 8
+    for (int t = T - 1; t >= 0; t--) {
+      // The value row is read at every step (16 B per sample), not under `if (tl)` (13 B): a load behind a branch keeps the unrolled
+      // loop from issuing the next steps' loads ahead.  -DSOLO_RETURNS_TL_BRANCH_LOAD builds that form for the A/B of
+      // tools/dev/bench_timelimit.py --variant (profiles/r26_timelimit.json "variants"); the product never defines it.
+#ifdef SOLO_RETURNS_TL_BRANCH_LOAD
+      const float m = msk[(size_t)(t + 1) * S + n];
+      const bool tl = (m == 0.f) & (tout[(size_t)t * S + n] != 0);
+      if (tl) r = val[(size_t)t * S + n];
+      r = r * gamma * (tl ? 1.f : m) + rew[(size_t)t * S + n];
+#else
+      const float m = msk[(size_t)(t + 1) * S + n], v = val[(size_t)t * S + n];
+      const bool tl = (m == 0.f) & (tout[(size_t)t * S + n] != 0);
+      r = (tl ? v : r) * gamma * (tl ? 1.f : m) + rew[(size_t)t * S + n];
+#endif
+      ret[(size_t)t * S + n] = r;
+    }
+  }
+}
+
 // ---- fused clipped-surrogate PPO loss (agents/ppo/ppo.py:52-74 + the diagonal-Gaussian log-prob / entropy of
 // agents/ppo/policy.py:51-58,171-173): forward AND the gradients w.r.t. the network heads in one pass over a
 // mini-batch.  One thread per sample; per-block partial sums (deterministic: reduced by the caller), layout
@@ -1709,6 +1756,21 @@ int solorl_compute_returns(const float* rewards, float* value_preds, const float
   HIP_TRY(hipSetDevice(device_id));
   hipLaunchKernelGGL(returns_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, rewards, value_preds, masks,
                      next_value, returns, T, N, use_gae, gamma, gae_lambda);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+int solorl_compute_returns_tl(const float* rewards, float* value_preds, const float* masks, const uint8_t* timeouts,
+                              const float* next_value, float* returns, int T, int N, int use_gae, float gamma, float gae_lambda,
+                              int device_id, void* stream) {
+  if (!rewards || !value_preds || !masks || !timeouts || !next_value || !returns)
+    return fail(SOLORL_ERR_INVALID, "solorl_compute_returns_tl: null array argument (without timeout flags call solorl_compute_returns)");
+  if (T < 1 || N < 1) return fail(SOLORL_ERR_INVALID, "solorl_compute_returns_tl: T and N must be >= 1");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(SOLORL_ERR_NODEVICE, "no HIP device available (no CPU fallback)");
+  if (device_id < 0 || device_id >= ndev) return fail(SOLORL_ERR_NODEVICE, "device_id out of range");
+  HIP_TRY(hipSetDevice(device_id));
+  hipLaunchKernelGGL(returns_tl_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, rewards, value_preds, masks,
+                     timeouts, next_value, returns, T, N, use_gae, gamma, gae_lambda);
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -116,6 +116,9 @@ class GraphedRollout:
         # an asymmetric policy (storage with critic rows): the critic reads st.critic_obs[t], which the env writes beside st.obs[t + 1]:
         # one policy launch per step (solorl_policy_act_critic where the shape is built, else act_into) plus the env's launches
         asym = getattr(st, "critic_obs", None) is not None
+        # a storage made with bootstrap_timeouts: every step launch writes its timeout flags into the storage's row by itself (the info
+        # block it is handed points there) -- no launch more, in any branch
+        tout = getattr(st, "timeouts", None)
         fused = _kernels_enabled() and policy_kernels_supported(self.ac)
         if fused:                            # one launch for the whole of Policy.act (csrc/solorl_ppo.hip)
             self._pp = policy_params(self.ac)
@@ -137,19 +140,21 @@ class GraphedRollout:
                 pal = 1 if t0 + K < self.T else 0
                 R = K + pal
                 self.envs.rollout_inplace(st.actions[t0:t0 + R], self._pp, noise[t0:t0 + R], st.value_preds[t0:t0 + R], st.action_log_probs[t0:t0 + R],
-                                          obs_out=st.obs[t0 + 1:t0 + 1 + K], rew_out=st.rewards[t0:t0 + K], done_out=done[t0:t0 + K], policy_after_last=pal)
+                                          obs_out=st.obs[t0 + 1:t0 + 1 + K], rew_out=st.rewards[t0:t0 + K], done_out=done[t0:t0 + K], policy_after_last=pal,
+                                          timeout_out=None if tout is None else tout[t0:t0 + K])
                 self.windows.append(K)
             torch.sub(torch.ones((), device=st.device), done, out=st.masks[1:].view(self.T, st.num_agents))
             return
         for t in range(self.T):
+            to_t = None if tout is None else tout[t]
             if self.step_act:
                 if t == 0:
                     policy_act(self._pp, st.obs[0], noise[0], st.value_preds[0], st.actions[0], st.action_log_probs[0])
                 if t + 1 < self.T:
                     self.envs.step_act_inplace(st.actions[t], self._pp, noise[t + 1], st.value_preds[t + 1], st.actions[t + 1], st.action_log_probs[t + 1],
-                                               obs_out=st.obs[t + 1], rew_out=st.rewards[t], done_out=done[t])
+                                               obs_out=st.obs[t + 1], rew_out=st.rewards[t], done_out=done[t], timeout_out=to_t)
                 else:
-                    self.envs.step_inplace(st.actions[t], obs_out=st.obs[t + 1], rew_out=st.rewards[t], done_out=done[t])
+                    self.envs.step_inplace(st.actions[t], obs_out=st.obs[t + 1], rew_out=st.rewards[t], done_out=done[t], timeout_out=to_t)
                 continue
             if fused:
                 policy_act(self._pp, st.obs[t], noise[t], st.value_preds[t], st.actions[t], st.action_log_probs[t],
@@ -159,9 +164,9 @@ class GraphedRollout:
             else:
                 self.ac.act_into(st.obs[t], st.value_preds[t], st.actions[t], st.action_log_probs[t])
             if asym:
-                self.envs.step_inplace(st.actions[t], obs_out=st.obs[t + 1], rew_out=st.rewards[t], done_out=done[t], critic_obs_out=st.critic_obs[t + 1])
+                self.envs.step_inplace(st.actions[t], obs_out=st.obs[t + 1], rew_out=st.rewards[t], done_out=done[t], critic_obs_out=st.critic_obs[t + 1], timeout_out=to_t)
                 continue
-            self.envs.step_inplace(st.actions[t], obs_out=st.obs[t + 1], rew_out=st.rewards[t], done_out=done[t])
+            self.envs.step_inplace(st.actions[t], obs_out=st.obs[t + 1], rew_out=st.rewards[t], done_out=done[t], timeout_out=to_t)
         torch.sub(torch.ones((), device=st.device), done, out=st.masks[1:].view(self.T, st.num_agents))
 
     def _capturable(self):

@@ -40,6 +40,10 @@ Differences that come with the GPU engine (documented, not behavioural):
     two launches behind every step launch of the eager and of the captured rollout alike (SoloVecEnv(critic_obs=)) -- while the actor
     keeps the row a robot could measure: Policy(critic_obs_dim=), RolloutStorage(critic_obs_dim=).  No policy kernel is built at a
     critic width, so the rollout's act and the mini-batch step take their PyTorch paths (inside the same HIP graphs);
+  * args.bootstrap_timeouts (train_ppo.py --bootstrap-timeouts; no reference counterpart: its returns treat an episode the time limit
+    ended like a fall) keeps the engine's timeout flag of every step in the rollout storage -- written there by the step launches
+    themselves, of the eager and of the captured rollout alike (SoloVecEnv.step_inplace(timeout_out=)) -- and computes the returns
+    with solorl_compute_returns_tl: a truncated step bootstraps from the value of the observation its action was taken from;
   * multi-GPU: one process per GPU (`python -m torch.distributed.run --nproc-per-node W ...`), envs
     sharded by rank (global env id = rank*N + i), flat-bucket RCCL gradient all-reduce (ppo.py).
 """
@@ -92,7 +96,8 @@ def rollout(envs, actor_critic, storage, num_steps):
             value, action, logp = actor_critic.act(storage.obs[step], **({"critic_inputs": storage.critic_obs[step]} if asym else {}))
         obs, reward, done, info = envs.step_inplace(action.contiguous())
         storage.append(obs, action, logp, value, reward.unsqueeze(-1), (1.0 - done.float()).unsqueeze(-1),
-                       **({"critic_obs": envs.last_critic_obs} if asym else {}))
+                       **({"critic_obs": envs.last_critic_obs} if asym else {}),
+                       **({"timeouts": info["timeout"]} if storage.timeouts is not None else {}))
 
 
 def train(args, config, env_constructor=None, writer=None):
@@ -131,7 +136,12 @@ def train(args, config, env_constructor=None, writer=None):
     agent = (GraphedPPO if use_graphs else PPO)(actor_critic, args.clip_param, args.ppo_epoch, args.mini_batch_size,
                                                  args.value_loss_coef, args.entropy_coef, lr=args.lr, l2_coef=args.l2_coef,
                                                  max_grad_norm=args.max_grad_norm)
-    storage = RolloutStorage(args.num_steps, N, envs.observation_space.shape, action_dim, device, critic_obs_dim=critic_dim)
+    bootstrap = bool(getattr(args, "bootstrap_timeouts", False))
+    storage = RolloutStorage(args.num_steps, N, envs.observation_space.shape, action_dim, device, critic_obs_dim=critic_dim,
+                             bootstrap_timeouts=bootstrap)
+    if bootstrap and rank == 0:
+        print("time-limit bootstrapping on: a step the time limit cut off bootstraps from the value of its own observation "
+              "(solorl_compute_returns_tl)", flush=True)
     storage.obs[0].copy_(envs.reset())
     if critic_dim is not None:
         storage.critic_obs[0].copy_(envs.last_critic_obs)

@@ -224,6 +224,7 @@ class SoloVecEnv:
         self.reset_randomization_count = None   # [N] int32 (uint32 words): the episodes each env has drawn an initial state for
         self._info_c = InfoSoA(ep_stats=self._ep_stats.data_ptr(), applied_torque=None if self._tau is None else self._tau.data_ptr(),
                                **{k: self._info[k].data_ptr() for k in _INFO_KEYS})
+        self._info_alt = {}         # timeout_out pointer -> _info_c with its timeout flags going there (_info_block)
         # VecNormalize (agents/running_mean_std.py:73-127; the reference's launcher passes ob=False, ret=False: agents/ppo/envs.py:26):
         # nothing is allocated or launched unless a switch is on
         self._norm = VecNormalizer(N, self.obs_dim, device, norm_obs, norm_ret, clipob, cliprew, gamma, epsilon) if (norm_obs or norm_ret) else None
@@ -473,14 +474,17 @@ class SoloVecEnv:
         self._term_eps[1] = self._ep_stats[0].sum(dtype=torch.float64)      # episodes finished before now are not this termination's
         self._term = p
 
-    def _terminate(self, e, rew, done):
+    def _terminate(self, e, rew, done, info=None):
         """the early termination of a control step, behind its step launch: the state after the step, one launch on the step's
-        outputs, and the reset of the envs it ended into the engine's observation rows ``e`` -> the rows (pre-reset) or None"""
+        outputs (``info``: the block the step launch was given, default the engine-owned one -- a rule-ended env reads timeout == 0
+        wherever the step wrote its flags), and the reset of the envs it ended into the engine's observation rows ``e`` -> the rows
+        (pre-reset) or None"""
         if self._term is None:
             return None
         from .termination import terminate
         rows = self.get_states(out=self._term_states)
-        terminate(self.cfg, self._term, rows, done, rew, self.last_termination, info=self._info_c, term_stats=self._term_stats)
+        terminate(self.cfg, self._term, rows, done, rew, self.last_termination, info=self._info_c if info is None else info,
+                  term_stats=self._term_stats)
         with torch.cuda.device(self.device):
             _native.check(self.L.solorl_reset_masked(self._h, C.c_void_p(self.last_termination.data_ptr()), C.c_void_p(e.data_ptr()), self._stream()))
         return rows
@@ -710,13 +714,14 @@ class SoloVecEnv:
         self._kick()
         return applied
 
-    def _after_step(self, e, o, r, d, actions, tail=False, clean=None, critic_out=None):
+    def _after_step(self, e, o, r, d, actions, tail=False, clean=None, critic_out=None, info=None):
         """behind a step launch that wrote the engine's observation rows ``e``, rewards ``r`` and done flags ``d``: every stage that is
         set, in the one order there is; ``o``: the caller's observation rows (``e`` without commands).  ``tail``: the subset of
         step_act_inplace -- restarts, shaped terms, return normalisation -- whose policy has already read ``o``.  ``clean``: the rows
-        the launch wrote instead of ``e`` (_clean_rows: the noise then writes ``e`` from them); ``critic_out``: where the critic rows go"""
+        the launch wrote instead of ``e`` (_clean_rows: the noise then writes ``e`` from them); ``critic_out``: where the critic rows go;
+        ``info``: the info block the launch was given (_info_block), which the early termination books into"""
         c = e if clean is None else clean
-        rows = None if tail else self._terminate(c, r, d)
+        rows = None if tail else self._terminate(c, r, d, info)
         self._restarts(d)
         rows = self._shape(actions, r, d, rows)         # (with commands: against the command the policy acted on, before it is redrawn)
         if not tail:
@@ -744,14 +749,35 @@ class SoloVecEnv:
         return (o, r, d, self._raw("obs_out", o, lead + (self.nenvs, self.obs_dim)), self._per_env("rew_out", r, lead),
                 self._raw("done_out", d, lead + (self.nenvs,), dtype=torch.uint8))
 
-    def step_inplace(self, actions, obs_out=None, rew_out=None, done_out=None, critic_obs_out=None):
+    def _info_block(self, base, tensors, alt, timeout_out, lead):
+        """The info block and the info tensors of a launch: the engine-owned ``base`` / ``tensors``, or -- with ``timeout_out``, a
+        caller-owned uint8 lead + [N] or [N, 1] tensor such as a rollout-storage row -- a copy of the block whose ``timeout`` pointer is
+        the caller's row, and the tensors with that row under "timeout".  The C ABI takes the info pointers per call, so the flags
+        land in the caller's row by the step launch itself: no copy, no further launch.  The copies are kept in ``alt`` per
+        destination pointer (a rollout storage has T of them)."""
+        if timeout_out is None:
+            return base, tensors
+        p = self._raw("timeout_out", timeout_out, lead + (self.nenvs,), lead + (self.nenvs, 1), dtype=torch.uint8).value
+        c = alt.get(p)
+        if c is None:
+            if len(alt) >= 4096:                        # (a caller that hands over a new tensor at every step)
+                alt.clear()
+            c = alt[p] = InfoSoA.from_buffer_copy(base)
+            c.timeout = p
+        return c, dict(tensors, timeout=timeout_out)
+
+    def step_inplace(self, actions, obs_out=None, rew_out=None, done_out=None, critic_obs_out=None, timeout_out=None):
         """Zero-copy variant for rollout loops: returns views of the engine-owned output buffers (overwritten by the next
         step) -- or writes observations [N, O] / rewards [N] or [N, 1] / done flags (uint8 [N]) straight into caller-owned tensors
         such as rollout-storage rows (the C ABI takes the caller's pointers anyway).  Host-side checks only, capturable in a HIP graph.
         With velocity commands O is the wide width: the engine writes its own narrow buffer and solorl_commands the caller's rows.
-        ``critic_obs_out`` (an env made with critic_obs): where the critic rows [N, critic_obs_dim] go instead of last_critic_obs."""
+        ``critic_obs_out`` (an env made with critic_obs): where the critic rows [N, critic_obs_dim] go instead of last_critic_obs.
+        ``timeout_out`` (uint8 [N] or [N, 1]): where the step's timeout flags go instead of the engine-owned info["timeout"] -- the
+        returned info then holds that row.  The flag is 1 where the time limit ended the episode (tested first: a fall on the very last
+        step is a timeout) and 0 for every other env, one that a termination rule, the NaN guard or a reached goal ended included."""
         a = self._raw("actions", actions, (self.nenvs, self.act_dim))
         o, r, d, po, pr, pd = self._outputs((), (self._obs, self._rew, self._done), obs_out, rew_out, done_out)
+        ic, info = self._info_block(self._info_c, self._info, self._info_alt, timeout_out, ())
         if critic_obs_out is not None:
             if self._critic is None:
                 raise _native.SoloRLError("critic_obs_out on an env made without critic_obs (the width is fixed at construction: "
@@ -764,9 +790,9 @@ class SoloVecEnv:
         if applied is not actions:
             a = C.c_void_p(applied.data_ptr())
         with torch.cuda.device(self.device):
-            _native.check(self.L.solorl_step(self._h, a, C.c_void_p(c.data_ptr()), pr, pd, C.byref(self._info_c), self._stream()))
-        self._after_step(e, o, r, d, actions, clean=c, critic_out=critic_obs_out)
-        return o, r, d, self._info
+            _native.check(self.L.solorl_step(self._h, a, C.c_void_p(c.data_ptr()), pr, pd, C.byref(ic), self._stream()))
+        self._after_step(e, o, r, d, actions, clean=c, critic_out=critic_obs_out, info=ic)
+        return o, r, d, info
 
     def step_act_supported(self, params):
         """The policy tail's prerequisites (solorl_step_act, solorl_rollout; include/solorl.h), decided from the handle -- what the engine
@@ -776,12 +802,15 @@ class SoloVecEnv:
                 and self.get_property("step_n_one_launch") == 1 and self.get_property("f64") == 0 and self.obs_dim % 4 == 0 and self.obs_dim <= 88
                 and params.obs_dim == self.obs_dim and params.act_dim == self.act_dim and params.hidden == 64)
 
-    def step_act_inplace(self, actions, params, noise, value_out, action_out, logp_out, obs_out=None, rew_out=None, done_out=None):
+    def step_act_inplace(self, actions, params, noise, value_out, action_out, logp_out, obs_out=None, rew_out=None, done_out=None,
+                         timeout_out=None):
         """step_inplace + Policy.act on the new observations in ONE launch (solorl_step_act): value_out [N] or [N,1], action_out [N,A] =
-        mean + exp(logstd) * noise (noise [N,A] or None), logp_out [N] or [N,1] -- e.g. the NEXT step's rollout-storage rows."""
+        mean + exp(logstd) * noise (noise [N,A] or None), logp_out [N] or [N,1] -- e.g. the NEXT step's rollout-storage rows.
+        ``timeout_out`` as step_inplace's (still one launch)."""
         self._no_policy_tail("step_act_inplace")
         a = self._raw("actions", actions, (self.nenvs, self.act_dim))
         o, r, d, po, pr, pd = self._outputs((), (self._obs, self._rew, self._done), obs_out, rew_out, done_out)
+        ic, info = self._info_block(self._info_c, self._info, self._info_alt, timeout_out, ())
         pv = self._per_env("value_out", value_out, ())
         pa = self._raw("action_out", action_out, (self.nenvs, self.act_dim))
         pl = self._per_env("logp_out", logp_out, ())
@@ -791,9 +820,9 @@ class SoloVecEnv:
         if applied is not actions:
             a = C.c_void_p(applied.data_ptr())
         with torch.cuda.device(self.device):
-            _native.check(self.L.solorl_step_act(self._h, a, po, pr, pd, C.byref(self._info_c), C.byref(params), pn, pv, pa, pl, self._stream()))
+            _native.check(self.L.solorl_step_act(self._h, a, po, pr, pd, C.byref(ic), C.byref(params), pn, pv, pa, pl, self._stream()))
         self._after_step(o, o, r, d, actions, tail=True)
-        return o, r, d, self._info
+        return o, r, d, info
 
     def _k_rows(self, K):
         """Engine-owned output rows [K, N, ...] and their info block (every per-step field [K, N], applied torques [K, N, A] when
@@ -808,7 +837,7 @@ class SoloVecEnv:
                 info["applied_torque"] = tau
             c = InfoSoA(ep_stats=self._ep_stats.data_ptr(), applied_torque=None if tau is None else tau.data_ptr(),
                         **{k: info[k].data_ptr() for k in _INFO_KEYS})
-            b = dict(obs=None, info=info, tau=tau, c=c)
+            b = dict(obs=None, info=info, tau=tau, c=c, alt={})      # alt: as _info_alt, for this K's block
             self._kbuf[K] = b
         return b
 
@@ -830,10 +859,11 @@ class SoloVecEnv:
         t["done"] = d.clone()
         return o.clone(), r.clone().unsqueeze(-1), t["done"].float(), t
 
-    def step_n_inplace(self, actions, obs_out=None, rew_out=None, done_out=None):
+    def step_n_inplace(self, actions, obs_out=None, rew_out=None, done_out=None, timeout_out=None):
         """step_inplace for K steps: actions [K, N, A] (float32, contiguous, on this device); returns views of engine-owned rows
         (overwritten by the next call with the same K) -- or writes observations [K, N, O] / rewards [K, N] or [K, N, 1] / done flags
-        (uint8 [K, N]) straight into caller-owned tensors such as rollout-storage rows.  Host-side checks only, capturable."""
+        (uint8 [K, N]) / timeout flags (``timeout_out``: uint8 [K, N] or [K, N, 1]) straight into caller-owned tensors such as
+        rollout-storage rows.  Host-side checks only, capturable."""
         self._refuse("step_n", k_step=True)
         K = int(actions.shape[0]) if actions.dim() == 3 else 0
         if K < 1:
@@ -841,12 +871,13 @@ class SoloVecEnv:
         pa = self._raw("actions", actions, (K, self.nenvs, self.act_dim))
         b = self._k_rows(K)
         o, r, d, po, pr, pd = self._rows_out(b, K, obs_out, rew_out, done_out)
+        ic, info = self._info_block(b["c"], b["info"], b["alt"], timeout_out, (K,))
         self._steps_issued += K
         with torch.cuda.device(self.device):
-            _native.check(self.L.solorl_step_n(self._h, K, pa, po, pr, pd, C.byref(b["c"]), self._stream()))
+            _native.check(self.L.solorl_step_n(self._h, K, pa, po, pr, pd, C.byref(ic), self._stream()))
         if self._norm is not None:                      # one call for the window's K rows
             self._normalize(o, r, d, K)
-        return o, r, d, b["info"]
+        return o, r, d, info
 
     def rollout_supported(self, params):
         """solorl_rollout (K closed-loop steps in one launch) on this handle: the prerequisites of solorl_step_act, and no perturbation
@@ -854,11 +885,13 @@ class SoloVecEnv:
         observation noise nor actuation set (their launches stand behind and in front of every step launch)."""
         return not any(between is not None and is_set(self) for _, is_set, _, between, _, _ in _STAGES) and self.step_act_supported(params)
 
-    def rollout_inplace(self, actions, params, noise, value_out, logp_out, obs_out=None, rew_out=None, done_out=None, policy_after_last=False):
+    def rollout_inplace(self, actions, params, noise, value_out, logp_out, obs_out=None, rew_out=None, done_out=None, policy_after_last=False,
+                        timeout_out=None):
         """K closed-loop steps in one launch (solorl_rollout), in rollout-storage rows: actions [K (+1), N, A] -- row 0 drives the
         first step, rows 1.. are written by the policy on the observations the steps produce (row K too with policy_after_last: the
         first action of the next window); noise [K (+1), N, A] or None (actions = the mean); value_out / logp_out [K (+1), N] or
-        [K (+1), N, 1], rows from 1 written; obs_out [K, N, O], rew_out [K, N] or [K, N, 1], done_out uint8 [K, N] as step_n_inplace."""
+        [K (+1), N, 1], rows from 1 written; obs_out [K, N, O], rew_out [K, N] or [K, N, 1], done_out uint8 [K, N] and timeout_out
+        uint8 [K, N] or [K, N, 1] as step_n_inplace."""
         self._refuse("rollout_inplace", tail=True)
         self._refuse("rollout_inplace", k_step=True)
         pal = 1 if policy_after_last else 0
@@ -871,12 +904,13 @@ class SoloVecEnv:
         pv, pl = self._per_env("value_out", value_out, (R,)), self._per_env("logp_out", logp_out, (R,))
         b = self._k_rows(K)
         o, r, d, po, pr, pd = self._rows_out(b, K, obs_out, rew_out, done_out)
+        ic, info = self._info_block(b["c"], b["info"], b["alt"], timeout_out, (K,))
         self._steps_issued += K
         with torch.cuda.device(self.device):
-            _native.check(self.L.solorl_rollout(self._h, K, pa, po, pr, pd, C.byref(b["c"]), C.byref(params), pn, pv, pl, pal, self._stream()))
+            _native.check(self.L.solorl_rollout(self._h, K, pa, po, pr, pd, C.byref(ic), C.byref(params), pn, pv, pl, pal, self._stream()))
         if self._norm_ret:                              # one call for the window's K rows, after the window
             self._normalize(o, r, d, K)
-        return o, r, d, b["info"]
+        return o, r, d, info
 
     def get_observation(self):
         """The clean observation rows; with velocity commands the current command words are appended (by torch ops)"""

@@ -165,6 +165,9 @@ def get_ppo_args(argv=None):
                         "words of the simulator's truth (contact forces, foot heights and speeds, the command, the episode's progress, "
                         "collisions, the drawn latency and gain error, the last kick); FILE.yaml holds scales per group of words, e.g. "
                         "configs/critic_walk12.yaml (without a file: the defaults; default: the critic reads the actor's rows)")
+    p.add_argument("--bootstrap-timeouts", action="store_true", default=False,
+                   help="time-limit bootstrapping: a step the time limit cut off bootstraps its return from the value of the observation its "
+                        "action was taken from, instead of reading as a fall (default: off, the reference's returns)")
     p.add_argument("--num-steps", type=int, default=None, help="rollout length (default: episode_length, train_ppo.py:62-63)")
     return p.parse_args(argv)
 
