@@ -812,7 +812,10 @@ int solorl_ppo_loss(const float* mean, const float* logstd, const float* values,
  * {(41|45, 12), (33|37, 8)} -- zero history levels with the three command words of solorl_commands; other shapes
  * return SOLORL_ERR_INVALID and the caller keeps its framework path.  Alignment: the weight matrices critic_w1/w2, actor_w1,
  * mean_w -- and, when obs_dim % 4 == 0, critic_w0, actor_w0 and every `obs` array handed to solorl_policy_act /
- * solorl_ppo_batch -- are read as float4 rows and must start on a 16-byte boundary (checked: SOLORL_ERR_INVALID otherwise). */
+ * solorl_ppo_batch -- are read as float4 rows and must start on a 16-byte boundary (checked: SOLORL_ERR_INVALID otherwise).
+ * The same table goes to the width-generic family (the _w entry points at the end of this header), which takes hidden = 64,
+ * act_dim 8 or 12 and ANY obs_dim and critic_obs_dim up to SOLORL_POLICY_MAX_WIDTH, the shapes above included. */
+#define SOLORL_POLICY_MAX_WIDTH 128
 typedef struct solorl_policy_params {
   int obs_dim, act_dim, hidden;
   int critic_obs_dim;   /* 0: the critic reads the actor's rows (symmetric); OC != 0: critic_w0 is [64][OC] and the critic reads rows of OC
@@ -941,6 +944,22 @@ int solorl_ppo_grad_stage2_critic(const solorl_policy_params* p, const solorl_pp
                                   const solorl_ppo_grads* out, int device_id, void* stream);
 int solorl_ppo_grad_count2(int obs_dim, int critic_obs_dim, int act_dim);
 int solorl_ppo_scratch_count2(int obs_dim, int critic_obs_dim, int act_dim, int m);
+
+/* The width-generic family: the same four steps for hidden = 64, act_dim 8 or 12 and any 1 <= obs_dim <= SOLORL_POLICY_MAX_WIDTH,
+ * critic_obs_dim = 0 (symmetric) or 1 .. SOLORL_POLICY_MAX_WIDTH other than obs_dim; anything else is SOLORL_ERR_INVALID with a message that
+ * names the cap.  The widths are run-time values of ONE kernel per action width instead of a template instance per shape, and every sum is
+ * taken in the order the per-shape kernels take it: at a shape those are built for, these write the same bits.  One set of entry points
+ * serves both forms: critic_obs / critic_xt0 are NULL for the symmetric policy (critic_obs_dim = 0) and the critic's arrays, as in the
+ * _critic entry points, for a policy with a critic width; given with critic_obs_dim = 0, or missing with one set, they are refused.
+ * Working memory and moments are sized by solorl_ppo_scratch_count2 / solorl_ppo_grad_count2 with the critic's width (obs_dim for the
+ * symmetric policy).  Alignment, the multiples of 32 / 64 rows and the 32-bit bound on m x width are those of the entry points above. */
+int solorl_policy_act_w(const solorl_policy_params* p, const float* obs /* [n][obs_dim] */, const float* critic_obs /* [n][OC] or NULL */,
+                        const float* noise, int n, float* value_out, float* action_out, float* logp_out, int device_id, void* stream);
+int solorl_ppo_grad_stage1_w(const solorl_policy_params* p, const solorl_ppo_batch* batch, const float* critic_obs,
+                             const solorl_ppo_stage1* work, float* critic_xt0, int device_id, void* stream);
+int solorl_ppo_grad_stage2_w(const solorl_policy_params* p, const solorl_ppo_stage1* work, const float* critic_xt0, int m,
+                             const solorl_ppo_grads* out, int device_id, void* stream);
+int solorl_ppo_clip_adam_w(const solorl_policy_params* p, const solorl_ppo_grads* g, const solorl_adam_state* a, int device_id, void* stream);
 
 const char* solorl_last_error(void);
 const char* solorl_version(void);

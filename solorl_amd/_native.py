@@ -22,7 +22,10 @@ SYMBOLS = ("solorl_default_config", "solorl_create", "solorl_destroy", "solorl_d
            "solorl_norm_scratch_count", "solorl_normalize_obs", "solorl_normalize_rewards", "solorl_kinematics", "solorl_dynamics",
            "solorl_shape_reward", "solorl_obs_noise", "solorl_actuate", "solorl_commands", "solorl_shape_reward_cmd",
            "solorl_terminate", "solorl_randomize_reset", "solorl_restart_history", "solorl_critic_obs",
-           "solorl_policy_act_critic", "solorl_ppo_grad_stage1_critic", "solorl_ppo_grad_stage2_critic", "solorl_ppo_grad_count2", "solorl_ppo_scratch_count2")
+           "solorl_policy_act_critic", "solorl_ppo_grad_stage1_critic", "solorl_ppo_grad_stage2_critic", "solorl_ppo_grad_count2", "solorl_ppo_scratch_count2",
+           "solorl_policy_act_w", "solorl_ppo_grad_stage1_w", "solorl_ppo_grad_stage2_w", "solorl_ppo_clip_adam_w")
+
+POLICY_MAX_WIDTH = 128                      # SOLORL_POLICY_MAX_WIDTH
 
 
 class PolicyParams(C.Structure):            # solorl_policy_params
@@ -162,6 +165,11 @@ def lib():
         L.solorl_ppo_grad_count2.argtypes = [C.c_int, C.c_int, C.c_int]
         L.solorl_ppo_scratch_count2.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
         L.solorl_ppo_clip_adam.argtypes = [C.POINTER(PolicyParams), C.POINTER(PpoGrads), C.POINTER(AdamState), C.c_int, C.c_void_p]
+        # the width-generic family: the _critic argument lists, the critic's arrays NULL for a symmetric policy
+        L.solorl_policy_act_w.argtypes = L.solorl_policy_act_critic.argtypes
+        L.solorl_ppo_grad_stage1_w.argtypes = L.solorl_ppo_grad_stage1_critic.argtypes
+        L.solorl_ppo_grad_stage2_w.argtypes = L.solorl_ppo_grad_stage2_critic.argtypes
+        L.solorl_ppo_clip_adam_w.argtypes = L.solorl_ppo_clip_adam.argtypes
         # running normalisation: stats / ret / scratch are device pointers to doubles
         L.solorl_norm_scratch_count.argtypes = [C.c_int, C.c_int, C.c_int]
         L.solorl_normalize_obs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double,

@@ -17,6 +17,9 @@
 // into an xt0 of its own.  The symmetric policy (solorl_policy_params.critic_obs_dim = 0) is the instance OC = O, launched with the
 // actor's rows and the shared xt0 in the critic's places; a critic width of its own (the asymmetric actor-critic) goes through the
 // _critic entry points, which take the two extra arrays.  Stage 2 / 3 and the host code take OC at run time in the same way.
+// Beside it stands a second, width-generic family behind the _w entry points (policy_act_w_kernel, ppo_grad_stage1_w_kernel,
+// ppo_clip_adam_w_kernel: one instance per action width, O and OC up to SOLORL_POLICY_MAX_WIDTH as run-time values, opt-in from Python):
+// the same device functions with O = 0 for "the width is an argument", every sum in the same order ("run-time value" below).
 //
 // The three product kernels run on the matrix cores (exact-f32 MFMA), see "MFMA formulation" below.  Two VALU formulations
 // (lane = row; weights through scalar loads, then through LDS broadcast reads) were built and measured first:
@@ -163,6 +166,7 @@ template <int O, int NOUT, bool BACKWARD> struct NetRegs {
   static constexpr int QO = (O + 7) / 8, QA = (NOUT + 7) / 8;
   float a0[2][QO][4], a1[2][8][4], ah[8][4];
   float aht[BACKWARD ? 2 : 1][QA][4], a1t[BACKWARD ? 2 : 1][BACKWARD ? 8 : 1][4];
+  static constexpr bool live(int) { return true; }       // every q < QO is a step of layer 0 (the run-time-width holders below: q < their qo)
   // operand access, four consecutive contraction steps at a time (the interface NetLds shares)
   __device__ __forceinline__ float4 A0(int mt, int q) const { return make_float4(a0[mt][q][0], a0[mt][q][1], a0[mt][q][2], a0[mt][q][3]); }
   __device__ __forceinline__ float4 A1(int mt, int q) const { return make_float4(a1[mt][q][0], a1[mt][q][1], a1[mt][q][2], a1[mt][q][3]); }
@@ -223,13 +227,16 @@ template <int O, int NOUT> struct NetLds {
   static constexpr int E_A0 = 0, E_A1 = E_A0 + 2 * QO, E_AH = E_A1 + 16, E_AHT = E_AH + 8, E_A1T = E_AHT + 2 * QA, NE = E_A1T + 16;
   static constexpr int BYTES = NE * 64 * 16;
   const float4* img;        // + lane
+  static constexpr bool live(int) { return true; }
+  static constexpr int count(int) { return NE; }         // entries of the image at this width
+  static __device__ __forceinline__ NetLds at(const float4* img, int) { return NetLds{img}; }
   __device__ __forceinline__ float4 A0(int mt, int q) const { return img[(E_A0 + mt * QO + q) * 64]; }
   __device__ __forceinline__ float4 A1(int mt, int q) const { return img[(E_A1 + mt * 8 + q) * 64]; }
   __device__ __forceinline__ float4 AH(int q) const { return img[(E_AH + q) * 64]; }
   __device__ __forceinline__ float4 AHT(int mt, int q) const { return img[(E_AHT + mt * QA + q) * 64]; }
   __device__ __forceinline__ float4 A1T(int mt, int q) const { return img[(E_A1T + mt * 8 + q) * 64]; }
   // entry e of the image for lane (c, h), from the PyTorch-layout parameters (what NetRegs::load puts into registers)
-  static __device__ __forceinline__ float4 entry(int e, NET_ARGS, int c, int h) {
+  static __device__ __forceinline__ float4 entry(int e, NET_ARGS, int c, int h, int = O) {
     float v[4] = {0.f, 0.f, 0.f, 0.f};
     if (e < E_A1) {
       const int mt = e / QO, q = e % QO, i0 = 8 * q + 4 * h;
@@ -268,6 +275,7 @@ __device__ __forceinline__ float comp4(const float4& f, int t) { return t == 0 ?
 template <int O> struct ObsRow {
   static constexpr int QO = (O + 7) / 8;
   float x[QO][4];
+  static constexpr int width() { return O; }
   __device__ __forceinline__ void load(const float* __restrict__ xrow, int h) {
 #pragma unroll
     for (int q = 0; q < QO; ++q) {
@@ -284,9 +292,126 @@ template <int O> struct ObsRow {
   }
 };
 
-template <int O, int NOUT, typename WT, typename S1, typename S2>
+// ---------------------------------------------------------------- the same holders with the input width as a RUN-TIME value
+// The width-generic family (the _w entry points): one kernel per action width for every input width up to SOLORL_POLICY_MAX_WIDTH.
+// Only layer 0 knows the width.  Each holder is laid out for the cap -- QO = 16 groups of 8 inputs -- and carries qo = ceil(width / 8);
+// the layer-0 loops stay fully unrolled over the 16 groups, so every register index is static (a run-time index into a register
+// array is served from scratch), and a group q >= qo is skipped by a wave-uniform branch: no load, no MFMA.  What is left is
+// mfma_forward's own sequence q = 0 .. qo - 1, t = 0 .. 3 into the two unit tiles with zero operands past the width: at a width the
+// templates are built for, the same bits.
+constexpr int WMAX = SOLORL_POLICY_MAX_WIDTH, QMAX = WMAX / 8;
+static_assert(WMAX % 32 == 0 && WMAX <= 128, "stage 2 computes at most four input tiles per wavefront");
+
+// the lane's four inputs 8 q + 4 h .. + 3 of a row of w words: one float4 where w is a multiple of 4, else word by word (zero past w)
+__device__ __forceinline__ float4 load4_w(const float* __restrict__ row, int i0, int w, bool vec) {
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (vec) { if (i0 < w) v = *reinterpret_cast<const float4*>(row + i0); }
+  else {
+    if (i0 < w) v.x = row[i0];
+    if (i0 + 1 < w) v.y = row[i0 + 1];
+    if (i0 + 2 < w) v.z = row[i0 + 2];
+    if (i0 + 3 < w) v.w = row[i0 + 3];
+  }
+  return v;
+}
+
+struct ObsRowW {
+  float x[QMAX][4];
+  int w;
+  __device__ __forceinline__ int width() const { return w; }
+  __device__ __forceinline__ void load(const float* __restrict__ xrow, int h, int w_) {
+    w = w_;
+    const int qo = (w + 7) / 8;
+    const bool vec = w % 4 == 0;
+#pragma unroll
+    for (int q = 0; q < QMAX; ++q) {
+      if (q < qo) { const float4 v = load4_w(xrow, 8 * q + 4 * h, w, vec); x[q][0] = v.x; x[q][1] = v.y; x[q][2] = v.z; x[q][3] = v.w; }
+    }
+  }
+};
+
+// act: layers 1, 2 and the head as NetRegs holds them; layer 0 for up to 16 groups, the loads of the live ones issued together
+template <int NOUT> struct NetRegsW {
+  static constexpr int QO = QMAX;
+  float4 a0[2][QMAX];
+  float a1[2][8][4], ah[8][4];
+  int qo;
+  __device__ __forceinline__ bool live(int q) const { return q < qo; }
+  __device__ __forceinline__ float4 A0(int mt, int q) const { return a0[mt][q]; }
+  __device__ __forceinline__ float4 A1(int mt, int q) const { return make_float4(a1[mt][q][0], a1[mt][q][1], a1[mt][q][2], a1[mt][q][3]); }
+  __device__ __forceinline__ float4 AH(int q) const { return make_float4(ah[q][0], ah[q][1], ah[q][2], ah[q][3]); }
+  __device__ __forceinline__ void load(NET_ARGS, int c, int h, int w) {
+    qo = (w + 7) / 8;
+    const bool vec = w % 4 == 0;
+#pragma unroll
+    for (int q = 0; q < QMAX; ++q) {
+      if (q < qo) {
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) a0[mt][q] = load4_w(w0 + (size_t)(32 * mt + c) * w, 8 * q + 4 * h, w, vec);
+      }
+    }
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const float4 v = *reinterpret_cast<const float4*>(w1 + (32 * mt + c) * H + 8 * q + 4 * h);
+        a1[mt][q][0] = v.x; a1[mt][q][1] = v.y; a1[mt][q][2] = v.z; a1[mt][q][3] = v.w;
+      }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (c < NOUT) v = *reinterpret_cast<const float4*>(wh + c * H + 8 * q + 4 * h);
+      ah[q][0] = v.x; ah[q][1] = v.y; ah[q][2] = v.z; ah[q][3] = v.w;
+    }
+  }
+};
+
+// stage 1: NetLds' image with the entries that do not depend on the width FIRST (A1, AH, AHT, A1T: compile-time offsets) and the
+// 2 qo layer-0 entries behind them -- 44 + 2 qo entries of 1 KB for the actor at A = 12, 76 KB at the cap: two workgroups fit the
+// 160 KB of a CU at every width
+template <int NOUT> struct NetLdsW {
+  static constexpr int QO = QMAX, QA = (NOUT + 7) / 8;
+  static constexpr int E_A1 = 0, E_AH = E_A1 + 16, E_AHT = E_AH + 8, E_A1T = E_AHT + 2 * QA, E_A0 = E_A1T + 16, NE = E_A0 + 2 * QMAX;   // NE: at the cap
+  const float4* img;        // + lane
+  int qo;
+  static __device__ __forceinline__ int count(int w) { return E_A0 + 2 * ((w + 7) / 8); }
+  static __device__ __forceinline__ NetLdsW at(const float4* img, int w) { return NetLdsW{img, (w + 7) / 8}; }
+  __device__ __forceinline__ bool live(int q) const { return q < qo; }
+  __device__ __forceinline__ float4 A0(int mt, int q) const { return img[(E_A0 + mt * qo + q) * 64]; }
+  __device__ __forceinline__ float4 A1(int mt, int q) const { return img[(E_A1 + mt * 8 + q) * 64]; }
+  __device__ __forceinline__ float4 AH(int q) const { return img[(E_AH + q) * 64]; }
+  __device__ __forceinline__ float4 AHT(int mt, int q) const { return img[(E_AHT + mt * QA + q) * 64]; }
+  __device__ __forceinline__ float4 A1T(int mt, int q) const { return img[(E_A1T + mt * 8 + q) * 64]; }
+  static __device__ __forceinline__ float4 entry(int e, NET_ARGS, int c, int h, int w) {
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (e >= E_A0) {
+      const int qo = (w + 7) / 8, mt = e - E_A0 >= qo ? 1 : 0, q = e - E_A0 - mt * qo;
+      return load4_w(w0 + (size_t)(32 * mt + c) * w, 8 * q + 4 * h, w, w % 4 == 0);
+    } else if (e < E_AH) {
+      const int mt = (e - E_A1) / 8, q = (e - E_A1) % 8;
+      return *reinterpret_cast<const float4*>(w1 + (32 * mt + c) * H + 8 * q + 4 * h);
+    } else if (e < E_AHT) {
+      if (c < NOUT) return *reinterpret_cast<const float4*>(wh + c * H + 8 * (e - E_AH) + 4 * h);
+    } else if (e < E_A1T) {
+      const int mt = (e - E_AHT) / QA, q = (e - E_AHT) % QA;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) { const int a = 8 * q + 4 * h + t; if (a < NOUT) v[t] = wh[a * H + 32 * mt + c]; }
+    } else {
+      const int mt = (e - E_A1T) / 8, q = (e - E_A1T) % 8;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) v[t] = w1[(8 * q + 4 * h + t) * H + 32 * mt + c];
+    }
+    return make_float4(v[0], v[1], v[2], v[3]);
+  }
+};
+// the holders of width O; O = 0: the run-time width
+template <int O> using RowOf = std::conditional_t<O == 0, ObsRowW, ObsRow<O>>;
+template <int O, int NOUT> using LdsOf = std::conditional_t<O == 0, NetLdsW<NOUT>, NetLds<O, NOUT>>;
+
+// XT: the row's holder, ObsRow<O> or ObsRowW (O = 0)
+template <int O, int NOUT, typename WT, typename XT, typename S1, typename S2>
 __device__ __forceinline__ void mfma_forward(const WT& R, const float* __restrict__ b0, const float* __restrict__ b1,
-                                             const float* __restrict__ bh, const ObsRow<O>& X, int h, f32x16 (&h1)[2],
+                                             const float* __restrict__ bh, const XT& X, int h, f32x16 (&h1)[2],
                                              f32x16 (&h2)[2], f32x16& dh, S1&& store_x, S2&& store_h) {
   constexpr int QO = WT::QO;
 #pragma unroll
@@ -297,14 +422,16 @@ __device__ __forceinline__ void mfma_forward(const WT& R, const float* __restric
   for (int v = 0; v < 16; ++v) { const int a = unit_of(0, v, h); dh[v] = a < NOUT ? bh[a] : 0.f; }
 #pragma unroll
   for (int q = 0; q < QO; ++q) {
-    const int i0 = 8 * q + 4 * h;
-    const float (&x)[4] = X.x[q];
-    if (i0 < O) store_x(i0, x);
-    const float4 wa = R.A0(0, q), wb = R.A0(1, q);
+    if (R.live(q)) {                     // (always, but for a run-time width: wave-uniform)
+      const int i0 = 8 * q + 4 * h;
+      const float (&x)[4] = X.x[q];
+      if (i0 < X.width()) store_x(i0, x);
+      const float4 wa = R.A0(0, q), wb = R.A0(1, q);
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      h1[0] = MFMA32(comp4(wa, t), x[t], h1[0]);
-      h1[1] = MFMA32(comp4(wb, t), x[t], h1[1]);
+      for (int t = 0; t < 4; ++t) {
+        h1[0] = MFMA32(comp4(wa, t), x[t], h1[0]);
+        h1[1] = MFMA32(comp4(wb, t), x[t], h1[1]);
+      }
     }
   }
 #pragma unroll
@@ -341,17 +468,26 @@ __device__ __forceinline__ void mfma_forward(const WT& R, const float* __restric
 // ---------------------------------------------------------------- act on MFMA: grid (ceil(n / 32), 2), one wavefront per 32 rows
 template <int O, int A, bool ACTOR>
 __device__ __forceinline__ void act_net_mfma(NET_ARGS, const float* __restrict__ logstd, const float* __restrict__ obs,
-                                             const float* __restrict__ noise, int n, float* value_out, float* action_out, float* logp_out) {
+                                             const float* __restrict__ noise, int n, float* value_out, float* action_out, float* logp_out,
+                                             int ow = O) {
   constexpr int NOUT = ACTOR ? A : 1;
   const int l = threadIdx.x, c = l & 31, h = l >> 5, row = blockIdx.x * 32 + c;
   const bool on = row < n;
   const int r = on ? row : n - 1;
-  NetRegs<O, NOUT, false> R;
-  R.load(w0, b0, w1, b1, wh, bh, c, h);
   f32x16 h1[2], h2[2], dh;
-  ObsRow<O> X;
-  X.load(obs + (size_t)r * O, h);
-  mfma_forward<O, NOUT>(R, b0, b1, bh, X, h, h1, h2, dh, [](int, const float (&)[4]) {}, [](int, f32x16 (&)[2]) {});
+  if constexpr (O != 0) {
+    NetRegs<O, NOUT, false> R;
+    R.load(w0, b0, w1, b1, wh, bh, c, h);
+    ObsRow<O> X;
+    X.load(obs + (size_t)r * O, h);
+    mfma_forward<O, NOUT>(R, b0, b1, bh, X, h, h1, h2, dh, [](int, const float (&)[4]) {}, [](int, f32x16 (&)[2]) {});
+  } else {                               // O = 0: rows of ow words, a run-time value
+    NetRegsW<NOUT> R;
+    R.load(w0, b0, w1, b1, wh, bh, c, h, ow);
+    ObsRowW X;
+    X.load(obs + (size_t)r * ow, h, ow);
+    mfma_forward<0, NOUT>(R, b0, b1, bh, X, h, h1, h2, dh, [](int, const float (&)[4]) {}, [](int, f32x16 (&)[2]) {});
+  }
   if constexpr (!ACTOR) {
     if (on && h == 0) value_out[row] = dh[0];
   } else {
@@ -381,6 +517,15 @@ policy_act_mfma_kernel(CRITIC_ARGS, ACTOR_ARGS, const float* __restrict__ obs, c
   if (blockIdx.y == 0) act_net_mfma<OC, A, false>(cw0, cb0, cw1, cb1, cwh, cbh, nullptr, cobs, noise, n, value_out, action_out, logp_out);
   else act_net_mfma<O, A, true>(aw0, ab0, aw1, ab1, awh, abh, logstd, obs, noise, n, value_out, action_out, logp_out);
 }
+// the same at run-time widths: ow the actor's, ocw the critic's (the symmetric policy: ocw = ow, cobs = obs).  At the cap NetRegsW
+// holds 128 + 64 + 32 weight registers and the row 64.
+template <int A>
+__global__ void __launch_bounds__(64)
+policy_act_w_kernel(CRITIC_ARGS, ACTOR_ARGS, const float* __restrict__ obs, const float* __restrict__ cobs, const float* __restrict__ noise, int n,
+                    float* value_out, float* action_out, float* logp_out, int ow, int ocw) {
+  if (blockIdx.y == 0) act_net_mfma<0, A, false>(cw0, cb0, cw1, cb1, cwh, cbh, nullptr, cobs, noise, n, value_out, action_out, logp_out, ocw);
+  else act_net_mfma<0, A, true>(aw0, ab0, aw1, ab1, awh, abh, logstd, obs, noise, n, value_out, action_out, logp_out, ow);
+}
 
 // ---------------------------------------------------------------- stage 1 on MFMA: grid (ceil(m / 128), 2), workgroups of four wavefronts,
 // one net per workgroup with its operand image in LDS (NetLds), one 32-row tile per wavefront (= one row of partials per 32 samples)
@@ -388,9 +533,10 @@ policy_act_mfma_kernel(CRITIC_ARGS, ACTOR_ARGS, const float* __restrict__ obs, c
 // rows: the [n][O] rollout rows this net reads
 template <int O, int A, bool ACTOR, bool WX>
 __device__ __forceinline__ void grad_net_mfma(NET_ARGS, const float* __restrict__ logstd, const float* __restrict__ rows, const solorl_ppo_batch& B, float* xt0, float* xt1,
-                                              float* xt2, float* g1, float* g2, float* gh, float* partials, float4* image) {
+                                              float* xt2, float* g1, float* g2, float* gh, float* partials, float4* image, int ow = O) {
   constexpr int NOUT = ACTOR ? A : 1;
-  using NR = NetLds<O, NOUT>;
+  using NR = LdsOf<O, NOUT>;                  // O = 0: rows of ow words, a run-time value
+  const int w = O != 0 ? O : ow;
   const int l = threadIdx.x & 63, wave = threadIdx.x >> 6, c = l & 31, h = l >> 5, m = B.m;
   // the tile's row: its index through the permutation, then its observation and its scalars -- issued BEFORE the image is filled, so that
   // the two dependent memory round trips run under the fill instead of after it
@@ -404,8 +550,8 @@ __device__ __forceinline__ void grad_net_mfma(NET_ARGS, const float* __restrict_
   const bool st = on;
 #endif
   const long long s = B.perm[*B.offset + r];
-  ObsRow<O> X;
-  X.load(rows + (size_t)s * O, h);
+  RowOf<O> X;
+  if constexpr (O != 0) X.load(rows + (size_t)s * O, h); else X.load(rows + (size_t)s * w, h, w);
   const float sc_ret = B.ret[s], sc_vp = B.vpred[s], sc_adv = B.adv[s], sc_olp = B.old_logp[s];
   float sc_act[ACTOR ? 16 : 1] = {};           // the row's actions, in the head's D layout
   if constexpr (ACTOR) {
@@ -418,17 +564,18 @@ __device__ __forceinline__ void grad_net_mfma(NET_ARGS, const float* __restrict_
   // fill: entry e by wavefront e mod 4, all loads of a wavefront in flight together
   {
     float4 v[(NR::NE + 3) / 4];
+    const int ne = NR::count(w);            // (NR::NE but for a run-time width, where NE is the cap's)
 #pragma unroll
 #ifdef SOLO_S1_NOFILL          // dev experiment: the image without its global loads
     for (int i = 0; i < (NR::NE + 3) / 4; ++i) v[i] = make_float4(0.01f * c, 0.02f, -0.01f * h, 0.03f);
 #else
-    for (int i = 0; i < (NR::NE + 3) / 4; ++i) { const int e = 4 * i + wave; if (e < NR::NE) v[i] = NR::entry(e, w0, b0, w1, b1, wh, bh, c, h); }
+    for (int i = 0; i < (NR::NE + 3) / 4; ++i) { const int e = 4 * i + wave; if (e < ne) v[i] = NR::entry(e, w0, b0, w1, b1, wh, bh, c, h, w); }
 #endif
 #pragma unroll
-    for (int i = 0; i < (NR::NE + 3) / 4; ++i) { const int e = 4 * i + wave; if (e < NR::NE) image[e * 64 + l] = v[i]; }
+    for (int i = 0; i < (NR::NE + 3) / 4; ++i) { const int e = 4 * i + wave; if (e < ne) image[e * 64 + l] = v[i]; }
   }
   __syncthreads();
-  const NR R{image + l};
+  const NR R = NR::at(image + l, w);
   if (tile0 >= m) return;
   const float inv_m = 1.0f / (float)m;
   float loss_acc = 0.f, gls_acc[ACTOR ? 16 : 1] = {};
@@ -447,7 +594,7 @@ __device__ __forceinline__ void grad_net_mfma(NET_ARGS, const float* __restrict_
         [&](int i0, const float (&x)[4]) {
           if (WX && st) {
 #pragma unroll
-            for (int t = 0; t < 4; ++t) if (i0 + t < O) xt0[(unsigned)((tile * O + i0 + t) * 32 + c)] = x[t];
+            for (int t = 0; t < 4; ++t) if (i0 + t < w) xt0[(unsigned)((tile * w + i0 + t) * 32 + c)] = x[t];
           }
         },
         [&](int layer, f32x16 (&a)[2]) { store_units(layer == 1 ? xt1 : xt2, a); });
@@ -567,6 +714,21 @@ ppo_grad_stage1_mfma_kernel(CRITIC_ARGS, ACTOR_ARGS, const solorl_ppo_batch B, c
   if (blockIdx.y == 0) grad_net_mfma<OC, A, false, true>(cw0, cb0, cw1, cb1, cwh, cbh, nullptr, cobs, B, cxt0, W.c_xt1, W.c_xt2, W.c_g1, W.c_g2, W.c_gh, W.partials, stage1_image);
   else grad_net_mfma<O, A, true, OC != O>(aw0, ab0, aw1, ab1, awh, abh, logstd, B.obs, B, W.xt0, W.a_xt1, W.a_xt2, W.a_g1, W.a_g2, W.a_gh, W.partials, stage1_image);
 }
+// the same at run-time widths; the dynamic LDS of a launch is stage1_w_lds_bytes of ITS widths (46 KB at 8 inputs, 76 KB at the cap: two
+// workgroups per CU at every width).  Whether the actor half writes xt0 is a wave-uniform choice between two instances of it.
+inline int stage1_w_lds_bytes(int ow, int ocw, int A) {
+  const int a = 40 + 2 * ((A + 7) / 8) + 2 * ((ow + 7) / 8), c = 40 + 2 + 2 * ((ocw + 7) / 8);       // NetLdsW<A>::count(ow), NetLdsW<1>::count(ocw)
+  return (a > c ? a : c) * 64 * 16;
+}
+template <int A>
+__global__ void __launch_bounds__(256, 2)
+ppo_grad_stage1_w_kernel(CRITIC_ARGS, ACTOR_ARGS, const solorl_ppo_batch B, const solorl_ppo_stage1 W, const float* __restrict__ cobs, float* cxt0, int ow, int ocw) {
+  extern __shared__ float4 stage1_image[];
+  static_assert(NetLdsW<A>::E_A0 == 40 + 2 * ((A + 7) / 8) && NetLdsW<1>::E_A0 == 42, "stage1_w_lds_bytes counts these entries");
+  if (blockIdx.y == 0) grad_net_mfma<0, A, false, true>(cw0, cb0, cw1, cb1, cwh, cbh, nullptr, cobs, B, cxt0, W.c_xt1, W.c_xt2, W.c_g1, W.c_g2, W.c_gh, W.partials, stage1_image, ocw);
+  else if (ow != ocw) grad_net_mfma<0, A, true, true>(aw0, ab0, aw1, ab1, awh, abh, logstd, B.obs, B, W.xt0, W.a_xt1, W.a_xt2, W.a_g1, W.a_g2, W.a_gh, W.partials, stage1_image, ow);
+  else grad_net_mfma<0, A, true, false>(aw0, ab0, aw1, ab1, awh, abh, logstd, B.obs, B, W.xt0, W.a_xt1, W.a_xt2, W.a_g1, W.a_g2, W.a_gh, W.partials, stage1_image, ow);
+}
 
 // ---------------------------------------------------------------- stage 2 on MFMA: d W = G . X^T with the ROW index as K
 // One wavefront per (layer, chunk of rows) computes ALL 32 x 32 tiles of the layer's product (2 x 3 for a hidden layer: 64 units x
@@ -682,6 +844,10 @@ __device__ __forceinline__ void stage2_tiles(const LayerDesc& L, int m, int r0, 
   }
 }
 
+// WIDE: the instance with the four-input-tile case compiled in (a first layer of 97 .. 128 inputs: the width-generic family, the only
+// callers that pass the shape check with one).  Shapes of at most three input tiles launch the instance without it, whose code is
+// what it was before the case existed: the case adds two accumulator tiles and a third of the operand ring to the kernel's registers.
+template <bool WIDE>
 __global__ void __launch_bounds__(64) ppo_grad_stage2_mfma_kernel(const Stage2Args S) {
   LayerDesc L = S.L[0];                  // (wave-uniform selects: a dynamic index into the argument struct would be served from scratch)
 #pragma unroll
@@ -691,6 +857,7 @@ __global__ void __launch_bounds__(64) ppo_grad_stage2_mfma_kernel(const Stage2Ar
   const int r0 = chunk * L.mchunk, r1 = min(r0 + L.mchunk, S.m);
   float* out = S.scratch + L.sbase + (size_t)chunk * L.U * L.K1;
   if (ntm == 2) {
+    if (WIDE && ntn == 4) { if constexpr (WIDE) stage2_tiles<2, 4>(L, S.m, r0, r1, out); } else
     if (ntn == 3) stage2_tiles<2, 3>(L, S.m, r0, r1, out); else if (ntn == 2) stage2_tiles<2, 2>(L, S.m, r0, r1, out); else stage2_tiles<2, 1>(L, S.m, r0, r1, out);
   } else {
     if (ntn == 3) stage2_tiles<1, 3>(L, S.m, r0, r1, out); else if (ntn == 2) stage2_tiles<1, 2>(L, S.m, r0, r1, out); else stage2_tiles<1, 1>(L, S.m, r0, r1, out);
@@ -738,6 +905,16 @@ template <int O, int OC, int A> struct AdamDims {
   static constexpr int j(int k) { return k - base(seg(k)); }
   static constexpr int GROUP = 3, NGROUPS = (SLOTS + GROUP - 1) / GROUP, AHEAD = 2;     // update phase: groups of three slots, two groups in flight ahead of the
                                                                                         // one being updated (128 registers at 1024 threads; ONE group ahead: a memory round trip per group, 12 us)
+  template <int S> static __device__ __forceinline__ unsigned size(const AdamArgs&) { constexpr unsigned v = n(S); return v; }      // elements of tensor S
+};
+// The width-generic family: templated on A alone.  Tensors 0 and 6 (64 OC and 64 O elements) get the slots of the cap, 8 each, and
+// their sizes come from the argument struct at STATIC indices; a slot past a tensor's end is predicated off like the tail of a partly
+// filled one and adds fmaf(0, 0, ss) = ss to the norm.  Thread tid still owns element tid + 1024 j of every tensor, tensors in order:
+// the norm is the templated kernel's sum term for term.
+template <int A> struct AdamDimsW : AdamDims<WMAX, WMAX, A> {
+  template <int S> static __device__ __forceinline__ unsigned size(const AdamArgs& K) {
+    if constexpr (S == 0 || S == 6) return (unsigned)K.seg[S].n; else { constexpr unsigned v = AdamDims<WMAX, WMAX, A>::n(S); return v; }
+  }
 };
 template <typename D> __device__ __forceinline__ void clip_adam_body(const AdamArgs& K) {
   __shared__ float red[16];
@@ -745,13 +922,15 @@ template <typename D> __device__ __forceinline__ void clip_adam_body(const AdamA
   const unsigned tid = threadIdx.x;        // (unsigned element offsets: scalar base + 32-bit vector offset addressing, no 64-bit address registers)
   float g[D::SLOTS], ss = 0.f;
   unrolled<D::SLOTS>([&](auto kc) {
-    constexpr int k = decltype(kc)::value, s = D::seg(k), jj = D::j(k), nn = D::n(s);      // (constexpr variables: forced constant evaluation)
+    constexpr int k = decltype(kc)::value, s = D::seg(k), jj = D::j(k);      // (constexpr variables: forced constant evaluation)
+    const unsigned nn = D::template size<s>(K);                              // (a constant but for the two run-time tensors of AdamDimsW)
     const unsigned i = tid + 1024u * jj;
-    g[k] = K.seg[s].g[min(i, (unsigned)(nn - 1))];          // (clamped and UNCONDITIONAL: all loads are issued here ...
+    g[k] = K.seg[s].g[min(i, nn - 1u)];          // (clamped and UNCONDITIONAL: all loads are issued here ...
   });
   asm volatile("" ::: "memory");
   unrolled<D::SLOTS>([&](auto kc) {
-    constexpr int k = decltype(kc)::value, s = D::seg(k), jj = D::j(k), nn = D::n(s);
+    constexpr int k = decltype(kc)::value, s = D::seg(k), jj = D::j(k);
+    const unsigned nn = D::template size<s>(K);
     asm volatile("" : "+v"(g[k]));            //  ... and pinned here: left alone the compiler sinks each load into the branch of its select
     g[k] = tid + 1024u * jj < nn ? g[k] * K.gscale : 0.f;     //  and waits for it there, one memory round trip per partly filled slot: 12 us)
   });                                         // gscale: 1 / world after a SUMMED gradient all-reduce (the mean's scale, fused)
@@ -762,9 +941,10 @@ template <typename D> __device__ __forceinline__ void clip_adam_body(const AdamA
     unrolled<D::GROUP>([&](auto qc) {
       constexpr int q = decltype(qc)::value, k = k0 + q;
       if constexpr (k < D::SLOTS) {
-        constexpr int s = D::seg(k), jj = D::j(k), nn = D::n(s);
+        constexpr int s = D::seg(k), jj = D::j(k);
+        const unsigned nn = D::template size<s>(K);
         const unsigned i = tid + 1024u * jj;
-        const unsigned ic = min(i, (unsigned)(nn - 1));
+        const unsigned ic = min(i, nn - 1u);
         r.p[q] = K.seg[s].p[ic]; r.m[q] = K.m[(unsigned)K.seg[s].off + ic]; r.v[q] = K.v[(unsigned)K.seg[s].off + ic];
       }
     });
@@ -798,7 +978,8 @@ template <typename D> __device__ __forceinline__ void clip_adam_body(const AdamA
     unrolled<D::GROUP>([&](auto qc) {
       constexpr int q = decltype(qc)::value, k = k0 + q;
       if constexpr (k < D::SLOTS) {
-        constexpr int s = D::seg(k), jj = D::j(k), nn = D::n(s);
+        constexpr int s = D::seg(k), jj = D::j(k);
+        const unsigned nn = D::template size<s>(K);
         const unsigned i = tid + 1024u * jj;
         if (i < nn) {
           float gg = g[k] * coef;
@@ -817,6 +998,8 @@ template <typename D> __device__ __forceinline__ void clip_adam_body(const AdamA
 }
 template <int O, int OC, int A>
 __global__ void __launch_bounds__(1024) ppo_clip_adam_kernel(const AdamArgs K) { clip_adam_body<AdamDims<O, OC, A>>(K); }
+template <int A>
+__global__ void __launch_bounds__(1024) ppo_clip_adam_w_kernel(const AdamArgs K) { clip_adam_body<AdamDimsW<A>>(K); }
 
 // (actor width, critic width, action width).  Symmetric, OC = O: the observation widths of zero or one history level (14 + 2 n
 // (+ 4 pointGoal), x 1 or x 2) at action widths n = 8 / 12, and the zero-history widths with the three velocity-command words of
@@ -849,7 +1032,7 @@ template <typename F> int dispatch_dims(int O, int OC, int A, F&& f) {
 inline int critic_width(const solorl_policy_params* p) { return p->critic_obs_dim != 0 ? p->critic_obs_dim : p->obs_dim; }
 // "<entry point>: <what>", as rows_check_args (row_batch.hpp) reports
 int fail_in(const char* fn, int code, const char* what) {
-  char msg[192];
+  char msg[384];
   std::snprintf(msg, sizeof(msg), "%s: %s", fn, what);
   return solorl_fail_(code, msg);
 }
@@ -857,9 +1040,7 @@ int fail_in(const char* fn, int code, const char* what) {
 // every policy entry point: the parameters, the shape (stage 2's kernel is not reached through dispatch_dims and computes only the tile
 // counts it instantiates), then the device -- so an unsupported shape is refused on a machine without a GPU too
 // critic: 0 = an entry point of the symmetric policy (refuses a critic width), 1 = one of the asymmetric policy (needs one), 2 = either
-int check_policy(const solorl_policy_params* p, int device_id, int critic = 0) {
-  if (!p) return solorl_fail_(SOLORL_ERR_INVALID, "null policy parameters");
-  if (p->hidden != H) return solorl_fail_(SOLORL_ERR_INVALID, "policy kernels are built for hidden size 64");
+int check_policy_pointers(const solorl_policy_params* p) {
   const void* ptrs[] = {p->critic_w0, p->critic_b0, p->critic_w1, p->critic_b1, p->critic_w2, p->critic_b2, p->actor_w0, p->actor_b0,
                         p->actor_w1, p->actor_b1, p->mean_w, p->mean_b, p->logstd};
   for (const void* q : ptrs) if (!q) return solorl_fail_(SOLORL_ERR_INVALID, "null policy parameter pointer");
@@ -867,14 +1048,40 @@ int check_policy(const solorl_policy_params* p, int device_id, int critic = 0) {
   // boundary (torch allocations do; an offset view passed by another C-ABI caller would fault on the GPU instead)
   const void* vec[] = {p->critic_w1, p->actor_w1, p->critic_w2, p->mean_w, critic_width(p) % 4 == 0 ? p->critic_w0 : nullptr, p->obs_dim % 4 == 0 ? p->actor_w0 : nullptr};
   for (const void* q : vec) if (reinterpret_cast<uintptr_t>(q) & 15u) return solorl_fail_(SOLORL_ERR_INVALID, "policy weight matrices must be 16-byte aligned (rows are read as float4)");
-  if (p->critic_obs_dim != 0 && critic == 0) return fail_critic_width();
-  if (p->critic_obs_dim == 0 && critic == 1) return fail_dims();
-  // (the actor's width is written critic_obs_dim = 0, never as a critic width of its own: those instances leave the actor's xt0 unwritten)
-  if (p->critic_obs_dim == p->obs_dim || !dims_supported(p->obs_dim, critic_width(p), p->act_dim)) return fail_dims();
+  return 0;
+}
+int use_device(int device_id) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return solorl_fail_(SOLORL_ERR_NODEVICE, "no HIP device available (no CPU fallback)");
   if (device_id < 0 || device_id >= ndev) return solorl_fail_(SOLORL_ERR_NODEVICE, "device_id out of range");
   if (hipSetDevice(device_id) != hipSuccess) return solorl_fail_(SOLORL_ERR_HIP, "hipSetDevice");
+  return 0;
+}
+int check_policy(const solorl_policy_params* p, int device_id, int critic = 0) {
+  if (!p) return solorl_fail_(SOLORL_ERR_INVALID, "null policy parameters");
+  if (p->hidden != H) return solorl_fail_(SOLORL_ERR_INVALID, "policy kernels are built for hidden size 64");
+  if (int rc = check_policy_pointers(p)) return rc;
+  if (p->critic_obs_dim != 0 && critic == 0) return fail_critic_width();
+  if (p->critic_obs_dim == 0 && critic == 1) return fail_dims();
+  // (the actor's width is written critic_obs_dim = 0, never as a critic width of its own: those instances leave the actor's xt0 unwritten)
+  if (p->critic_obs_dim == p->obs_dim || !dims_supported(p->obs_dim, critic_width(p), p->act_dim)) return fail_dims();
+  return use_device(device_id);
+}
+
+// The width-generic family's check, WITHOUT the device: its entry points check every argument first and look the device up last.
+// has_critic_arrays: the caller gave the critic's arrays (< 0: the entry point takes none)
+#define SOLO_STR_(x) #x
+#define SOLO_STR(x) SOLO_STR_(x)
+int check_policy_w(const char* fn, const solorl_policy_params* p, int has_critic_arrays) {
+  if (!p) return fail_in(fn, SOLORL_ERR_INVALID, "null policy parameters");
+  const int O = p->obs_dim, OC = p->critic_obs_dim, A = p->act_dim;
+  if (p->hidden != H || (A != 8 && A != 12) || O < 1 || O > WMAX || OC < 0 || OC > WMAX || OC == O)
+    return fail_in(fn, SOLORL_ERR_INVALID, "the width-generic policy kernels take hidden = 64, act_dim 8 or 12, 1 <= obs_dim <= " SOLO_STR(SOLORL_POLICY_MAX_WIDTH)
+                   " and critic_obs_dim = 0 (the critic reads the actor's rows) or 1 .. " SOLO_STR(SOLORL_POLICY_MAX_WIDTH) " other than obs_dim "
+                   "(SOLORL_POLICY_MAX_WIDTH = " SOLO_STR(SOLORL_POLICY_MAX_WIDTH) "); use the PyTorch path for other shapes");
+  if (int rc = check_policy_pointers(p)) return rc;
+  if (has_critic_arrays == 1 && OC == 0) return fail_in(fn, SOLORL_ERR_INVALID, "the critic's arrays are given but critic_obs_dim is 0: a symmetric policy passes NULL");
+  if (has_critic_arrays == 0 && OC != 0) return fail_in(fn, SOLORL_ERR_INVALID, "critic_obs_dim is set but the critic's arrays are NULL");
   return 0;
 }
 
@@ -910,28 +1117,38 @@ int grad_stage2_launch(const solorl_policy_params* p, const solorl_ppo_stage1* w
   }
   T.partials = work->partials; T.nwaves = (m + 31) / 32; T.A = A; T.logstd = p->logstd; T.logstd_grad = out->logstd;
   T.loss_sums = out->loss_sums; T.logstd_sum = out->logstd_sum; T.entropy_coef = out->entropy_coef;
-  hipLaunchKernelGGL(ppo_grad_stage2_mfma_kernel, dim3(S.nwaves), dim3(64), 0, (hipStream_t)stream, S);
+  if (O > 96 || OC > 96) hipLaunchKernelGGL(ppo_grad_stage2_mfma_kernel<true>, dim3(S.nwaves), dim3(64), 0, (hipStream_t)stream, S);
+  else hipLaunchKernelGGL(ppo_grad_stage2_mfma_kernel<false>, dim3(S.nwaves), dim3(64), 0, (hipStream_t)stream, S);
   hipLaunchKernelGGL(ppo_grad_stage3_kernel, dim3((S.total + 15) / 16 + 3 + A), dim3(256), 0, (hipStream_t)stream, T);
   return hipGetLastError() == hipSuccess ? 0 : solorl_fail_(SOLORL_ERR_HIP, "ppo_grad_stage2/3 launch");
 }
-int grad_stage2_check(const solorl_ppo_stage1* work, int m, const solorl_ppo_grads* out) {
-  if (!work || !out || m < 1) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage2: null argument or m < 1");
+int grad_stage2_check(const solorl_ppo_stage1* work, int m, const solorl_ppo_grads* out, const char* fn = "solorl_ppo_grad_stage2") {
+  if (!work || !out || m < 1) return fail_in(fn, SOLORL_ERR_INVALID, "null argument or m < 1");
   const void* ptrs[] = {out->critic_w0, out->critic_b0, out->critic_w1, out->critic_b1, out->critic_w2, out->critic_b2, out->actor_w0,
                         out->actor_b0, out->actor_w1, out->actor_b1, out->mean_w, out->mean_b, out->logstd, out->loss_sums, out->logstd_sum,
                         out->scratch, work->xt0, work->partials};
-  for (const void* q : ptrs) if (!q) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_grad_stage2: null array");
+  for (const void* q : ptrs) if (!q) return fail_in(fn, SOLORL_ERR_INVALID, "null array");
   return 0;
 }
 
 // a row array of width w is read as float4 where w is a multiple of 4
 bool rows_misaligned(const void* rows, int w) { return w % 4 == 0 && (reinterpret_cast<uintptr_t>(rows) & 15u); }
 
-// act of both forms, behind check_policy: cobs = the critic's rows [n][critic_width(p)] (obs for the symmetric policy)
-int policy_act_launch(const char* fn, const solorl_policy_params* p, const float* obs, const float* cobs, const float* noise, int n, float* value_out,
-                      float* action_out, float* logp_out, void* stream) {
+// the one family on A alone
+template <typename F> int dispatch_act_dim(int A, F&& f) { return A == 8 ? f(std::integral_constant<int, 8>()) : f(std::integral_constant<int, 12>()); }
+
+// act of both forms and both families: cobs = the critic's rows [n][critic_width(p)] (obs for the symmetric policy)
+int policy_act_check(const char* fn, const solorl_policy_params* p, const float* obs, const float* cobs, int n, float* value_out, float* action_out,
+                     float* logp_out) {
   if (!obs || !cobs || !value_out || !action_out || !logp_out || n < 1) return fail_in(fn, SOLORL_ERR_INVALID, "null array or n < 1");
   if (rows_misaligned(obs, p->obs_dim) || rows_misaligned(cobs, critic_width(p)))
     return fail_in(fn, SOLORL_ERR_INVALID, "rows of a width that is a multiple of 4 must be 16-byte aligned (they are read as float4)");
+  return 0;
+}
+// behind check_policy
+int policy_act_launch(const char* fn, const solorl_policy_params* p, const float* obs, const float* cobs, const float* noise, int n, float* value_out,
+                      float* action_out, float* logp_out, void* stream) {
+  if (int rc = policy_act_check(fn, p, obs, cobs, n, value_out, action_out, logp_out)) return rc;
   const solorl_policy_params P = *p;
   return dispatch_dims(P.obs_dim, critic_width(p), P.act_dim, [&](auto oc, auto cc, auto ac) {
     constexpr int O = decltype(oc)::value, OC = decltype(cc)::value, A = decltype(ac)::value;
@@ -941,10 +1158,10 @@ int policy_act_launch(const char* fn, const solorl_policy_params* p, const float
   });
 }
 
-// stage 1 of both forms, behind check_policy: cobs = the critic's rollout rows, cxt0 = the critic's gathered rows; the symmetric policy's
+// stage 1 of both forms and both families: cobs = the critic's rollout rows, cxt0 = the critic's gathered rows; the symmetric policy's
 // are batch->obs and work->xt0 (null with a null batch / work, which is refused first)
-int grad_stage1_launch(const char* fn, const solorl_policy_params* p, const solorl_ppo_batch* batch, const float* cobs, const solorl_ppo_stage1* work,
-                       float* cxt0, int device_id, void* stream) {
+int grad_stage1_check(const char* fn, const solorl_policy_params* p, const solorl_ppo_batch* batch, const float* cobs, const solorl_ppo_stage1* work,
+                      float* cxt0) {
   if (!batch || !work || batch->m < 1) return fail_in(fn, SOLORL_ERR_INVALID, "null argument or m < 1");
   if (batch->m % 32 != 0) return fail_in(fn, SOLORL_ERR_INVALID, "m must be a multiple of 32 rows (the work arrays are written in tiles of 32)");
   const int OC = critic_width(p), widest = OC > p->obs_dim ? (OC > H ? OC : H) : (p->obs_dim > H ? p->obs_dim : H);
@@ -955,6 +1172,13 @@ int grad_stage1_launch(const char* fn, const solorl_policy_params* p, const solo
   for (const void* q : ptrs) if (!q) return fail_in(fn, SOLORL_ERR_INVALID, "null array");
   if (rows_misaligned(batch->obs, p->obs_dim) || rows_misaligned(cobs, OC))
     return fail_in(fn, SOLORL_ERR_INVALID, "rows of a width that is a multiple of 4 must be 16-byte aligned (they are read as float4)");
+  return 0;
+}
+// behind check_policy
+int grad_stage1_launch(const char* fn, const solorl_policy_params* p, const solorl_ppo_batch* batch, const float* cobs, const solorl_ppo_stage1* work,
+                       float* cxt0, int device_id, void* stream) {
+  if (int rc = grad_stage1_check(fn, p, batch, cobs, work, cxt0)) return rc;
+  const int OC = critic_width(p);
   const solorl_policy_params P = *p;
   const solorl_ppo_batch B = *batch;
   const solorl_ppo_stage1 W = *work;
@@ -966,6 +1190,43 @@ int grad_stage1_launch(const char* fn, const solorl_policy_params* p, const solo
                        cobs, cxt0);
     return hipGetLastError() == hipSuccess ? 0 : fail_in(fn, SOLORL_ERR_HIP, "ppo_grad_stage1_mfma_kernel launch");
   });
+}
+
+// ---- the width-generic family: every argument is checked first (check_policy_w and the checks above), the device is looked up last
+// the kernel's dynamic LDS limit goes to the cap's 76 KB once per (action width, device)
+template <int A> int stage1_w_raise_lds_limit(int device_id) {
+  static std::mutex mu;
+  static bool raised[64] = {};
+  if (device_id < 0 || device_id >= 64) return solorl_fail_(SOLORL_ERR_NODEVICE, "ppo_grad_stage1_w_kernel: device_id beyond the 64 the library tracks");
+  std::lock_guard<std::mutex> lock(mu);
+  if (raised[device_id]) return 0;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_grad_stage1_w_kernel<A>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          stage1_w_lds_bytes(WMAX, WMAX, A)) != hipSuccess)
+    return solorl_fail_(SOLORL_ERR_HIP, "ppo_grad_stage1_w_kernel: cannot raise the dynamic LDS limit");
+  raised[device_id] = true;
+  return 0;
+}
+
+// the 13 tensors of clip + Adam in the order of solorl_policy_params' pointers
+int clip_adam_args(const char* fn, const solorl_policy_params* p, const solorl_ppo_grads* g, const solorl_adam_state* a, AdamArgs& K) {
+  if (!g || !a || !a->exp_avg || !a->exp_avg_sq || !a->step || !a->lr) return fail_in(fn, SOLORL_ERR_INVALID, "null argument");
+  const int O = p->obs_dim, A = p->act_dim, OC = critic_width(p);
+  const float* ps[13] = {p->critic_w0, p->critic_b0, p->critic_w1, p->critic_b1, p->critic_w2, p->critic_b2, p->actor_w0, p->actor_b0,
+                         p->actor_w1, p->actor_b1, p->mean_w, p->mean_b, p->logstd};
+  const float* gs[13] = {g->critic_w0, g->critic_b0, g->critic_w1, g->critic_b1, g->critic_w2, g->critic_b2, g->actor_w0, g->actor_b0,
+                         g->actor_w1, g->actor_b1, g->mean_w, g->mean_b, g->logstd};
+  const int ns[13] = {H * OC, H, H * H, H, H, 1, H * O, H, H * H, H, A * H, A, A};
+  int off = 0;
+  for (int i = 0; i < 13; ++i) {
+    if (!gs[i]) return fail_in(fn, SOLORL_ERR_INVALID, "null gradient pointer");
+    K.seg[i] = {const_cast<float*>(ps[i]), gs[i], ns[i], off};
+    off += ns[i];
+  }
+  K.total = off; K.m = a->exp_avg; K.v = a->exp_avg_sq; K.step = a->step; K.lr = a->lr;
+  K.b1 = a->beta1; K.b2 = a->beta2; K.eps = a->eps; K.wd = a->weight_decay; K.max_norm = a->max_grad_norm;
+  K.gscale = a->grad_scale > 0.f ? a->grad_scale : 1.0f;
+  K.offset = reinterpret_cast<long long*>(a->offset); K.inc = a->offset_increment;
+  return 0;
 }
 
 }  // namespace
@@ -1021,27 +1282,70 @@ int solorl_ppo_grad_stage2_critic(const solorl_policy_params* p, const solorl_pp
 
 int solorl_ppo_clip_adam(const solorl_policy_params* p, const solorl_ppo_grads* g, const solorl_adam_state* a, int device_id, void* stream) {
   if (int rc = check_policy(p, device_id, 2)) return rc;
-  if (!g || !a || !a->exp_avg || !a->exp_avg_sq || !a->step || !a->lr) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_clip_adam: null argument");
-  const int O = p->obs_dim, A = p->act_dim, OC = critic_width(p);
-  const float* ps[13] = {p->critic_w0, p->critic_b0, p->critic_w1, p->critic_b1, p->critic_w2, p->critic_b2, p->actor_w0, p->actor_b0,
-                         p->actor_w1, p->actor_b1, p->mean_w, p->mean_b, p->logstd};
-  const float* gs[13] = {g->critic_w0, g->critic_b0, g->critic_w1, g->critic_b1, g->critic_w2, g->critic_b2, g->actor_w0, g->actor_b0,
-                         g->actor_w1, g->actor_b1, g->mean_w, g->mean_b, g->logstd};
-  const int ns[13] = {H * OC, H, H * H, H, H, 1, H * O, H, H * H, H, A * H, A, A};
   AdamArgs K;
-  int off = 0;
-  for (int i = 0; i < 13; ++i) {
-    if (!gs[i]) return solorl_fail_(SOLORL_ERR_INVALID, "solorl_ppo_clip_adam: null gradient pointer");
-    K.seg[i] = {const_cast<float*>(ps[i]), gs[i], ns[i], off};
-    off += ns[i];
-  }
-  K.total = off; K.m = a->exp_avg; K.v = a->exp_avg_sq; K.step = a->step; K.lr = a->lr;
-  K.b1 = a->beta1; K.b2 = a->beta2; K.eps = a->eps; K.wd = a->weight_decay; K.max_norm = a->max_grad_norm;
-  K.gscale = a->grad_scale > 0.f ? a->grad_scale : 1.0f;
-  K.offset = reinterpret_cast<long long*>(a->offset); K.inc = a->offset_increment;
-  return dispatch_dims(O, OC, A, [&](auto oc, auto cc, auto ac) {
+  if (int rc = clip_adam_args("solorl_ppo_clip_adam", p, g, a, K)) return rc;
+  return dispatch_dims(p->obs_dim, critic_width(p), p->act_dim, [&](auto oc, auto cc, auto ac) {
     hipLaunchKernelGGL((ppo_clip_adam_kernel<decltype(oc)::value, decltype(cc)::value, decltype(ac)::value>), dim3(1), dim3(1024), 0, (hipStream_t)stream, K);
     return hipGetLastError() == hipSuccess ? 0 : solorl_fail_(SOLORL_ERR_HIP, "ppo_clip_adam_kernel launch");
+  });
+}
+
+// ---- the width-generic family (include/solorl.h): critic_obs / critic_xt0 NULL = the symmetric policy, whose critic reads obs / xt0
+int solorl_policy_act_w(const solorl_policy_params* p, const float* obs, const float* critic_obs, const float* noise, int n, float* value_out,
+                        float* action_out, float* logp_out, int device_id, void* stream) {
+  const char* fn = "solorl_policy_act_w";
+  if (int rc = check_policy_w(fn, p, critic_obs != nullptr)) return rc;
+  const float* cobs = critic_obs ? critic_obs : obs;
+  if (int rc = policy_act_check(fn, p, obs, cobs, n, value_out, action_out, logp_out)) return rc;
+  if (int rc = use_device(device_id)) return rc;
+  const solorl_policy_params P = *p;
+  return dispatch_act_dim(P.act_dim, [&](auto ac) {
+    hipLaunchKernelGGL((policy_act_w_kernel<decltype(ac)::value>), dim3((n + 31) / 32, 2), dim3(64), 0, (hipStream_t)stream, CRITIC_PASS, ACTOR_PASS, obs, cobs,
+                       noise, n, value_out, action_out, logp_out, P.obs_dim, critic_width(p));
+    return hipGetLastError() == hipSuccess ? 0 : fail_in(fn, SOLORL_ERR_HIP, "policy_act_w_kernel launch");
+  });
+}
+
+int solorl_ppo_grad_stage1_w(const solorl_policy_params* p, const solorl_ppo_batch* batch, const float* critic_obs, const solorl_ppo_stage1* work,
+                             float* critic_xt0, int device_id, void* stream) {
+  const char* fn = "solorl_ppo_grad_stage1_w";
+  if ((critic_obs != nullptr) != (critic_xt0 != nullptr)) return fail_in(fn, SOLORL_ERR_INVALID, "critic_obs and critic_xt0 go together: both or neither");
+  if (int rc = check_policy_w(fn, p, critic_obs != nullptr)) return rc;
+  const float* cobs = critic_obs ? critic_obs : (batch ? batch->obs : nullptr);
+  float* cxt0 = critic_xt0 ? critic_xt0 : (work ? work->xt0 : nullptr);
+  if (int rc = grad_stage1_check(fn, p, batch, cobs, work, cxt0)) return rc;
+  if (int rc = use_device(device_id)) return rc;
+  const solorl_policy_params P = *p;
+  const solorl_ppo_batch B = *batch;
+  const solorl_ppo_stage1 W = *work;
+  return dispatch_act_dim(P.act_dim, [&](auto ac) {
+    constexpr int A = decltype(ac)::value;
+    if (int rc = stage1_w_raise_lds_limit<A>(device_id)) return rc;
+    hipLaunchKernelGGL((ppo_grad_stage1_w_kernel<A>), dim3((B.m + 127) / 128, 2), dim3(256), stage1_w_lds_bytes(P.obs_dim, critic_width(p), A), (hipStream_t)stream,
+                       CRITIC_PASS, ACTOR_PASS, B, W, cobs, cxt0, P.obs_dim, critic_width(p));
+    return hipGetLastError() == hipSuccess ? 0 : fail_in(fn, SOLORL_ERR_HIP, "ppo_grad_stage1_w_kernel launch");
+  });
+}
+
+int solorl_ppo_grad_stage2_w(const solorl_policy_params* p, const solorl_ppo_stage1* work, const float* critic_xt0, int m, const solorl_ppo_grads* out,
+                             int device_id, void* stream) {
+  const char* fn = "solorl_ppo_grad_stage2_w";
+  if (int rc = check_policy_w(fn, p, critic_xt0 != nullptr)) return rc;
+  if (int rc = grad_stage2_check(work, m, out, fn)) return rc;
+  if (m % 64 != 0) return fail_in(fn, SOLORL_ERR_INVALID, "m must be a multiple of 64 rows");
+  if (int rc = use_device(device_id)) return rc;
+  return grad_stage2_launch(p, work, critic_xt0 ? critic_xt0 : work->xt0, m, out, stream);
+}
+
+int solorl_ppo_clip_adam_w(const solorl_policy_params* p, const solorl_ppo_grads* g, const solorl_adam_state* a, int device_id, void* stream) {
+  const char* fn = "solorl_ppo_clip_adam_w";
+  if (int rc = check_policy_w(fn, p, -1)) return rc;
+  AdamArgs K;
+  if (int rc = clip_adam_args(fn, p, g, a, K)) return rc;
+  if (int rc = use_device(device_id)) return rc;
+  return dispatch_act_dim(p->act_dim, [&](auto ac) {
+    hipLaunchKernelGGL((ppo_clip_adam_w_kernel<decltype(ac)::value>), dim3(1), dim3(1024), 0, (hipStream_t)stream, K);
+    return hipGetLastError() == hipSuccess ? 0 : fail_in(fn, SOLORL_ERR_HIP, "ppo_clip_adam_w_kernel launch");
   });
 }
 

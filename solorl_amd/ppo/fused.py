@@ -75,6 +75,56 @@ def policy_kernels_supported(actor_critic):
     return h == 64 and (o, oc or o, a) in _SUPPORTED and p.is_cuda and p.dtype == torch.float32
 
 
+def _policy_shape(actor_critic):
+    """(obs, critic width or None for a symmetric policy, act, hidden) of the reference's MLP; None for another module"""
+    b = actor_critic.base
+    try:
+        o, h, a = b.features[0].in_features, b.features[0].out_features, actor_critic.pi_dist.mean.out_features
+        oc = getattr(actor_critic, "critic_obs_dim", None)
+        if oc is not None and b.critic[0].in_features != oc:
+            return None
+    except AttributeError:
+        return None
+    return o, oc, a, h
+
+
+def generic_shape_supported(o, oc, a, h=64):
+    """The width-generic family (csrc/solorl_ppo.hip, the _w entry points): hidden 64, 8 or 12 actions, any observation width and any
+    critic width (None: symmetric) up to SOLORL_POLICY_MAX_WIDTH; a critic width that equals obs is written None, as for the templates"""
+    W = _native.POLICY_MAX_WIDTH
+    return h == 64 and a in (8, 12) and 1 <= o <= W and (oc is None or (1 <= oc <= W and oc != o))
+
+
+def policy_kernels_generic_supported(actor_critic):
+    """policy_kernels_supported for the width-generic family"""
+    shape = _policy_shape(actor_critic)
+    p = next(actor_critic.parameters())
+    return shape is not None and generic_shape_supported(*shape) and p.is_cuda and p.dtype == torch.float32
+
+
+TEMPLATED, GENERIC = "templated", "generic"
+
+
+def shape_kernel_family(o, oc, a, h=64, generic=0):
+    """The kernel family for a policy shape (oc None: symmetric): TEMPLATED (one instance per shape, _SUPPORTED), GENERIC (the _w entry
+    points) or None (the PyTorch path).  ``generic`` is the value of the switch SOLORL_POLICY_GENERIC (graphs.py reads it):
+    0 the templated family or none, today's behaviour; 1 the generic family for the shapes the templated one does not build;
+    2 the generic family for every shape it takes (A/B runs, the bitwise tests)."""
+    templated = h == 64 and oc != o and (o, oc or o, a) in _SUPPORTED
+    if generic and generic_shape_supported(o, oc, a, h) and (generic >= 2 or not templated):
+        return GENERIC
+    return TEMPLATED if templated else None
+
+
+def policy_kernel_family(actor_critic, generic=0):
+    """shape_kernel_family of a policy module whose parameters the kernels can read (CUDA, float32); None otherwise"""
+    shape = _policy_shape(actor_critic)
+    p = next(actor_critic.parameters())
+    if shape is None or not (p.is_cuda and p.dtype == torch.float32):
+        return None
+    return shape_kernel_family(*shape, generic=generic)
+
+
 def _named_parameters(actor_critic):
     """The MLP's 13 parameters under the member names of solorl_policy_params / solorl_ppo_grads"""
     b, d = actor_critic.base, actor_critic.pi_dist
@@ -84,9 +134,10 @@ def _named_parameters(actor_critic):
             "logstd": d.logstd}
 
 
-def policy_params(actor_critic):
+def policy_params(actor_critic, family=TEMPLATED):
     """solorl_policy_params over the module's own parameter storage (PyTorch layout is the kernels' layout: no copies).
-    The pointers stay valid as long as the parameters are updated in place (optimizers do)."""
+    The pointers stay valid as long as the parameters are updated in place (optimizers do).  ``family``: the entry points the calls
+    below use with this table (policy_kernel_family)."""
     b, d = actor_critic.base, actor_critic.pi_dist
     P = _native.PolicyParams()
     P.obs_dim, P.hidden, P.act_dim = b.features[0].in_features, b.features[0].out_features, d.mean.out_features
@@ -96,6 +147,8 @@ def policy_params(actor_critic):
         assert t.is_contiguous() and t.dtype == torch.float32 and t.is_cuda
         setattr(P, k, t.data_ptr())
     P._tensors = named            # keeps the storages alive and lets check_params() notice a re-allocated parameter
+    assert family in (TEMPLATED, GENERIC)
+    P.family = family
     return P
 
 
@@ -108,10 +161,15 @@ def check_params(P):
             raise RuntimeError("policy parameter %s moved since solorl_policy_params was built; rebuild it (and any HIP graph)" % k)
 
 
-def _call(params, name, args, critic):
+def _call(params, name, args, critic, both_forms=False):
     """The entry point `name` of the symmetric policy on `args` (what follows the parameters), or, where params.critic_obs_dim is set,
-    `name`_critic with the critic's arrays put in: critic = {position in that argument list: tensor}"""
-    if params.critic_obs_dim:
+    `name`_critic with the critic's arrays put in: critic = {position in that argument list: tensor}.  The generic family: `name`_w,
+    which takes the critic's arrays in the same places, null for a symmetric policy"""
+    if params.family == GENERIC:
+        name += "_w"
+        for i in sorted(critic):
+            args.insert(i, C.c_void_p(critic[i].data_ptr() if params.critic_obs_dim else None))
+    elif params.critic_obs_dim and not both_forms:         # (both_forms: one templated entry point serves either policy)
         name += "_critic"
         for i in sorted(critic):
             args.insert(i, C.c_void_p(critic[i].data_ptr()))
@@ -144,12 +202,12 @@ class MiniBatchGrad:
     loss.backward() (agents/ppo/ppo.py:46-74) in a different summation order."""
     SLICE = 64                        # mini-batch rows must fill whole wavefronts
 
-    def __init__(self, actor_critic, storage, mini_batch, clip, value_coef, entropy_coef, clipped_value, perm, offset, adv):
+    def __init__(self, actor_critic, storage, mini_batch, clip, value_coef, entropy_coef, clipped_value, perm, offset, adv, family=TEMPLATED):
         n, m = storage.num_samples, mini_batch
         assert m % self.SLICE == 0, "mini-batch must be a multiple of %d rows" % self.SLICE
         dev = storage.device
         self.ac, self.m = actor_critic, m
-        self.P = policy_params(actor_critic)
+        self.P = policy_params(actor_critic, family)
         O, A, H = self.P.obs_dim, self.P.act_dim, 64
         OC = self.OC = self.P.critic_obs_dim          # 0: symmetric
         self.A = A
@@ -231,7 +289,7 @@ class ClipAdam:
 
     def __call__(self):
         with torch.cuda.device(self.dev):
-            _native.check(_native.lib().solorl_ppo_clip_adam(C.byref(self.P), C.byref(self.G), C.byref(self.S), self.dev.index or 0, _native.stream(self.dev)))
+            _call(self.P, "solorl_ppo_clip_adam", [C.byref(self.G), C.byref(self.S), self.dev.index or 0, _native.stream(self.dev)], {}, both_forms=True)
 
     def zero_state(self):
         self.exp_avg.zero_(); self.exp_avg_sq.zero_(); self.step.zero_()

@@ -22,13 +22,24 @@ import torch
 import torch.nn as nn
 
 from . import dist as D
-from .fused import ClipAdam, MiniBatchGrad, fused_ppo_loss, policy_act, policy_kernels_supported, policy_params
+from .fused import TEMPLATED, ClipAdam, MiniBatchGrad, fused_ppo_loss, policy_act, policy_kernel_family, policy_params
 from .ppo import PPO
 
 
 def _kernels_enabled():
     """SOLORL_PPO_KERNELS=0 keeps the rollout's act and the mini-batch step on their PyTorch paths (A/B runs)."""
     return os.environ.get("SOLORL_PPO_KERNELS", "1") != "0"
+
+
+def _generic_switch():
+    """SOLORL_POLICY_GENERIC: 0 or unset, the policy kernels built per shape or the PyTorch path; 1, the width-generic kernels for the
+    shapes the per-shape family does not build; 2, the width-generic kernels for every shape they take (A/B runs)."""
+    return int(os.environ.get("SOLORL_POLICY_GENERIC", "0") or 0)
+
+
+def _policy_family(actor_critic):
+    """The kernel family both loops run this policy on (fused.policy_kernel_family), None = the PyTorch path"""
+    return policy_kernel_family(actor_critic, _generic_switch()) if _kernels_enabled() else None
 
 
 def capture_kwargs():
@@ -119,18 +130,20 @@ class GraphedRollout:
         # a storage made with bootstrap_timeouts: every step launch writes its timeout flags into the storage's row by itself (the info
         # block it is handed points there) -- no launch more, in any branch
         tout = getattr(st, "timeouts", None)
-        fused = _kernels_enabled() and policy_kernels_supported(self.ac)
+        family = _policy_family(self.ac)
+        fused = family is not None
         if fused:                            # one launch for the whole of Policy.act (csrc/solorl_ppo.hip)
-            self._pp = policy_params(self.ac)
+            self._pp = policy_params(self.ac, family)
         # the normal draws of all T steps and masks = 1 - done of all T steps are one launch each per rollout, not per step
         noise = torch.randn_like(st.actions) if fused else None
         done = torch.empty(self.T, st.num_agents, dtype=torch.uint8, device=st.device)
         # ONE launch per rollout step where the engine supports it (solorl_step_act: each wavefront of the step kernel evaluates the policy
         # on the observations it has just produced, in the time it would otherwise idle until the slowest wavefront ends); the first
         # step's action still needs its own policy launch.  SOLORL_STEP_ACT=0 keeps the two-launch form (A/B runs).
-        self.step_act = bool(fused and os.environ.get("SOLORL_STEP_ACT", "1") != "0" and hasattr(self.envs, "step_act_supported")
+        # (the step kernel's policy tail is built per shape: the width-generic family always acts in a launch of its own)
+        self.step_act = bool(family == TEMPLATED and os.environ.get("SOLORL_STEP_ACT", "1") != "0" and hasattr(self.envs, "step_act_supported")
                              and self.envs.step_act_supported(self._pp))
-        if fused and self.chunk > 0 and hasattr(self.envs, "rollout_supported") and self.envs.rollout_supported(self._pp):
+        if family == TEMPLATED and self.chunk > 0 and hasattr(self.envs, "rollout_supported") and self.envs.rollout_supported(self._pp):
             # row 0's action from its own policy launch, then windows of K steps straight into storage rows; every window but the last
             # also evaluates the policy after its last step (row t0 + K: the next window's first action)
             policy_act(self._pp, st.obs[0], noise[0], st.value_preds[0], st.actions[0], st.action_log_probs[0])
@@ -201,7 +214,8 @@ class GraphedPPO(PPO):
                          l2_coef=l2_coef, max_grad_norm=max_grad_norm, use_clipped_value_loss=use_clipped_value_loss)
         self.fused_loss = fused_loss
         # hand-written mini-batch kernel (csrc/solorl_ppo.hip) where it is built for this policy's shape; otherwise autograd
-        self.fused_mlp = fused_mlp and _kernels_enabled() and policy_kernels_supported(actor_critic)
+        self._family = _policy_family(actor_critic) if fused_mlp else None
+        self.fused_mlp = self._family is not None
         dev = next(actor_critic.parameters()).device
         # (fused: one multi-tensor launch per optimizer step instead of a dozen -- a captured mini-batch step is ~100 launches of a
         # few microseconds each, so launches are what it costs)
@@ -229,7 +243,7 @@ class GraphedPPO(PPO):
         self._mb = None
         if self.fused_mlp and m % MiniBatchGrad.SLICE == 0:
             self._mb = MiniBatchGrad(self.actor_critic, storage, m, clip, self.value_loss_coef, self.entropy_coef, self.use_clipped_value_loss,
-                                     self._perm, self._off, self._adv)
+                                     self._perm, self._off, self._adv, family=self._family)
 
         self._ca = None
         if self._mb is not None:             # norm clip + Adam + cursor in one launch; lr stays the optimizer's device tensor

@@ -168,6 +168,10 @@ def get_ppo_args(argv=None):
     p.add_argument("--bootstrap-timeouts", action="store_true", default=False,
                    help="time-limit bootstrapping: a step the time limit cut off bootstraps its return from the value of the observation its "
                         "action was taken from, instead of reading as a fall (default: off, the reference's returns)")
+    p.add_argument("--generic-policy-kernels", action="store_true", default=False,
+                   help="run a policy shape the per-shape policy kernels are not built for (e.g. --commands with a history level: 79 wide) on "
+                        "the width-generic kernels instead of the PyTorch path: any observation and critic width up to 128 "
+                        "(sets SOLORL_POLICY_GENERIC=1; default: off)")
     p.add_argument("--num-steps", type=int, default=None, help="rollout length (default: episode_length, train_ppo.py:62-63)")
     return p.parse_args(argv)
 
@@ -182,6 +186,8 @@ def main(argv=None):
     if args.env_name != "base":
         raise SystemExit("--env-name %s needs the absent `scripts.Controller` (SURVEY.md section 0.6); only 'base' is provided" % args.env_name)
     args.cuda = not args.no_cuda
+    if args.generic_policy_kernels:
+        os.environ["SOLORL_POLICY_GENERIC"] = "1"       # read by ppo/graphs.py when the loops are built
     if not args.cuda:
         raise SystemExit("the rollout engine is GPU-only (no CPU fallback)")
     if args.num_steps is None:
