@@ -961,6 +961,49 @@ int solorl_ppo_grad_stage2_w(const solorl_policy_params* p, const solorl_ppo_sta
                              const solorl_ppo_grads* out, int device_id, void* stream);
 int solorl_ppo_clip_adam_w(const solorl_policy_params* p, const solorl_ppo_grads* g, const solorl_adam_state* a, int device_id, void* stream);
 
+/* PPO KL control on the device: the approximate KL divergence and the clip fraction of every mini-batch step, a learning rate that
+ * follows the KL (rsl_rl's "adaptive" schedule) and an early stop of the update (stable-baselines' target_kl), without a launch more
+ * and without a host round trip -- capturable like the steps they stand in for.  No struct above changes (SOLORL_ABI_VERSION stays).
+ *
+ * solorl_ppo_grad_stage1_kl is stage 1 with one more output: diag [m / 32][2], per tile of 32 rows the sums over its rows of
+ *   k3 = (ratio - 1) - (logp - old_logp)      Schulman's estimator of KL(old || new) (stable-baselines' approx_kl), >= 0 per row
+ *   1 - inside                                 1 for a row whose ratio left [1 - clip, 1 + clip]
+ * Every other output has the bits the plain entry point writes.  Stage 2 follows unchanged.
+ *
+ * solorl_ppo_clip_adam_kl is clip + Adam with the controller in front.  It adds diag up in a fixed order, kl = sum k3 / m and
+ * cf = sum (1 - inside) / m, and then, in f32 and in this order:
+ *   1. target_kl > 0 and kl > 1.5 target_kl                     the stopped flag state[4] is set, and stays set until the caller clears it
+ *   2. not stopped and desired_kl > 0:
+ *        kl > 2 desired_kl                                      lr = max(lr_min, lr / lr_factor)
+ *        else kl < desired_kl / 2 and kl > 0                    lr = min(lr_max, lr * lr_factor)
+ *      and lr is written back to *lr and used by this step
+ *   3. stopped: no parameter, moment or step count is written; the cursor a->offset still advances
+ * A kl that is not finite decides nothing: no stop, no change.  With desired_kl <= 0 and target_kl <= 0 and a clear flag the
+ * parameters, moments, step count and cursor are bit for bit solorl_ppo_clip_adam's.
+ *   state [8]   += (1, applied ? 1 : 0, kl, cf) in [0..3]; [4] the stopped flag; [5..7] = this step's kl, cf and lr.  The caller zeroes it
+ *               at the start of an update.
+ *   log         optional [log_capacity][4]: row state[0] (the steps seen before this one), while below log_capacity, receives
+ *               (kl, cf, the lr used, 1 if the step was applied else 0)
+ *   lr          must be a->lr; m the mini-batch's rows (= a->offset_increment where a->offset is given)
+ * One pair of entry points serves the three kernel families: generic != 0 picks the width-generic kernels (the _w entry points'
+ * shapes), 0 the kernels built per shape; critic_obs / critic_xt0 go with p->critic_obs_dim as in the _w entry points (NULL for a
+ * symmetric policy).  Refused with SOLORL_ERR_INVALID, before the device is looked up and with a message that starts with the
+ * entry point's name: what the plain entry points refuse; a null diag, state or lr; lr other than a->lr; m that is not the
+ * batch's; lr_factor <= 1; lr_min > lr_max. */
+typedef struct solorl_kl_control {
+  const float* diag;   /* [m / 32][2], written by solorl_ppo_grad_stage1_kl */
+  int m;
+  float desired_kl, lr_factor, lr_min, lr_max, target_kl;
+  float* lr;
+  float* state;
+  float* log;
+  int log_capacity;
+} solorl_kl_control;
+int solorl_ppo_grad_stage1_kl(const solorl_policy_params* p, const solorl_ppo_batch* batch, const float* critic_obs,
+                              const solorl_ppo_stage1* work, float* critic_xt0, float* diag, int generic, int device_id, void* stream);
+int solorl_ppo_clip_adam_kl(const solorl_policy_params* p, const solorl_ppo_grads* g, const solorl_adam_state* a,
+                            const solorl_kl_control* k, int generic, int device_id, void* stream);
+
 const char* solorl_last_error(void);
 const char* solorl_version(void);
 int solorl_abi_version(void);   /* SOLORL_ABI_VERSION of the built library */

@@ -23,7 +23,8 @@ SYMBOLS = ("solorl_default_config", "solorl_create", "solorl_destroy", "solorl_d
            "solorl_shape_reward", "solorl_obs_noise", "solorl_actuate", "solorl_commands", "solorl_shape_reward_cmd",
            "solorl_terminate", "solorl_randomize_reset", "solorl_restart_history", "solorl_critic_obs",
            "solorl_policy_act_critic", "solorl_ppo_grad_stage1_critic", "solorl_ppo_grad_stage2_critic", "solorl_ppo_grad_count2", "solorl_ppo_scratch_count2",
-           "solorl_policy_act_w", "solorl_ppo_grad_stage1_w", "solorl_ppo_grad_stage2_w", "solorl_ppo_clip_adam_w")
+           "solorl_policy_act_w", "solorl_ppo_grad_stage1_w", "solorl_ppo_grad_stage2_w", "solorl_ppo_clip_adam_w",
+           "solorl_ppo_grad_stage1_kl", "solorl_ppo_clip_adam_kl")
 
 POLICY_MAX_WIDTH = 128                      # SOLORL_POLICY_MAX_WIDTH
 
@@ -49,6 +50,12 @@ class AdamState(C.Structure):               # solorl_adam_state
     _fields_ = [("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("step", C.c_void_p), ("lr", C.c_void_p), ("offset", C.c_void_p),
                 ("offset_increment", C.c_int64), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
                 ("max_grad_norm", C.c_float), ("grad_scale", C.c_float)]
+
+
+class KlControl(C.Structure):               # solorl_kl_control
+    _fields_ = [("diag", C.c_void_p), ("m", C.c_int), ("desired_kl", C.c_float), ("lr_factor", C.c_float), ("lr_min", C.c_float),
+                ("lr_max", C.c_float), ("target_kl", C.c_float), ("lr", C.c_void_p), ("state", C.c_void_p), ("log", C.c_void_p),
+                ("log_capacity", C.c_int)]
 
 
 class PpoStage1(C.Structure):               # solorl_ppo_stage1
@@ -170,6 +177,11 @@ def lib():
         L.solorl_ppo_grad_stage1_w.argtypes = L.solorl_ppo_grad_stage1_critic.argtypes
         L.solorl_ppo_grad_stage2_w.argtypes = L.solorl_ppo_grad_stage2_critic.argtypes
         L.solorl_ppo_clip_adam_w.argtypes = L.solorl_ppo_clip_adam.argtypes
+        # KL control: one pair for the three kernel families (generic: the _w kernels; the critic's arrays NULL for a symmetric policy)
+        L.solorl_ppo_grad_stage1_kl.argtypes = [C.POINTER(PolicyParams), C.POINTER(PpoBatch), C.c_void_p, C.POINTER(PpoStage1), C.c_void_p, C.c_void_p,
+                                                C.c_int, C.c_int, C.c_void_p]
+        L.solorl_ppo_clip_adam_kl.argtypes = [C.POINTER(PolicyParams), C.POINTER(PpoGrads), C.POINTER(AdamState), C.POINTER(KlControl), C.c_int, C.c_int,
+                                              C.c_void_p]
         # running normalisation: stats / ret / scratch are device pointers to doubles
         L.solorl_norm_scratch_count.argtypes = [C.c_int, C.c_int, C.c_int]
         L.solorl_normalize_obs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double,

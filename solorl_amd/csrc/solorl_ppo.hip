@@ -29,6 +29,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <mutex>
+#include <string>
 #include <type_traits>
 #include <utility>
 
@@ -531,9 +532,13 @@ policy_act_w_kernel(CRITIC_ARGS, ACTOR_ARGS, const float* __restrict__ obs, cons
 // one net per workgroup with its operand image in LDS (NetLds), one 32-row tile per wavefront (= one row of partials per 32 samples)
 // WX: this net writes its gathered input rows to xt0 (the critic always; the actor where its rows are not the critic's: OC != O);
 // rows: the [n][O] rollout rows this net reads
-template <int O, int A, bool ACTOR, bool WX>
+// DIAG (the actor half of the _kl kernels): the wavefront also sums, over its rows, Schulman's k3 estimate of KL(old || new),
+// (ratio - 1) - log ratio, and the clipped samples, 1 - inside, into diag[tile][0..1] -- the two numbers the controller in
+// clip_adam_body<D, true> acts on.  DIAG = false compiles none of it: the kernels without it are what they were.
+template <int O, int A, bool ACTOR, bool WX, bool DIAG = false>
 __device__ __forceinline__ void grad_net_mfma(NET_ARGS, const float* __restrict__ logstd, const float* __restrict__ rows, const solorl_ppo_batch& B, float* xt0, float* xt1,
-                                              float* xt2, float* g1, float* g2, float* gh, float* partials, float4* image, int ow = O) {
+                                              float* xt2, float* g1, float* g2, float* gh, float* partials, float4* image, int ow = O, float* diag = nullptr) {
+  static_assert(ACTOR || !DIAG, "the critic half has no diagnostics");
   constexpr int NOUT = ACTOR ? A : 1;
   using NR = LdsOf<O, NOUT>;                  // O = 0: rows of ow words, a run-time value
   const int w = O != 0 ? O : ow;
@@ -579,6 +584,7 @@ __device__ __forceinline__ void grad_net_mfma(NET_ARGS, const float* __restrict_
   if (tile0 >= m) return;
   const float inv_m = 1.0f / (float)m;
   float loss_acc = 0.f, gls_acc[ACTOR ? 16 : 1] = {};
+  [[maybe_unused]] float kl_acc = 0.f, cf_acc = 0.f;        // DIAG: this lane's row (lane half 0), summed over the wavefront below
   const int rows_here = min(m - tile0, 32);
   {
     f32x16 h1[2], h2[2], dh;
@@ -646,6 +652,9 @@ __device__ __forceinline__ void grad_net_mfma(NET_ARGS, const float* __restrict_
         }
       }
       if (on && h == 0) loss_acc += -fminf(s1, s2);
+      if constexpr (DIAG) {
+        if (on && h == 0) { const float d = lp - sc_olp; kl_acc = (ratio - 1.0f) - d; cf_acc = 1.0f - inside; }
+      }
     }
     // back through the head, layer 2, layer 1: the same register-to-operand identity as forward
     f32x16 d2[2], d1[2];
@@ -701,6 +710,10 @@ __device__ __forceinline__ void grad_net_mfma(NET_ARGS, const float* __restrict_
         if (c == 0 && a < A) P_[3 + a] = sg;
       }
     }
+    if constexpr (DIAG) {
+      const float sk = wave_sum(kl_acc), sc = wave_sum(cf_acc);
+      if (l == 0) { diag[2 * tile] = sk; diag[2 * tile + 1] = sc; }       // tile < m / 32: the tiles past m have returned
+    }
   }
 }
 
@@ -713,6 +726,14 @@ ppo_grad_stage1_mfma_kernel(CRITIC_ARGS, ACTOR_ARGS, const solorl_ppo_batch B, c
   extern __shared__ float4 stage1_image[];         // stage1_lds_bytes<O, OC, A>() of dynamic LDS: 50-66 KB, two workgroups per CU
   if (blockIdx.y == 0) grad_net_mfma<OC, A, false, true>(cw0, cb0, cw1, cb1, cwh, cbh, nullptr, cobs, B, cxt0, W.c_xt1, W.c_xt2, W.c_g1, W.c_g2, W.c_gh, W.partials, stage1_image);
   else grad_net_mfma<O, A, true, OC != O>(aw0, ab0, aw1, ab1, awh, abh, logstd, B.obs, B, W.xt0, W.a_xt1, W.a_xt2, W.a_g1, W.a_g2, W.a_gh, W.partials, stage1_image);
+}
+// stage 1 with diagnostics (solorl_ppo_grad_stage1_kl): the same launch, the actor half with DIAG
+template <int O, int OC, int A>
+__global__ void __launch_bounds__(256, 2)
+ppo_grad_stage1_kl_kernel(CRITIC_ARGS, ACTOR_ARGS, const solorl_ppo_batch B, const solorl_ppo_stage1 W, const float* __restrict__ cobs, float* cxt0, float* diag) {
+  extern __shared__ float4 stage1_image[];
+  if (blockIdx.y == 0) grad_net_mfma<OC, A, false, true>(cw0, cb0, cw1, cb1, cwh, cbh, nullptr, cobs, B, cxt0, W.c_xt1, W.c_xt2, W.c_g1, W.c_g2, W.c_gh, W.partials, stage1_image);
+  else grad_net_mfma<O, A, true, OC != O, true>(aw0, ab0, aw1, ab1, awh, abh, logstd, B.obs, B, W.xt0, W.a_xt1, W.a_xt2, W.a_g1, W.a_g2, W.a_gh, W.partials, stage1_image, O, diag);
 }
 // the same at run-time widths; the dynamic LDS of a launch is stage1_w_lds_bytes of ITS widths (46 KB at 8 inputs, 76 KB at the cap: two
 // workgroups per CU at every width).  Whether the actor half writes xt0 is a wave-uniform choice between two instances of it.
@@ -728,6 +749,14 @@ ppo_grad_stage1_w_kernel(CRITIC_ARGS, ACTOR_ARGS, const solorl_ppo_batch B, cons
   if (blockIdx.y == 0) grad_net_mfma<0, A, false, true>(cw0, cb0, cw1, cb1, cwh, cbh, nullptr, cobs, B, cxt0, W.c_xt1, W.c_xt2, W.c_g1, W.c_g2, W.c_gh, W.partials, stage1_image, ocw);
   else if (ow != ocw) grad_net_mfma<0, A, true, true>(aw0, ab0, aw1, ab1, awh, abh, logstd, B.obs, B, W.xt0, W.a_xt1, W.a_xt2, W.a_g1, W.a_g2, W.a_gh, W.partials, stage1_image, ow);
   else grad_net_mfma<0, A, true, false>(aw0, ab0, aw1, ab1, awh, abh, logstd, B.obs, B, W.xt0, W.a_xt1, W.a_xt2, W.a_g1, W.a_g2, W.a_gh, W.partials, stage1_image, ow);
+}
+template <int A>
+__global__ void __launch_bounds__(256, 2)
+ppo_grad_stage1_w_kl_kernel(CRITIC_ARGS, ACTOR_ARGS, const solorl_ppo_batch B, const solorl_ppo_stage1 W, const float* __restrict__ cobs, float* cxt0, int ow, int ocw, float* diag) {
+  extern __shared__ float4 stage1_image[];
+  if (blockIdx.y == 0) grad_net_mfma<0, A, false, true>(cw0, cb0, cw1, cb1, cwh, cbh, nullptr, cobs, B, cxt0, W.c_xt1, W.c_xt2, W.c_g1, W.c_g2, W.c_gh, W.partials, stage1_image, ocw);
+  else if (ow != ocw) grad_net_mfma<0, A, true, true, true>(aw0, ab0, aw1, ab1, awh, abh, logstd, B.obs, B, W.xt0, W.a_xt1, W.a_xt2, W.a_g1, W.a_g2, W.a_gh, W.partials, stage1_image, ow, diag);
+  else grad_net_mfma<0, A, true, false, true>(aw0, ab0, aw1, ab1, awh, abh, logstd, B.obs, B, W.xt0, W.a_xt1, W.a_xt2, W.a_g1, W.a_g2, W.a_gh, W.partials, stage1_image, ow, diag);
 }
 
 // ---------------------------------------------------------------- stage 2 on MFMA: d W = G . X^T with the ROW index as K
@@ -916,11 +945,53 @@ template <int A> struct AdamDimsW : AdamDims<WMAX, WMAX, A> {
     if constexpr (S == 0 || S == 6) return (unsigned)K.seg[S].n; else { constexpr unsigned v = AdamDims<WMAX, WMAX, A>::n(S); return v; }
   }
 };
-template <typename D> __device__ __forceinline__ void clip_adam_body(const AdamArgs& K) {
+// The KL controller of solorl_ppo_clip_adam_kl (include/solorl.h has the rule table): what stage 1 with DIAG left in diag [nw][2],
+// reduced here in a fixed order, decides in thread 0 whether this step is applied and at which learning rate.
+struct KlArgs { const float* diag; int nw; float m; float desired_kl, lr_factor, lr_min, lr_max, target_kl; float* lr; float* state; float* log; int log_capacity; };
+
+// the controller's LDS: the 16 wavefronts' two sums, then thread 0's verdict (applied or not, the learning rate) (a function of its own: only the KL kernels call it and have it)
+__device__ __forceinline__ float* kl_shared() { __shared__ float r[34]; return r; }
+
+// KL = false compiles none of the controller: the kernels without it are what they were.
+template <typename D, bool KL = false> __device__ __forceinline__ void clip_adam_body(const AdamArgs& K, const KlArgs* Q = nullptr) {
   __shared__ float red[16];
   __shared__ float coef_s, step_size_s, inv_sqrt_bc2_s;
   const unsigned tid = threadIdx.x;        // (unsigned element offsets: scalar base + 32-bit vector offset addressing, no 64-bit address registers)
   float g[D::SLOTS], ss = 0.f;
+  // KL: the controller runs FIRST and is done before a gradient is loaded.  Thread t adds rows t, t + 1024, ... of diag, then the
+  // wavefront, then -- behind a barrier of its own -- thread 0 the 16 wavefronts in order, and decides; its verdict waits in LDS.
+  // (Reduced beside the gradient norm, behind the norm's barrier, the controller's sums, its 14 scalar arguments and thread 0's
+  // arithmetic were live together with the gradients and the moments' loads in flight: the three widest instances, which fill the 128
+  // registers a lane of 1024 threads has without it, went 12 to 20 bytes into scratch.)
+  if constexpr (KL) {
+    float dk = 0.f, dc = 0.f;
+    for (unsigned r = tid; r < (unsigned)Q->nw; r += 1024u) { const float2 d = reinterpret_cast<const float2*>(Q->diag)[r]; dk += d.x; dc += d.y; }
+    dk = wave_sum(dk); dc = wave_sum(dc);
+    if ((tid & 63) == 0) { kl_shared()[tid >> 6] = dk; kl_shared()[16 + (tid >> 6)] = dc; }
+    __syncthreads();
+    if (tid == 0) {
+      float lr = *K.lr, s0 = 0.f, s1 = 0.f;
+      for (int w = 0; w < 16; ++w) { s0 += kl_shared()[w]; s1 += kl_shared()[16 + w]; }
+      const float kl = s0 / Q->m, cf = s1 / Q->m;
+      const bool finite = fabsf(kl) < __builtin_huge_valf();          // a NaN or an infinity decides nothing
+      float stopped = Q->state[4];
+      if (finite && Q->target_kl > 0.f && kl > 1.5f * Q->target_kl) stopped = 1.0f;
+      if (stopped == 0.f && Q->desired_kl > 0.f) {                     // rsl_rl's adaptive schedule
+        if (finite && kl > 2.0f * Q->desired_kl) lr = fmaxf(Q->lr_min, lr / Q->lr_factor);
+        else if (finite && kl < Q->desired_kl / 2.0f && kl > 0.f) lr = fminf(Q->lr_max, lr * Q->lr_factor);
+        *Q->lr = lr;                                                   // (nobody else reads it in this launch)
+      }
+      const float applied = stopped == 0.f ? 1.0f : 0.f, seen = Q->state[0];
+      if (Q->log && seen >= 0.f && seen < (float)Q->log_capacity) {
+        float* row = Q->log + 4 * (int)seen;
+        row[0] = kl; row[1] = cf; row[2] = lr; row[3] = applied;
+      }
+      Q->state[0] = seen + 1.0f; Q->state[1] += applied; Q->state[2] += kl; Q->state[3] += cf;
+      Q->state[4] = stopped; Q->state[5] = kl; Q->state[6] = cf; Q->state[7] = lr;
+      kl_shared()[32] = applied; kl_shared()[33] = lr;
+    }
+    asm volatile("" ::: "memory");
+  }
   unrolled<D::SLOTS>([&](auto kc) {
     constexpr int k = decltype(kc)::value, s = D::seg(k), jj = D::j(k);      // (constexpr variables: forced constant evaluation)
     const unsigned nn = D::template size<s>(K);                              // (a constant but for the two run-time tensors of AdamDimsW)
@@ -956,7 +1027,9 @@ template <typename D> __device__ __forceinline__ void clip_adam_body(const AdamA
   for (int k = 0; k < D::SLOTS; ++k) ss = fmaf(g[k], g[k], ss);
   ss = wave_sum(ss);
   if ((tid & 63) == 0) red[tid >> 6] = ss;
-  const float step = *K.step + 1.0f, lr = *K.lr;
+  const float step = *K.step + 1.0f;
+  float lr = 0.f;
+  if constexpr (!KL) lr = *K.lr;
   __syncthreads();
   if (tid == 0) {
     float t = 0.f;
@@ -964,10 +1037,14 @@ template <typename D> __device__ __forceinline__ void clip_adam_body(const AdamA
     coef_s = K.max_norm > 0.f ? fminf(1.0f, K.max_norm / (sqrtf(t) + 1e-6f)) : 1.0f;      // clip_coef clamped to 1
     // (one thread: two powf are ~300 instructions, and the whole launch is one CU's instruction issue: 16 wavefronts on 4 SIMDs)
     const float bc1 = 1.0f - powf(K.b1, step), bc2 = 1.0f - powf(K.b2, step);
+    if constexpr (KL) lr = kl_shared()[33];       // (this thread's own store)
     step_size_s = lr / bc1; inv_sqrt_bc2_s = 1.0f / sqrtf(bc2);
   }
   __syncthreads();
   const float coef = coef_s, step_size = step_size_s, inv_sqrt_bc2 = inv_sqrt_bc2_s;
+  if constexpr (KL) {          // a stopped step writes no parameter, no moment and no step count; the cursor still advances
+    if (kl_shared()[32] == 0.f) { if (tid == 0 && K.offset) *K.offset += K.inc; return; }
+  }
   unrolled<D::NGROUPS>([&](auto gc) {
     constexpr int gi = decltype(gc)::value, k0 = gi * D::GROUP;
     if constexpr (gi + D::AHEAD < D::NGROUPS) ring[(gi + D::AHEAD) % (D::AHEAD + 1)] = load_group(std::integral_constant<int, gi + D::AHEAD>{});
@@ -1000,6 +1077,10 @@ template <int O, int OC, int A>
 __global__ void __launch_bounds__(1024) ppo_clip_adam_kernel(const AdamArgs K) { clip_adam_body<AdamDims<O, OC, A>>(K); }
 template <int A>
 __global__ void __launch_bounds__(1024) ppo_clip_adam_w_kernel(const AdamArgs K) { clip_adam_body<AdamDimsW<A>>(K); }
+template <int O, int OC, int A>
+__global__ void __launch_bounds__(1024) ppo_clip_adam_kl_kernel(const AdamArgs K, const KlArgs Q) { clip_adam_body<AdamDims<O, OC, A>, true>(K, &Q); }
+template <int A>
+__global__ void __launch_bounds__(1024) ppo_clip_adam_w_kl_kernel(const AdamArgs K, const KlArgs Q) { clip_adam_body<AdamDimsW<A>, true>(K, &Q); }
 
 // (actor width, critic width, action width).  Symmetric, OC = O: the observation widths of zero or one history level (14 + 2 n
 // (+ 4 pointGoal), x 1 or x 2) at action widths n = 8 / 12, and the zero-history widths with the three velocity-command words of
@@ -1057,7 +1138,7 @@ int use_device(int device_id) {
   if (hipSetDevice(device_id) != hipSuccess) return solorl_fail_(SOLORL_ERR_HIP, "hipSetDevice");
   return 0;
 }
-int check_policy(const solorl_policy_params* p, int device_id, int critic = 0) {
+int check_policy_shape(const solorl_policy_params* p, int critic) {
   if (!p) return solorl_fail_(SOLORL_ERR_INVALID, "null policy parameters");
   if (p->hidden != H) return solorl_fail_(SOLORL_ERR_INVALID, "policy kernels are built for hidden size 64");
   if (int rc = check_policy_pointers(p)) return rc;
@@ -1065,6 +1146,10 @@ int check_policy(const solorl_policy_params* p, int device_id, int critic = 0) {
   if (p->critic_obs_dim == 0 && critic == 1) return fail_dims();
   // (the actor's width is written critic_obs_dim = 0, never as a critic width of its own: those instances leave the actor's xt0 unwritten)
   if (p->critic_obs_dim == p->obs_dim || !dims_supported(p->obs_dim, critic_width(p), p->act_dim)) return fail_dims();
+  return 0;
+}
+int check_policy(const solorl_policy_params* p, int device_id, int critic = 0) {
+  if (int rc = check_policy_shape(p, critic)) return rc;
   return use_device(device_id);
 }
 
@@ -1086,14 +1171,14 @@ int check_policy_w(const char* fn, const solorl_policy_params* p, int has_critic
 }
 
 // Stage 1 takes more than the 64 KB of dynamic LDS a kernel gets by default: the limit is raised once per (instantiation, device)
-template <int O, int OC, int A> int stage1_raise_lds_limit(int device_id) {
+template <int O, int OC, int A, bool DIAG = false> int stage1_raise_lds_limit(int device_id) {
   static std::mutex mu;
   static bool raised[64] = {};
   if (device_id < 0 || device_id >= 64) return solorl_fail_(SOLORL_ERR_NODEVICE, "ppo_grad_stage1_mfma_kernel: device_id beyond the 64 the library tracks");
   std::lock_guard<std::mutex> lock(mu);
   if (raised[device_id]) return 0;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_grad_stage1_mfma_kernel<O, OC, A>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          stage1_lds_bytes<O, OC, A>()) != hipSuccess)
+  const void* kernel = DIAG ? reinterpret_cast<const void*>(&ppo_grad_stage1_kl_kernel<O, OC, A>) : reinterpret_cast<const void*>(&ppo_grad_stage1_mfma_kernel<O, OC, A>);
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, stage1_lds_bytes<O, OC, A>()) != hipSuccess)
     return solorl_fail_(SOLORL_ERR_HIP, "ppo_grad_stage1_mfma_kernel: cannot raise the dynamic LDS limit");
   raised[device_id] = true;
   return 0;
@@ -1174,10 +1259,9 @@ int grad_stage1_check(const char* fn, const solorl_policy_params* p, const solor
     return fail_in(fn, SOLORL_ERR_INVALID, "rows of a width that is a multiple of 4 must be 16-byte aligned (they are read as float4)");
   return 0;
 }
-// behind check_policy
-int grad_stage1_launch(const char* fn, const solorl_policy_params* p, const solorl_ppo_batch* batch, const float* cobs, const solorl_ppo_stage1* work,
-                       float* cxt0, int device_id, void* stream) {
-  if (int rc = grad_stage1_check(fn, p, batch, cobs, work, cxt0)) return rc;
+// behind check_policy and grad_stage1_check; diag: the kernel with diagnostics (solorl_ppo_grad_stage1_kl)
+int grad_stage1_dispatch(const char* fn, const solorl_policy_params* p, const solorl_ppo_batch* batch, const float* cobs, const solorl_ppo_stage1* work,
+                         float* cxt0, float* diag, int device_id, void* stream) {
   const int OC = critic_width(p);
   const solorl_policy_params P = *p;
   const solorl_ppo_batch B = *batch;
@@ -1185,6 +1269,12 @@ int grad_stage1_launch(const char* fn, const solorl_policy_params* p, const solo
   return dispatch_dims(P.obs_dim, OC, P.act_dim, [&](auto oc, auto cc, auto ac) {
     constexpr int O = decltype(oc)::value, OC_ = decltype(cc)::value, A = decltype(ac)::value;
     constexpr int LDS = stage1_lds_bytes<O, OC_, A>();
+    if (diag) {
+      if (int rc = stage1_raise_lds_limit<O, OC_, A, true>(device_id)) return rc;
+      hipLaunchKernelGGL((ppo_grad_stage1_kl_kernel<O, OC_, A>), dim3((B.m + 127) / 128, 2), dim3(256), LDS, (hipStream_t)stream, CRITIC_PASS, ACTOR_PASS, B, W,
+                         cobs, cxt0, diag);
+      return hipGetLastError() == hipSuccess ? 0 : fail_in(fn, SOLORL_ERR_HIP, "ppo_grad_stage1_kl_kernel launch");
+    }
     if (int rc = stage1_raise_lds_limit<O, OC_, A>(device_id)) return rc;
     hipLaunchKernelGGL((ppo_grad_stage1_mfma_kernel<O, OC_, A>), dim3((B.m + 127) / 128, 2), dim3(256), LDS, (hipStream_t)stream, CRITIC_PASS, ACTOR_PASS, B, W,
                        cobs, cxt0);
@@ -1192,19 +1282,48 @@ int grad_stage1_launch(const char* fn, const solorl_policy_params* p, const solo
   });
 }
 
+// behind check_policy
+int grad_stage1_launch(const char* fn, const solorl_policy_params* p, const solorl_ppo_batch* batch, const float* cobs, const solorl_ppo_stage1* work,
+                       float* cxt0, int device_id, void* stream) {
+  if (int rc = grad_stage1_check(fn, p, batch, cobs, work, cxt0)) return rc;
+  return grad_stage1_dispatch(fn, p, batch, cobs, work, cxt0, nullptr, device_id, stream);
+}
+
 // ---- the width-generic family: every argument is checked first (check_policy_w and the checks above), the device is looked up last
 // the kernel's dynamic LDS limit goes to the cap's 76 KB once per (action width, device)
-template <int A> int stage1_w_raise_lds_limit(int device_id) {
+template <int A, bool DIAG = false> int stage1_w_raise_lds_limit(int device_id) {
   static std::mutex mu;
   static bool raised[64] = {};
   if (device_id < 0 || device_id >= 64) return solorl_fail_(SOLORL_ERR_NODEVICE, "ppo_grad_stage1_w_kernel: device_id beyond the 64 the library tracks");
   std::lock_guard<std::mutex> lock(mu);
   if (raised[device_id]) return 0;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_grad_stage1_w_kernel<A>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          stage1_w_lds_bytes(WMAX, WMAX, A)) != hipSuccess)
+  const void* kernel = DIAG ? reinterpret_cast<const void*>(&ppo_grad_stage1_w_kl_kernel<A>) : reinterpret_cast<const void*>(&ppo_grad_stage1_w_kernel<A>);
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, stage1_w_lds_bytes(WMAX, WMAX, A)) != hipSuccess)
     return solorl_fail_(SOLORL_ERR_HIP, "ppo_grad_stage1_w_kernel: cannot raise the dynamic LDS limit");
   raised[device_id] = true;
   return 0;
+}
+
+// behind check_policy_w, grad_stage1_check and use_device; diag as in grad_stage1_dispatch
+int grad_stage1_w_dispatch(const char* fn, const solorl_policy_params* p, const solorl_ppo_batch* batch, const float* cobs, const solorl_ppo_stage1* work,
+                           float* cxt0, float* diag, int device_id, void* stream) {
+  const solorl_policy_params P = *p;
+  const solorl_ppo_batch B = *batch;
+  const solorl_ppo_stage1 W = *work;
+  return dispatch_act_dim(P.act_dim, [&](auto ac) {
+    constexpr int A = decltype(ac)::value;
+    const int lds = stage1_w_lds_bytes(P.obs_dim, critic_width(p), A);
+    if (diag) {
+      if (int rc = stage1_w_raise_lds_limit<A, true>(device_id)) return rc;
+      hipLaunchKernelGGL((ppo_grad_stage1_w_kl_kernel<A>), dim3((B.m + 127) / 128, 2), dim3(256), lds, (hipStream_t)stream, CRITIC_PASS, ACTOR_PASS, B, W, cobs, cxt0,
+                         P.obs_dim, critic_width(p), diag);
+      return hipGetLastError() == hipSuccess ? 0 : fail_in(fn, SOLORL_ERR_HIP, "ppo_grad_stage1_w_kl_kernel launch");
+    }
+    if (int rc = stage1_w_raise_lds_limit<A>(device_id)) return rc;
+    hipLaunchKernelGGL((ppo_grad_stage1_w_kernel<A>), dim3((B.m + 127) / 128, 2), dim3(256), lds, (hipStream_t)stream, CRITIC_PASS, ACTOR_PASS, B, W, cobs, cxt0,
+                       P.obs_dim, critic_width(p));
+    return hipGetLastError() == hipSuccess ? 0 : fail_in(fn, SOLORL_ERR_HIP, "ppo_grad_stage1_w_kernel launch");
+  });
 }
 
 // the 13 tensors of clip + Adam in the order of solorl_policy_params' pointers
@@ -1226,6 +1345,25 @@ int clip_adam_args(const char* fn, const solorl_policy_params* p, const solorl_p
   K.b1 = a->beta1; K.b2 = a->beta2; K.eps = a->eps; K.wd = a->weight_decay; K.max_norm = a->max_grad_norm;
   K.gscale = a->grad_scale > 0.f ? a->grad_scale : 1.0f;
   K.offset = reinterpret_cast<long long*>(a->offset); K.inc = a->offset_increment;
+  return 0;
+}
+
+// ---- the _kl entry points: one pair for the three families.  Every refusal precedes the device lookup and starts with the entry point's name:
+// a message of the shared checks that does not is given it here
+int named(const char* fn, int rc) {
+  if (rc == 0) return 0;
+  char old[384];
+  std::snprintf(old, sizeof(old), "%s", solorl_last_error());
+  const size_t n = std::char_traits<char>::length(fn);
+  if (std::char_traits<char>::compare(old, fn, n) == 0 && old[n] == ':') return rc;
+  return fail_in(fn, rc, old);
+}
+// the policy table and the critic's arrays of either family, without the device: the arrays go with critic_obs_dim, as in the _w entry points
+int check_policy_kl(const char* fn, const solorl_policy_params* p, int has_critic_arrays, int generic) {
+  if (generic) return named(fn, check_policy_w(fn, p, has_critic_arrays));
+  if (int rc = named(fn, check_policy_shape(p, 2))) return rc;
+  if (has_critic_arrays == 1 && p->critic_obs_dim == 0) return fail_in(fn, SOLORL_ERR_INVALID, "the critic's arrays are given but critic_obs_dim is 0: a symmetric policy passes NULL");
+  if (has_critic_arrays == 0 && p->critic_obs_dim != 0) return fail_in(fn, SOLORL_ERR_INVALID, "critic_obs_dim is set but the critic's arrays are NULL");
   return 0;
 }
 
@@ -1315,16 +1453,7 @@ int solorl_ppo_grad_stage1_w(const solorl_policy_params* p, const solorl_ppo_bat
   float* cxt0 = critic_xt0 ? critic_xt0 : (work ? work->xt0 : nullptr);
   if (int rc = grad_stage1_check(fn, p, batch, cobs, work, cxt0)) return rc;
   if (int rc = use_device(device_id)) return rc;
-  const solorl_policy_params P = *p;
-  const solorl_ppo_batch B = *batch;
-  const solorl_ppo_stage1 W = *work;
-  return dispatch_act_dim(P.act_dim, [&](auto ac) {
-    constexpr int A = decltype(ac)::value;
-    if (int rc = stage1_w_raise_lds_limit<A>(device_id)) return rc;
-    hipLaunchKernelGGL((ppo_grad_stage1_w_kernel<A>), dim3((B.m + 127) / 128, 2), dim3(256), stage1_w_lds_bytes(P.obs_dim, critic_width(p), A), (hipStream_t)stream,
-                       CRITIC_PASS, ACTOR_PASS, B, W, cobs, cxt0, P.obs_dim, critic_width(p));
-    return hipGetLastError() == hipSuccess ? 0 : fail_in(fn, SOLORL_ERR_HIP, "ppo_grad_stage1_w_kernel launch");
-  });
+  return grad_stage1_w_dispatch(fn, p, batch, cobs, work, cxt0, nullptr, device_id, stream);
 }
 
 int solorl_ppo_grad_stage2_w(const solorl_policy_params* p, const solorl_ppo_stage1* work, const float* critic_xt0, int m, const solorl_ppo_grads* out,
@@ -1347,6 +1476,50 @@ int solorl_ppo_clip_adam_w(const solorl_policy_params* p, const solorl_ppo_grads
     hipLaunchKernelGGL((ppo_clip_adam_w_kernel<decltype(ac)::value>), dim3(1), dim3(1024), 0, (hipStream_t)stream, K);
     return hipGetLastError() == hipSuccess ? 0 : fail_in(fn, SOLORL_ERR_HIP, "ppo_clip_adam_w_kernel launch");
   });
+}
+
+// ---- PPO KL control (include/solorl.h): stage 1 with the per-tile KL and clip sums, clip + Adam with the controller on them
+int solorl_ppo_grad_stage1_kl(const solorl_policy_params* p, const solorl_ppo_batch* batch, const float* critic_obs, const solorl_ppo_stage1* work,
+                              float* critic_xt0, float* diag, int generic, int device_id, void* stream) {
+  const char* fn = "solorl_ppo_grad_stage1_kl";
+  if ((critic_obs != nullptr) != (critic_xt0 != nullptr)) return fail_in(fn, SOLORL_ERR_INVALID, "critic_obs and critic_xt0 go together: both or neither");
+  if (int rc = check_policy_kl(fn, p, critic_obs != nullptr, generic)) return rc;
+  const float* cobs = critic_obs ? critic_obs : (batch ? batch->obs : nullptr);
+  float* cxt0 = critic_xt0 ? critic_xt0 : (work ? work->xt0 : nullptr);
+  if (int rc = grad_stage1_check(fn, p, batch, cobs, work, cxt0)) return rc;
+  if (!diag) return fail_in(fn, SOLORL_ERR_INVALID, "null diag");
+  if (int rc = named(fn, use_device(device_id))) return rc;
+  return generic ? grad_stage1_w_dispatch(fn, p, batch, cobs, work, cxt0, diag, device_id, stream)
+                 : named(fn, grad_stage1_dispatch(fn, p, batch, cobs, work, cxt0, diag, device_id, stream));
+}
+
+int solorl_ppo_clip_adam_kl(const solorl_policy_params* p, const solorl_ppo_grads* g, const solorl_adam_state* a, const solorl_kl_control* k, int generic,
+                            int device_id, void* stream) {
+  const char* fn = "solorl_ppo_clip_adam_kl";
+  if (int rc = check_policy_kl(fn, p, -1, generic)) return rc;
+  AdamArgs K;
+  if (int rc = clip_adam_args(fn, p, g, a, K)) return rc;
+  if (!k) return fail_in(fn, SOLORL_ERR_INVALID, "null argument");
+  if (!k->diag || !k->state || !k->lr) return fail_in(fn, SOLORL_ERR_INVALID, "null diag, state or lr");
+  if (reinterpret_cast<uintptr_t>(k->diag) & 7u) return fail_in(fn, SOLORL_ERR_INVALID, "diag must be 8-byte aligned (its rows are read as float2)");
+  if (k->lr != a->lr) return fail_in(fn, SOLORL_ERR_INVALID, "k->lr must be a->lr: the controller rewrites the learning rate this step reads");
+  if (k->m < 32 || k->m % 32 != 0) return fail_in(fn, SOLORL_ERR_INVALID, "k->m must be the mini-batch's m, a multiple of 32 rows (diag holds m / 32 rows)");
+  if (a->offset && a->offset_increment != k->m)
+    return fail_in(fn, SOLORL_ERR_INVALID, "k->m is not the batch's m: the cursor a->offset advances by another number of rows (offset_increment)");
+  if (!(k->lr_factor > 1.0f)) return fail_in(fn, SOLORL_ERR_INVALID, "lr_factor must be > 1");
+  if (!(k->lr_min <= k->lr_max)) return fail_in(fn, SOLORL_ERR_INVALID, "lr_min must not exceed lr_max");
+  if (k->log && k->log_capacity < 1) return fail_in(fn, SOLORL_ERR_INVALID, "log is given with log_capacity < 1");
+  if (int rc = named(fn, use_device(device_id))) return rc;
+  const KlArgs Q = {k->diag, k->m / 32, (float)k->m, k->desired_kl, k->lr_factor, k->lr_min, k->lr_max, k->target_kl, k->lr, k->state, k->log, k->log ? k->log_capacity : 0};
+  if (generic)
+    return dispatch_act_dim(p->act_dim, [&](auto ac) {
+      hipLaunchKernelGGL((ppo_clip_adam_w_kl_kernel<decltype(ac)::value>), dim3(1), dim3(1024), 0, (hipStream_t)stream, K, Q);
+      return hipGetLastError() == hipSuccess ? 0 : fail_in(fn, SOLORL_ERR_HIP, "ppo_clip_adam_w_kl_kernel launch");
+    });
+  return named(fn, dispatch_dims(p->obs_dim, critic_width(p), p->act_dim, [&](auto oc, auto cc, auto ac) {
+    hipLaunchKernelGGL((ppo_clip_adam_kl_kernel<decltype(oc)::value, decltype(cc)::value, decltype(ac)::value>), dim3(1), dim3(1024), 0, (hipStream_t)stream, K, Q);
+    return hipGetLastError() == hipSuccess ? 0 : fail_in(fn, SOLORL_ERR_HIP, "ppo_clip_adam_kl_kernel launch");
+  }));
 }
 
 }  // extern "C"

@@ -202,7 +202,8 @@ class MiniBatchGrad:
     loss.backward() (agents/ppo/ppo.py:46-74) in a different summation order."""
     SLICE = 64                        # mini-batch rows must fill whole wavefronts
 
-    def __init__(self, actor_critic, storage, mini_batch, clip, value_coef, entropy_coef, clipped_value, perm, offset, adv, family=TEMPLATED):
+    def __init__(self, actor_critic, storage, mini_batch, clip, value_coef, entropy_coef, clipped_value, perm, offset, adv, family=TEMPLATED,
+                 diagnostics=False):
         n, m = storage.num_samples, mini_batch
         assert m % self.SLICE == 0, "mini-batch must be a multiple of %d rows" % self.SLICE
         dev = storage.device
@@ -234,6 +235,8 @@ class MiniBatchGrad:
         W = self.W = _native.PpoStage1()
         for k, t in self.buf.items():
             setattr(W, k, t.data_ptr())
+        # diagnostics: stage 1 through solorl_ppo_grad_stage1_kl, which also leaves per 32 rows (sum of the KL estimate, clipped rows)
+        self.diag = torch.zeros(m // 32, 2, device=dev) if diagnostics else None
         self.psum = torch.zeros(3 + A, device=dev)          # running sums of the partials over the steps of an update
         self.ent = torch.zeros(1, device=dev)               # running sum of sum_a logstd_a
         L = _native.lib()
@@ -250,7 +253,12 @@ class MiniBatchGrad:
         dev = self.psum.device
         with torch.cuda.device(dev):
             st = _native.stream(dev)
-            _call(self.P, "solorl_ppo_grad_stage1", [C.byref(self.B), C.byref(self.W), dev.index or 0, st], {1: self.cobs, 3: self.cxt0})
+            if self.diag is not None:
+                crit = lambda t: C.c_void_p(t.data_ptr() if self.OC else None)
+                _native.check(_native.lib().solorl_ppo_grad_stage1_kl(C.byref(self.P), C.byref(self.B), crit(self.cobs), C.byref(self.W), crit(self.cxt0),
+                                                                      C.c_void_p(self.diag.data_ptr()), int(self.P.family == GENERIC), dev.index or 0, st))
+            else:
+                _call(self.P, "solorl_ppo_grad_stage1", [C.byref(self.B), C.byref(self.W), dev.index or 0, st], {1: self.cobs, 3: self.cxt0})
             _call(self.P, "solorl_ppo_grad_stage2", [C.byref(self.W), self.m, C.byref(self.G), dev.index or 0, st], {1: self.cxt0})
 
     def losses(self, steps):
@@ -268,7 +276,8 @@ class ClipAdam:
     (solorl_ppo_clip_adam) instead of nine; also advances the mini-batch cursor.  The learning rate is read from `lr`, a device
     tensor (the linear schedule rewrites it between updates); moments and the step count live here."""
 
-    def __init__(self, mini_batch_grad, lr, max_grad_norm, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, offset=None, offset_increment=0, grad_scale=1.0):
+    def __init__(self, mini_batch_grad, lr, max_grad_norm, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, offset=None, offset_increment=0, grad_scale=1.0,
+                 kl_control=None):
         mb = mini_batch_grad
         dev = mb.psum.device
         L = _native.lib()
@@ -286,10 +295,44 @@ class ClipAdam:
         S.max_grad_norm = float(max_grad_norm) if max_grad_norm is not None else 0.0
         S.grad_scale = float(grad_scale)     # 1 / world: the gradients arrive SUMMED over the ranks (FlatGradBucket.all_reduce_sum)
         self._offset = offset
+        # kl_control = dict(desired_kl, target_kl, lr_factor, lr_bounds, log_capacity), each optional: the step through
+        # solorl_ppo_clip_adam_kl, which reads the mini-batch's KL from the diagnostics of `mini_batch_grad` and adapts lr / stops on it
+        # (include/solorl.h has the rule).  An empty dict only measures: state and log are filled, nothing is decided.
+        self.K = None
+        if kl_control is not None:
+            assert mb.diag is not None, "kl_control needs MiniBatchGrad(..., diagnostics=True)"
+            unknown = set(kl_control) - {"desired_kl", "target_kl", "lr_factor", "lr_bounds", "log_capacity"}
+            assert not unknown, "unknown kl_control keys %s" % sorted(unknown)
+            cap = int(kl_control.get("log_capacity", 0))
+            self.kl_state = torch.zeros(8, device=dev)
+            self.kl_log = torch.zeros(cap, 4, device=dev) if cap > 0 else None
+            lo, hi = kl_control.get("lr_bounds", (1e-5, 1e-2))
+            K = self.K = _native.KlControl()
+            K.diag, K.m, K.lr, K.state = mb.diag.data_ptr(), mb.m, lr.data_ptr(), self.kl_state.data_ptr()
+            K.desired_kl, K.target_kl = float(kl_control.get("desired_kl") or 0.0), float(kl_control.get("target_kl") or 0.0)
+            K.lr_factor, K.lr_min, K.lr_max = float(kl_control.get("lr_factor", 1.5)), float(lo), float(hi)
+            K.log, K.log_capacity = (self.kl_log.data_ptr() if cap > 0 else None), cap
+            self._keep_diag = mb.diag
 
     def __call__(self):
         with torch.cuda.device(self.dev):
+            if self.K is not None:
+                _native.check(_native.lib().solorl_ppo_clip_adam_kl(C.byref(self.P), C.byref(self.G), C.byref(self.S), C.byref(self.K),
+                                                                    int(self.P.family == GENERIC), self.dev.index or 0, _native.stream(self.dev)))
+                return
             _call(self.P, "solorl_ppo_clip_adam", [C.byref(self.G), C.byref(self.S), self.dev.index or 0, _native.stream(self.dev)], {}, both_forms=True)
 
     def zero_state(self):
         self.exp_avg.zero_(); self.exp_avg_sq.zero_(); self.step.zero_()
+
+    def clear_kl(self):
+        """the controller's state (the stopped flag with it) and log, at the start of an update"""
+        self.kl_state.zero_()
+        if self.kl_log is not None:
+            self.kl_log.zero_()
+
+    def kl_diagnostics(self):
+        """what the controller saw since clear_kl(): means over the steps seen, the lr last used, the step counts"""
+        seen, applied, skl, scf, stopped, _kl, _cf, lr = self.kl_state.tolist()
+        n = max(seen, 1.0)
+        return dict(approx_kl=skl / n, clip_fraction=scf / n, lr=lr, steps=int(seen), steps_applied=int(applied), stopped=bool(stopped))

@@ -209,9 +209,11 @@ class GraphedPPO(PPO):
     device tensor (update_linear_schedule fills it), otherwise the arithmetic is PPO.update's."""
 
     def __init__(self, actor_critic, clip_param, ppo_epoch, mini_batch_size, value_loss_coef, entropy_coef, lr=None,
-                 l2_coef=0.0, max_grad_norm=None, use_clipped_value_loss=True, fused_loss=True, fused_mlp=True):
+                 l2_coef=0.0, max_grad_norm=None, use_clipped_value_loss=True, fused_loss=True, fused_mlp=True, desired_kl=None, target_kl=None,
+                 diagnostics=False, lr_factor=1.5, lr_bounds=(1e-5, 1e-2)):
         super().__init__(actor_critic, clip_param, ppo_epoch, mini_batch_size, value_loss_coef, entropy_coef, lr=lr,
-                         l2_coef=l2_coef, max_grad_norm=max_grad_norm, use_clipped_value_loss=use_clipped_value_loss)
+                         l2_coef=l2_coef, max_grad_norm=max_grad_norm, use_clipped_value_loss=use_clipped_value_loss, desired_kl=desired_kl,
+                         target_kl=target_kl, diagnostics=diagnostics, lr_factor=lr_factor, lr_bounds=lr_bounds)
         self.fused_loss = fused_loss
         # hand-written mini-batch kernel (csrc/solorl_ppo.hip) where it is built for this policy's shape; otherwise autograd
         self._family = _policy_family(actor_critic) if fused_mlp else None
@@ -240,16 +242,45 @@ class GraphedPPO(PPO):
         self._ar = torch.arange(m, device=dev)
         self._stats = torch.zeros(3, device=dev)
         clip = self.clip_param
+        kl = self.kl                          # KL control (kl_control.py); kl.on False: nothing below is allocated or called differently
+        kl_steps = self.ppo_epoch * (n // m)  # mini-batch steps of an update = rows of the step log
+        kw = dict(diagnostics=True) if kl.on else {}
         self._mb = None
         if self.fused_mlp and m % MiniBatchGrad.SLICE == 0:
             self._mb = MiniBatchGrad(self.actor_critic, storage, m, clip, self.value_loss_coef, self.entropy_coef, self.use_clipped_value_loss,
-                                     self._perm, self._off, self._adv, family=self._family)
+                                     self._perm, self._off, self._adv, family=self._family, **kw)
+        self._kl_state = self._kl_log = None
+        if kl.on and self._mb is None:
+            # the autograd path: the rule as torch ops on the capturable Adam's lr tensor.  That optimizer cannot skip a step
+            if kl.target_kl:
+                raise NotImplementedError("target_kl needs the mini-batch kernels (a policy shape they are built for, or --generic-policy-kernels) "
+                                          "or the eager update (--no-hip-graphs): the captured PyTorch optimizer cannot skip a step")
+            t32 = lambda v: torch.tensor(float(v), dtype=torch.float32, device=dev)
+            d = kl.desired_kl or 0.0
+            self._kl_state, self._kl_log = torch.zeros(8, device=dev), torch.zeros(max(kl_steps, 1), 4, device=dev)
+            self._kl_c = dict(f=t32(kl.lr_factor), lr_min=t32(kl.lr_bounds[0]), lr_max=t32(kl.lr_bounds[1]), hi=t32(d) * 2.0, lo=t32(d) / 2.0,
+                              one=t32(1.0))
+
+        def kl_ops(ratio, logp, old_lp_b):
+            with torch.no_grad():
+                c, st, lr_t = self._kl_c, self._kl_state, self.optimizer.param_groups[0]["lr"]
+                k = ((ratio - 1.0) - (logp - old_lp_b)).mean()
+                cf = ((ratio < 1.0 - clip) | (ratio > 1.0 + clip)).float().mean()
+                if kl.desired_kl:
+                    fin = torch.isfinite(k)
+                    shrink, grow = fin & (k > c["hi"]), fin & (k < c["lo"]) & (k > 0)
+                    lr_t.copy_(torch.where(shrink, torch.maximum(c["lr_min"], lr_t / c["f"]),           # (a tensor divisor: a true division)
+                                           torch.where(grow, torch.minimum(c["lr_max"], lr_t * c["f"]), lr_t)))
+                row = torch.stack([k, cf, lr_t.reshape(()), c["one"]])
+                self._kl_log.index_copy_(0, st[0:1].long().clamp(max=self._kl_log.shape[0] - 1), row.unsqueeze(0))
+                st[0:4] += torch.stack([c["one"], c["one"], k, cf])
+                st[5:8] = row[:3]
 
         self._ca = None
         if self._mb is not None:             # norm clip + Adam + cursor in one launch; lr stays the optimizer's device tensor
             g0 = self.optimizer.param_groups[0]
             self._ca = ClipAdam(self._mb, g0["lr"], self.max_grad_norm, weight_decay=g0["weight_decay"], betas=g0["betas"], eps=g0["eps"],
-                                offset=self._off, offset_increment=m)
+                                offset=self._off, offset_increment=m, **(dict(kl_control=kl.as_dict(log_capacity=kl_steps)) if kl.on else {}))
 
         def fwd_bwd():
             if self._mb is not None:     # three launches: gather + forward + losses + back-propagation; weight gradients; their sum
@@ -260,13 +291,15 @@ class GraphedPPO(PPO):
             obs_b, act_b, vpred_b, ret_b, old_lp_b = (s.index_select(0, idx) for s in self._src)
             adv_b = self._adv.index_select(0, idx)
             critic = {} if self._csrc is None else {"critic_inputs": self._csrc.index_select(0, idx)}
-            if self.fused_loss:       # one HIP launch for log-prob, both losses and their head gradients (ppo/fused.py)
+            if self.fused_loss and not kl.on:       # one HIP launch for log-prob, both losses and their head gradients (ppo/fused.py)
                 values, mean, logstd = self.actor_critic.heads(obs_b, **critic)
                 loss, value_loss, action_loss, entropy = fused_ppo_loss(mean, logstd, values, act_b, old_lp_b, adv_b, vpred_b, ret_b, clip,
                                                                         self.value_loss_coef, self.entropy_coef, self.use_clipped_value_loss)
             else:
                 values, logp, entropy = self.actor_critic.evaluate_actions(obs_b, act_b, **critic)
                 ratio = torch.exp(logp - old_lp_b)
+                if kl.on:             # (these expressions have logp, the fused loss does not)
+                    kl_ops(ratio, logp, old_lp_b)
                 action_loss = -torch.min(ratio * adv_b, torch.clamp(ratio, 1.0 - clip, 1.0 + clip) * adv_b).mean()
                 if self.use_clipped_value_loss:
                     v_clipped = vpred_b + (values - vpred_b).clamp(-clip, clip)
@@ -292,6 +325,7 @@ class GraphedPPO(PPO):
         # warm-up on a side stream (allocator, autograd and optimizer state), then put everything back
         params = [p for p in self.actor_critic.parameters()]
         saved = [p.detach().clone() for p in params]
+        lr_saved = self.optimizer.param_groups[0]["lr"].detach().clone()     # (the warm-up steps may adapt it)
         self._perm.copy_(torch.randperm(n, device=dev, generator=torch.Generator(device=dev).manual_seed(0)))   # (own generator: the
                                                                                    # global RNG stream stays the eager path's)
         def warm():
@@ -308,6 +342,8 @@ class GraphedPPO(PPO):
                         v.zero_()
             if self._ca is not None:
                 self._ca.zero_state()
+            self.optimizer.param_groups[0]["lr"].copy_(lr_saved)
+        self._kl_clear()
         self._stats.zero_(); self._off.zero_()
         if self._mb is not None:
             self._mb.reset()
@@ -341,6 +377,12 @@ class GraphedPPO(PPO):
             self._stats.zero_(); self._off.zero_()
         self._built_for = (id(storage), n, m)
 
+    def _kl_clear(self):
+        if self._ca is not None and self._ca.K is not None:
+            self._ca.clear_kl()
+        if self._kl_state is not None:
+            self._kl_state.zero_(); self._kl_log.zero_()
+
     def _collective_is_capturable(self, dev):
         """Whether the bucket all-reduce goes INSIDE the captured mini-batch step.  Opt-in (SOLORL_CAPTURE_ALLREDUCE=1) until a real
         multi-GPU run has exercised it: no box of this project has had two GPUs, so the split form (graph -> eager all-reduce -> graph)
@@ -363,8 +405,12 @@ class GraphedPPO(PPO):
         self._stats.zero_()
         if self._mb is not None:
             self._mb.reset()
+        if self.kl.on:
+            self._kl_clear()
         n_updates = 0
         for _ in range(self.ppo_epoch):
+            if self.kl.target_kl and self._ca.kl_state[4].item() != 0.0:     # stopped: what is left would be replays that apply nothing
+                break
             self._perm.copy_(torch.randperm(n, device=storage.device))
             self._off.zero_()
             for _s in range(0, n - m + 1, m):
@@ -373,6 +419,12 @@ class GraphedPPO(PPO):
                     self._reduce()
                     self._g2.replay()
                 n_updates += 1
+        if self.kl.on:
+            state, log = (self._ca.kl_state, self._ca.kl_log) if self._mb is not None else (self._kl_state, self._kl_log)
+            seen, applied, skl, scf, stopped, _k, _c, lr = state.tolist()
+            self.last_diagnostics = dict(approx_kl=skl / max(seen, 1.0), clip_fraction=scf / max(seen, 1.0), lr=lr, steps=int(seen),
+                                         steps_applied=int(applied), stopped=bool(stopped))
+            self.last_step_log = log[:int(seen)].cpu()
         if self._mb is not None:
             return self._mb.losses(n_updates)
         v, a, e = (self._stats / max(n_updates, 1)).tolist()

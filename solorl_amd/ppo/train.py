@@ -115,6 +115,15 @@ def train(args, config, env_constructor=None, writer=None):
         # every rank would keep statistics of its own shard and the policies would drift apart; merging moments across ranks is not built
         raise NotImplementedError("--normalize-obs / --normalize-returns need a single process (world size %d): the running statistics "
                                   "are not merged across ranks" % world)
+    # PPO KL control (ppo/kl_control.py): --desired-kl, --target-kl, --ppo-diagnostics; all off: no argument more goes to the agent
+    kl_args = {k: v for k, v in (("desired_kl", getattr(args, "desired_kl", None)), ("target_kl", getattr(args, "target_kl", None)),
+                                 ("diagnostics", bool(getattr(args, "ppo_diagnostics", False)))) if v}
+    if kl_args.get("desired_kl") and args.use_linear_lr_decay:
+        raise ValueError("--desired-kl with --use-linear-lr-decay: two schedules for one learning rate")
+    if world > 1 and kl_args:
+        # the KL sums are per rank: the ranks would adapt different rates and stop at different steps
+        raise NotImplementedError("--desired-kl / --target-kl / --ppo-diagnostics need a single process (world size %d): the KL sums "
+                                  "are not merged across ranks" % world)
     envs = make_vec_envs(config, N, env_constructor, args.gamma, device, seed=args.seed, env_id_offset=rank * N,
                          norm_obs=norm_obs, norm_ret=norm_ret, push_interval=getattr(args, "push_interval", None),
                          push_max_vel=getattr(args, "push_max_vel", 0.0), push_max_yaw_rate=getattr(args, "push_max_yaw_rate", 0.0),
@@ -135,7 +144,7 @@ def train(args, config, env_constructor=None, writer=None):
     use_graphs = bool(args.cuda) and not getattr(args, "no_hip_graphs", False)
     agent = (GraphedPPO if use_graphs else PPO)(actor_critic, args.clip_param, args.ppo_epoch, args.mini_batch_size,
                                                  args.value_loss_coef, args.entropy_coef, lr=args.lr, l2_coef=args.l2_coef,
-                                                 max_grad_norm=args.max_grad_norm)
+                                                 max_grad_norm=args.max_grad_norm, **kl_args)
     bootstrap = bool(getattr(args, "bootstrap_timeouts", False))
     storage = RolloutStorage(args.num_steps, N, envs.observation_space.shape, action_dim, device, critic_obs_dim=critic_dim,
                              bootstrap_timeouts=bootstrap)
@@ -187,6 +196,9 @@ def train(args, config, env_constructor=None, writer=None):
                 rec.update({k: v for k, v in envs.shaping_stats(reset=True).items() if k.startswith("sr/")})
             if termination:                           # this rank's finished episodes: the share each rule ended
                 rec.update(envs.termination_stats(reset=True))
+            if kl_args:                               # the last update's mini-batch steps: mean KL estimate and clip fraction, the rate last used
+                dg = agent.last_diagnostics
+                rec.update(approx_kl=dg["approx_kl"], clip_fraction=dg["clip_fraction"], lr=dg["lr"], kl_stopped_steps=dg["steps"] - dg["steps_applied"])
             history.append(rec)
             if rank == 0:
                 print("Updates {update}, num timesteps {timesteps}, FPS {fps}\n mean reward {ep_reward:.2f} mean length "
@@ -194,6 +206,8 @@ def train(args, config, env_constructor=None, writer=None):
                       "action loss {action_loss:.3f}".format(**rec), flush=True)
                 if writer is not None:
                     for k in ("value_loss", "action_loss", "entropy", "ep_reward", "ep_length", "success"):
+                        writer.add_scalar(k, rec[k], total)
+                    for k in ("approx_kl", "clip_fraction", "lr", "kl_stopped_steps") if kl_args else ():
                         writer.add_scalar(k, rec[k], total)
                     for k in rec:
                         if k.startswith(("dr/", "sr/", "term/")):   # agents/ppo/train.py:98-100, utils.log of the dr/ deques; sr/: shaped terms; term/: early terminations

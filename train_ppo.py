@@ -172,6 +172,13 @@ def get_ppo_args(argv=None):
                    help="run a policy shape the per-shape policy kernels are not built for (e.g. --commands with a history level: 79 wide) on "
                         "the width-generic kernels instead of the PyTorch path: any observation and critic width up to 128 "
                         "(sets SOLORL_POLICY_GENERIC=1; default: off)")
+    p.add_argument("--desired-kl", type=float, default=None, metavar="D",
+                   help="adaptive learning rate: after every mini-batch step's KL estimate, lr / 1.5 above 2 D and lr * 1.5 below D / 2, within "
+                        "[1e-5, 1e-2] (rsl_rl's schedule, decided on the device; not with --use-linear-lr-decay; default: off)")
+    p.add_argument("--target-kl", type=float, default=None, metavar="K",
+                   help="end an update's mini-batch steps once the KL estimate exceeds 1.5 K (stable-baselines' target_kl; default: off)")
+    p.add_argument("--ppo-diagnostics", action="store_true", default=False,
+                   help="log approx_kl, clip_fraction and lr of every update (on by itself with --desired-kl / --target-kl; default: off)")
     p.add_argument("--num-steps", type=int, default=None, help="rollout length (default: episode_length, train_ppo.py:62-63)")
     return p.parse_args(argv)
 
